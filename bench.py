@@ -24,7 +24,12 @@ frame into contiguous shards; rank r owns its rows of EVERY frame of the batch.
     beyond the halo.  All inside the timed region.
 Both legs: W untimed warmup steps, then exactly K steps between barrier + device sync, MAX over ranks.
 
-Launch: python bench.py [--steps K --warmup W]            (1 GPU)
+A plain run times the headline leg only and prints its line (`value`, `ms_per_step` = milliseconds of one timed step, the
+per-kernel statistics and roofline of the same launches).  --full adds the determinism re-launch of the headline leg, the shard
+leg, the reference's own benchmark workload, the encoder leg and the CPU baseline.  --dump-outputs DIR writes the last timed
+step's outputs (dump_outputs); the inputs depend on the arguments only.
+
+Launch: python bench.py [--steps K --warmup W] [--full] [--dump-outputs DIR]      (1 GPU)
         python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -286,7 +291,9 @@ def collect_event_ms(env, evs):
     return ms
 
 
-def headline_leg(env, steps, warmup, frames):
+def headline_leg(env, steps, warmup, frames, check=False):
+    """-> (seconds of the K timed steps, per-launch event ms, blocks per launch, the last step's outputs {name: tensor});
+    check: also re-launch satd_8x8 once after the timed steps and require identical costs (--full)"""
     torch, dev = env.torch, env.dev
     n8, n32 = BLK8_PER_FRAME * frames, BLK32_PER_FRAME * frames
     gen = torch.Generator(device=dev); gen.manual_seed(SEED + env.rank)
@@ -303,13 +310,38 @@ def headline_leg(env, steps, warmup, frames):
     launch = three_kernel_step(env, cur, ref, res, sad, satd, coef, n8, n32)
     dt = env.timed(lambda k: launch(evs[k] if k is not None else None), steps, warmup)
     ms = collect_event_ms(env, evs)
-    # light integrity property at full size (parity proper lives in tests/): a second launch gives identical costs
-    satd2 = torch.empty_like(satd)
-    env.check(env.L.kvz_hip_satd_nxn_batch(8, cur.data_ptr(), ref.data_ptr(), n8, satd2.data_ptr(), env.stream), "satd_8x8")
-    env.sync()
-    assert bool((satd2 == satd).all()), "non-deterministic satd"
+    if check:
+        # light integrity property at full size (parity proper lives in tests/): a second launch gives identical costs
+        satd2 = torch.empty_like(satd)
+        env.check(env.L.kvz_hip_satd_nxn_batch(8, cur.data_ptr(), ref.data_ptr(), n8, satd2.data_ptr(), env.stream), "satd_8x8")
+        env.sync()
+        assert bool((satd2 == satd).all()), "non-deterministic satd"
     blocks = {"sad_8x8": n8, "satd_8x8": n8, "dct_32x32": n32}
-    return dt, ms, blocks
+    return dt, ms, blocks, {"sad_8x8": sad, "satd_8x8": satd, "dct_32x32": coef}
+
+
+DUMP_MAX_ELEMS = 1 << 22        # per array: 16 MiB of float32, three arrays -> at most 48 MiB per --dump-outputs directory
+
+
+def dump_outputs(env, out_dir, outs):
+    """--dump-outputs DIR: the arrays a caller of the timed path receives from its last step, as DIR/<name>.npy in float32
+    (every value is an integer below 2^24, so the conversion is exact): sad_8x8 / satd_8x8 [n8] costs, dct_32x32 [n32, 32, 32]
+    coefficients.  An array of more than DUMP_MAX_ELEMS values keeps a fixed sample of its blocks (first axis): the sorted
+    indices np.random.default_rng(SEED).choice(n, k, replace=False), the same for the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    env.sync()
+    for name in NAMES:
+        t = outs[name]
+        n, per = t.shape[0], t[0].numel()
+        k = min(n, max(1, DUMP_MAX_ELEMS // per))
+        if k < n:
+            idx = np.sort(np.random.default_rng(SEED).choice(n, k, replace=False))
+            t = t[env.torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy().astype(np.float32)
+        if name == "dct_32x32":
+            a = a.reshape(-1, 32, 32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def shard_kernel_leg(env, sh, steps, warmup, frames, partition):
@@ -662,12 +694,23 @@ def main():
     ap.add_argument("--no-reference-workload", action="store_true", help="skip the leg that runs the reference's own benchmark patterns (tests/speed_tests.c)")
     ap.add_argument("--partition", choices=("spans", "rows"), default="spans",
                     help="shard_4k block-kernel leg: raster spans of CTUs (equal to within one CTU) or whole CTU rows")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg: its determinism check, the shard_4k leg, the reference workload, the encoder leg "
+                         "and the CPU baseline (each can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; rank 0)")
     args = ap.parse_args()
     env = Env(args)
     torch, world, rank = env.torch, env.world, env.rank
     F = args.frames
 
-    dt, ms, blocks = headline_leg(env, args.steps, args.warmup, F)
+    dt, ms, blocks, outs = headline_leg(env, args.steps, args.warmup, F, check=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs, outs)
+    del outs
+    if not args.full:
+        # a plain run: the headline line and nothing else
+        args.no_cpu_baseline = args.no_shard_leg = args.no_encoder_leg = args.no_reference_workload = True
     torch.cuda.empty_cache()
     ref_workload = None
     if world == 1 and not args.no_reference_workload:
@@ -706,7 +749,7 @@ def main():
             "metric": "Mblocks/s (SAD8/SATD8/DCT32) per GPU",
             "value": round(total_blocks / dt / 1e6, 1),
             "unit": "Mblocks/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(dt / args.steps * 1e3, 5),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic",

@@ -19,7 +19,7 @@ def _run(n, port):
     env = dict(os.environ, KVZ_BENCH_SHARE_DEVICE="1", KVZ_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "4", "--warmup", "1",
-           "--frames", "16", "--frames-4k", "16", "--search-frames", "2", "--no-cpu-baseline", "--no-encoder-leg", "--no-reference-workload"]
+           "--frames", "16", "--frames-4k", "16", "--search-frames", "2", "--full", "--no-cpu-baseline", "--no-encoder-leg", "--no-reference-workload"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

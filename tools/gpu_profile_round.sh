@@ -1,6 +1,6 @@
 #!/bin/bash
 # End-of-work profile set of one build, written under gpurun_out/TAG_* (copy what is to be judged into profiles/):
-#   0. bench.py with the driver's exact command, `python3 bench.py --gpus 1 --steps 20 --warmup 5` (no profiler): TAG_bench.json
+#   0. bench.py with the driver's arguments and every leg, `python3 bench.py --gpus 1 --steps 20 --warmup 5 --full` (no profiler): TAG_bench.json
 #   1. the same command with the legs that launch the same kernels on other batches switched off (--no-shard-leg
 #      --no-reference-workload --no-encoder-leg) under rocprofv3 --kernel-trace --stats: TAG_bench_profiled.json + TAG_kernel_stats.csv,
 #      so that a kernel's average in the CSV is the average of the launches the bench line's roofline describes; with every leg on:
@@ -19,13 +19,13 @@ export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O/${TAG}_prof
 if [ "${3:-}" != "service" ]; then       # `service`: step 7 only (the search service and the served encodes)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_prof/bench.log
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${TAG}_bench.json 2> $O/${TAG}_prof/bench.log
 ONLY="--no-shard-leg --no-reference-workload --no-encoder-leg"
 rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof/stats -o p --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 $ONLY > $O/${TAG}_bench_profiled.json 2> $O/${TAG}_prof/stats.log
 cp $O/${TAG}_prof/stats/p_kernel_stats.csv $O/${TAG}_kernel_stats.csv
 python3 tools/trace_launches.py $O/${TAG}_prof/stats/p_kernel_trace.csv > $O/${TAG}_kernel_trace_summary.txt 2>&1 || true
 rm -rf $O/${TAG}_prof/stats
-rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof/stats2 -o p --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-encoder-leg > $O/${TAG}_bench_profiled_all_legs.json 2> $O/${TAG}_prof/stats2.log
+rocprofv3 --kernel-trace --stats -d $O/${TAG}_prof/stats2 -o p --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-encoder-leg > $O/${TAG}_bench_profiled_all_legs.json 2> $O/${TAG}_prof/stats2.log
 cp $O/${TAG}_prof/stats2/p_kernel_stats.csv $O/${TAG}_kernel_stats_all_legs.csv
 rm -rf $O/${TAG}_prof/stats2
 B="python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline $ONLY"
