@@ -140,6 +140,41 @@ typedef struct {
 } kvz_hip_shard_plane;
 KVZ_HIP_API int kvz_hip_halo_exchange(const kvz_hip_shard_plane *self, const kvz_hip_shard_plane *up, const kvz_hip_shard_plane *down,
                                       uint32_t stride, int margin, kvz_hip_stream s);
+/* A batch of 2-D byte rectangles copied by ONE kernel launch on stream s of the calling thread's current device: rect i copies h rows
+ * of w bytes from src (rows src_stride bytes apart) to dst (rows dst_stride bytes apart).  The rects travel as a kernel argument (no
+ * upload), so n is at most KVZ_HIP_MAX_RECTS.  The pointers may be device memory of the current device or of a peer device whose
+ * access is enabled (kvz_hip_tile_halo_exchange / kvz_hip_memcpy_peer enable it); any alignment and width is accepted, 16-byte
+ * accesses are used where both pointers and both strides are multiples of 16.  A rect with w == 0 or h == 0 is skipped.  Sources and
+ * destinations must not overlap.  KVZ_HIP_ERR_INVALID: n outside 0..KVZ_HIP_MAX_RECTS, rects NULL with n > 0, a negative w / h, a
+ * NULL pointer or a stride < w in a non-empty rect (with h > 1), a batch of 2^31 or more 16-byte chunks, a stream of another device.
+ * Uses: packing halo strips into contiguous staging, unpacking them into an extended buffer, copying a tile's own rectangle into
+ * its extended buffer (a strided copy kvz_hip_memcpy_d2d cannot do). */
+#define KVZ_HIP_MAX_RECTS 16
+typedef struct {
+  const void *src;
+  void *dst;
+  uint32_t src_stride, dst_stride;    /* bytes */
+  int32_t w, h;                       /* bytes per row, rows */
+} kvz_hip_rect_copy;                  /* 32 bytes */
+KVZ_HIP_API int kvz_hip_copy_rects_batch(const kvz_hip_rect_copy *rects, int n, kvz_hip_stream s);
+/* The exchange step of a frame cut into TILES in both directions (kvazaar_amd/shard.py TileShard / exchange_tile_halo_into) for a host
+ * that drives its tiles from one process.  A tile's plane is an EXTENDED buffer on `device`: the rectangle (ext_x, ext_y, ext_w, ext_h)
+ * of the frame, rows `stride` bytes apart; the tile's own rectangle (own_x, own_y, own_w, own_h), also in frame coordinates, lies
+ * inside it.  The calling thread's tile PUSHES, for every neighbour, the pixels of the intersection of self.own and neighbour.ext to the same frame position
+ * in the neighbour's buffer: up to 8 neighbours (left, right, above, below and the four corners), all regions in ONE launch of the
+ * kvz_hip_copy_rects_batch kernel on stream s of self->device; a neighbour on another device is written through peer access (enabled
+ * on first use).  A full-width row shard is the special case ext_x = own_x = 0, ext_w = own_w = width: the same bytes as
+ * kvz_hip_halo_exchange.  KVZ_HIP_ERR_INVALID: the calling thread does not work on self->device, n outside 0..8, neighbours NULL with
+ * n > 0, a NULL buffer, a stride < ext_w, an own rectangle outside its extended rectangle, own rectangles (self's and the neighbours')
+ * that overlap, a device that was not initialised, a stream of another device. */
+typedef struct {
+  void *ext;                          /* the tile's extended plane on `device` */
+  int32_t device;
+  uint32_t stride;                    /* bytes between rows of ext (>= ext_w) */
+  int32_t ext_x, ext_y, ext_w, ext_h; /* the extended rectangle, frame coordinates */
+  int32_t own_x, own_y, own_w, own_h; /* the own rectangle, frame coordinates, inside the extended one */
+} kvz_hip_tile_plane;                 /* 48 bytes */
+KVZ_HIP_API int kvz_hip_tile_halo_exchange(const kvz_hip_tile_plane *self, const kvz_hip_tile_plane *neighbours, int n, kvz_hip_stream s);
 KVZ_HIP_API kvz_hip_stream kvz_hip_stream_create(void);
 KVZ_HIP_API void kvz_hip_stream_destroy(kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_stream_sync(kvz_hip_stream s);

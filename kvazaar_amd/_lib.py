@@ -30,6 +30,22 @@ class QuantParams(C.Structure):
                 ("scaling_list", C.c_int32), ("quant_coeff", C.c_void_p), ("dequant_coeff", C.c_void_p)]
 
 
+class RectCopy(C.Structure):
+    """kvz_hip_rect_copy"""
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("src_stride", C.c_uint32), ("dst_stride", C.c_uint32),
+                ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class TilePlane(C.Structure):
+    """kvz_hip_tile_plane"""
+    _fields_ = [("ext", C.c_void_p), ("device", C.c_int32), ("stride", C.c_uint32),
+                ("ext_x", C.c_int32), ("ext_y", C.c_int32), ("ext_w", C.c_int32), ("ext_h", C.c_int32),
+                ("own_x", C.c_int32), ("own_y", C.c_int32), ("own_w", C.c_int32), ("own_h", C.c_int32)]
+
+
+MAX_RECTS = 16      # KVZ_HIP_MAX_RECTS
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -60,6 +76,8 @@ SIGNATURES = {
     "kvz_hip_memcpy_d2d": (_I, [_P, _P, _SZ, _P]),
     "kvz_hip_memcpy_peer": (_I, [_P, _I, _P, _I, _SZ, _P]),
     "kvz_hip_halo_exchange": (_I, [_P, _P, _P, _U, _I, _P]),
+    "kvz_hip_copy_rects_batch": (_I, [_P, _I, _P]),
+    "kvz_hip_tile_halo_exchange": (_I, [_P, _P, _I, _P]),
     "kvz_hip_stream_create": (_P, []),
     "kvz_hip_stream_destroy": (None, [_P]),
     "kvz_hip_stream_sync": (_I, [_P]),

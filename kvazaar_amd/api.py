@@ -508,6 +508,30 @@ def deblock_frame(y, u, v, cus, prm):
     return (dy.to_numpy(np.uint8, y.shape), du.to_numpy(np.uint8, u.shape) if du else None, dv.to_numpy(np.uint8, v.shape) if dv else None)
 
 
+# ---- tile halo exchange: batched rectangle copies on device pointers ----
+def copy_rects(rects, stream=None):
+    """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most
+    _lib.MAX_RECTS of them, copied by one launch on `stream` (a kvz_hip_stream / hipStream_t handle, None = the library's)."""
+    L = _lib.init()
+    rects = list(rects)
+    arr = (_lib.RectCopy * max(1, len(rects)))(*[_lib.RectCopy(*r) for r in rects])
+    check(L.kvz_hip_copy_rects_batch(arr, len(rects), stream), "copy_rects_batch")
+
+
+def tile_plane(ext_ptr, device, stride, ext_rect, own_rect):
+    """a kvz_hip_tile_plane record: ext_rect / own_rect = (x, y, w, h) in frame coordinates (TileShard.ext / .own)"""
+    return _lib.TilePlane(ext_ptr, device, stride, *(tuple(ext_rect) + tuple(own_rect)))
+
+
+def tile_halo_exchange(self_plane, neighbours, stream=None):
+    """kvz_hip_tile_halo_exchange: self_plane pushes its pixels into the extended buffers of `neighbours` (TilePlane records) in one
+    launch on `stream` of self_plane.device (the calling thread must work on it)."""
+    L = _lib.load()
+    nbs = list(neighbours)
+    arr = (_lib.TilePlane * max(1, len(nbs)))(*nbs)
+    check(L.kvz_hip_tile_halo_exchange(C.byref(self_plane), arr if nbs else None, len(nbs), stream), "tile_halo_exchange")
+
+
 # ---- search service: requests of many host threads in shared launches (include/kvz_hip.h, "search service") ----
 class MeService:
     """kvz_hip_me_service: resident luma planes in numbered slots + kvz_hip_me_service_search, callable from many threads."""

@@ -78,6 +78,19 @@ int invalid_arg(const char *entry)
   return KVZ_HIP_ERR_INVALID;
 }
 
+// a stream handed in by the caller must be a stream of the calling thread's current device
+int stream_on_current_device(kvz_hip_stream s, const char *entry)
+{
+  if (!s) return KVZ_HIP_OK;
+  hipDevice_t dev = -1;
+  if (hipStreamGetDevice((hipStream_t)s, &dev) != hipSuccess) { (void)hipGetLastError(); return KVZ_HIP_OK; }   // cannot tell: the copy itself will
+  if ((int)dev != ctx_device()) {
+    std::snprintf(g_err, sizeof(g_err), "%s: the stream belongs to device %d, the calling thread works on device %d", entry, (int)dev, ctx_device());
+    return KVZ_HIP_ERR_INVALID;
+  }
+  return KVZ_HIP_OK;
+}
+
 // brings up the context of one device (idempotent); g_mu held by the caller
 static int ctx_create_locked(int device)
 {
@@ -275,19 +288,6 @@ static int enable_peer(int cur, int other)
   return KVZ_HIP_OK;
 }
 
-// a stream handed in by the caller must be a stream of the calling thread's current device
-static int stream_on_current_device(kvz_hip_stream s, const char *entry)
-{
-  if (!s) return KVZ_HIP_OK;
-  hipDevice_t dev = -1;
-  if (hipStreamGetDevice((hipStream_t)s, &dev) != hipSuccess) { (void)hipGetLastError(); return KVZ_HIP_OK; }   // cannot tell: the copy itself will
-  if ((int)dev != ctx_device()) {
-    std::snprintf(g_err, sizeof(g_err), "%s: the stream belongs to device %d, the calling thread works on device %d", entry, (int)dev, ctx_device());
-    return KVZ_HIP_ERR_INVALID;
-  }
-  return KVZ_HIP_OK;
-}
-
 int kvz_hip_memcpy_peer(void *dst, int dst_device, const void *src, int src_device, size_t bytes, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
@@ -333,6 +333,67 @@ int kvz_hip_halo_exchange(const kvz_hip_shard_plane *self, const kvz_hip_shard_p
   }
   return KVZ_HIP_OK;
 }
+
+// The exchange of a frame cut into tiles in both directions (kvazaar_amd/shard.py exchange_tile_halo_into): the calling thread's
+// tile pushes self.own & neighbour.ext into every neighbour's buffer, all regions in one launch of the rectangle-copy kernel
+// (halo.hip).  See include/kvz_hip.h.
+namespace {
+struct frame_rect { int32_t x, y, w, h; };
+frame_rect intersect(frame_rect a, frame_rect b)
+{
+  const int32_t x0 = a.x > b.x ? a.x : b.x, y0 = a.y > b.y ? a.y : b.y;
+  const int64_t ax1 = (int64_t)a.x + a.w, bx1 = (int64_t)b.x + b.w, ay1 = (int64_t)a.y + a.h, by1 = (int64_t)b.y + b.h;
+  const int64_t x1 = ax1 < bx1 ? ax1 : bx1, y1 = ay1 < by1 ? ay1 : by1;
+  if (x1 <= x0 || y1 <= y0) return { x0, y0, 0, 0 };
+  return { x0, y0, (int32_t)(x1 - x0), (int32_t)(y1 - y0) };
+}
+frame_rect own_of(const kvz_hip_tile_plane &t) { return { t.own_x, t.own_y, t.own_w, t.own_h }; }
+frame_rect ext_of(const kvz_hip_tile_plane &t) { return { t.ext_x, t.ext_y, t.ext_w, t.ext_h }; }
+// a usable description: buffer, sizes, own rectangle inside the extended one, device initialised
+bool tile_plane_ok(const kvz_hip_tile_plane &t)
+{
+  if (!t.ext || t.device < 0 || t.device >= KVZ_MAX_DEVICES || !g_ctx[t.device].ready.load(std::memory_order_acquire)) return false;
+  if (t.ext_w < 0 || t.ext_h < 0 || t.own_w < 0 || t.own_h < 0 || t.stride < (uint32_t)t.ext_w) return false;
+  return t.own_x >= t.ext_x && t.own_y >= t.ext_y && (int64_t)t.own_x + t.own_w <= (int64_t)t.ext_x + t.ext_w &&
+         (int64_t)t.own_y + t.own_h <= (int64_t)t.ext_y + t.ext_h;
+}
+}  // namespace
+
+int kvz_hip_tile_halo_exchange(const kvz_hip_tile_plane *self, const kvz_hip_tile_plane *neighbours, int n, kvz_hip_stream s)
+{
+  KVZ_CHECK_CTX();
+  if (!self || !tile_plane_ok(*self) || self->device != ctx_device() || n < 0 || n > 8 || (n > 0 && !neighbours)) {
+    set_error_msg("kvz_hip_tile_halo_exchange: the calling thread must work on self->device, self must be a valid tile plane and "
+                  "there are at most 8 neighbours");
+    return KVZ_HIP_ERR_INVALID;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!tile_plane_ok(neighbours[i])) return kvzhip::invalid_arg(__func__);
+    if (intersect(own_of(*self), own_of(neighbours[i])).w > 0) return kvzhip::invalid_arg(__func__);
+    for (int j = 0; j < i; ++j)
+      if (intersect(own_of(neighbours[j]), own_of(neighbours[i])).w > 0) return kvzhip::invalid_arg(__func__);
+  }
+  int rc = stream_on_current_device(s, "kvz_hip_tile_halo_exchange");
+  if (rc != KVZ_HIP_OK) return rc;
+  const int cur = ctx_device();
+  kvz_hip_rect_copy rects[8];
+  int m = 0;
+  for (int i = 0; i < n; ++i) {
+    const kvz_hip_tile_plane &nb = neighbours[i];
+    const frame_rect r = intersect(own_of(*self), ext_of(nb));
+    if (r.w == 0 || r.h == 0) continue;
+    if ((rc = enable_peer(cur, nb.device)) != KVZ_HIP_OK) return rc;
+    rects[m].src = (const u8 *)self->ext + (size_t)(r.y - self->ext_y) * self->stride + (size_t)(r.x - self->ext_x);
+    rects[m].dst = (u8 *)nb.ext + (size_t)(r.y - nb.ext_y) * nb.stride + (size_t)(r.x - nb.ext_x);
+    rects[m].src_stride = self->stride;
+    rects[m].dst_stride = nb.stride;
+    rects[m].w = r.w;
+    rects[m].h = r.h;
+    ++m;
+  }
+  return copy_rects_launch(rects, m, ctx_stream(s), "kvz_hip_tile_halo_exchange");
+}
+
 kvz_hip_stream kvz_hip_stream_create(void)
 {
   if (!ctx_enter() && (kvz_hip_init(-1) != KVZ_HIP_OK || !ctx_enter())) return nullptr;

@@ -25,6 +25,11 @@ void set_error_msg(const char *what);
 int invalid_arg(const char *entry);             // records "<entry>: invalid argument" and returns KVZ_HIP_ERR_INVALID
 int num_cus();
 int tuning(const char *key, int dflt);     // kvz_hip_set_tuning override or dflt
+int stream_on_current_device(kvz_hip_stream s, const char *entry);   // KVZ_HIP_ERR_INVALID for a stream of another device
+
+// ---- rectangle copies (halo.hip) ----
+// checks rects[0 .. n) as kvz_hip_copy_rects_batch documents and copies them in one launch on st; errors are reported as `entry`'s
+int copy_rects_launch(const kvz_hip_rect_copy *rects, int n, hipStream_t st, const char *entry);
 
 #define KVZ_CHECK_CTX()                         \
   do {                                          \
