@@ -84,8 +84,8 @@ KVZ_HIP_API const char *kvz_hip_device_name(void);   /* of the calling thread's 
 KVZ_HIP_API int kvz_hip_abi_version(void);
 
 /* Launch-geometry / kernel-selection knobs for A/B runs (tools/bench_all.py --tune key=v1,v2);
- * value < 0 restores the built-in default.  Keys: "{sad,satd8,dct,dct16,idct16,dct32,idct32,qr,qr16,
- * qr32}_wgs_per_cu" (workgroups per CU of the streaming grids),
+ * value < 0 restores the built-in default.  Keys: "{sad,satd8,dct,dct4,idct4,dct16,idct16,dct32,idct32,quant,qr,qr4,qr8,
+ * qr16,qr32}_wgs_per_cu" (workgroups per CU of the streaming grids; 0 counts as 1),
  * "qr4_lane_kernel", "qr8_reg_kernel", "qr_tile_kernel" (0: the LDS butterfly kernel instead of the register / matrix-core ones), "dct4_tile" (0: the LDS butterfly kernel for 4x4 transforms), "sao_edge_fast" (0/1),
  * "intra_rough_waves" (4/8 waves per workgroup of the rough search), "pair_wave_kernel" (0/1: one wave per
  * descriptor for frame-level pair batches of up to 4096 descriptors), "wg_chunk_min_wgs" (the workgroup-per-descriptor

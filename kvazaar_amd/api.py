@@ -216,13 +216,15 @@ def coeff_abs_sum_batch(coeffs, length):
 
 
 def quantize_residual_batch(ref_in, pred_in, w, qp, color, scan_order, cu_is_intra, slice_is_intra=0, signhide=0,
-                            use_trskip=0, alias_rec=False, with_costs=False):
-    """-> (rec, coeff, has_coeffs) and, with_costs, (+ ssd(ref, rec), coeff_abs_sum) from the same launch"""
+                            use_trskip=0, alias_rec=False, with_costs=False, quant_coeff=None, dequant_coeff=None):
+    """-> (rec, coeff, has_coeffs) and, with_costs, (+ ssd(ref, rec), coeff_abs_sum) from the same launch.
+    quant_coeff / dequant_coeff: per-coefficient scaling-list tables (w*w int32, raster order) of the quantisation and of
+    the dequantisation; either may be left flat"""
     L = _lib.init()
     ref_in = np.ascontiguousarray(ref_in, dtype=np.uint8).reshape(-1, w * w)
     pred_in = np.ascontiguousarray(pred_in, dtype=np.uint8).reshape(-1, w * w)
     count = ref_in.shape[0]
-    p, keep = _qparams(qp, slice_is_intra, signhide)
+    p, keep = _qparams(qp, slice_is_intra, signhide, quant_coeff, dequant_coeff)
     r, pr = DeviceBuffer.from_numpy(ref_in), DeviceBuffer.from_numpy(pred_in)
     rec = pr if alias_rec else DeviceBuffer(ref_in.nbytes)
     co, has = DeviceBuffer(2 * ref_in.size), DeviceBuffer(4 * count)

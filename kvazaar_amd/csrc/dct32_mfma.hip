@@ -148,7 +148,7 @@ int launch_dct32_mfma(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   // leg (1 029 120 blocks) the forward kernel confirmed that what it wants is ONE BLOCK PER WAVE at any size, not a number of
   // workgroups per CU: cap 192: 5.77, 384: 5.90, 768: 6.07, 1100 (no wave takes a second block): 6.14 TB/s -- so the forward cap only
   // bounds the grid for lists beyond 4 M blocks.
-  const size_t cap = (size_t)num_cus() * (size_t)(inverse ? tuning("idct32_wgs_per_cu", 96) : tuning("dct32_wgs_per_cu", 4096));
+  const size_t cap = wg_cap(inverse ? tuning("idct32_wgs_per_cu", 96) : tuning("dct32_wgs_per_cu", 4096));
   if (wgs > cap) wgs = cap;
   if (tuning("dct_pipe", 0)) {
     if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<32, true, false, true>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
@@ -165,7 +165,7 @@ int launch_dct4_tile(bool inverse, bool dst, const i16 *in, i16 *out, size_t cou
   size_t wgs = (ntiles + 3) / 4;
   // workgroups per CU (0.5 GiB arrays): forward 64: 6.20, 128: 6.37, 192: 6.42, 256: 6.29 TB/s; inverse 32: 5.89, 64: 6.18, 96: 6.05, 128: 5.80
   // (the LDS butterfly kernel these replace: 5.4 / 5.55)
-  const size_t cap = (size_t)num_cus() * (size_t)(inverse ? tuning("idct4_wgs_per_cu", 64) : tuning("dct4_wgs_per_cu", 192));
+  const size_t cap = wg_cap(inverse ? tuning("idct4_wgs_per_cu", 64) : tuning("dct4_wgs_per_cu", 192));
   if (wgs > cap) wgs = cap;
   const dim3 g((unsigned)wgs), b(256);
   if (dst) {
@@ -184,7 +184,7 @@ int launch_dct16_tile(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   const size_t ntiles = (count + 3) / 4;
   size_t wgs = (ntiles + 3) / 4;
   // workgroups per CU (0.5 GiB arrays): forward 64: 6.43, 96: 6.50, 128: 6.52, 192: 6.42, 256: 6.34 TB/s; inverse 32: 6.16, 64: 6.17, 96: 5.98, 128: 5.81
-  const size_t cap = (size_t)num_cus() * (size_t)(inverse ? tuning("idct16_wgs_per_cu", 64) : tuning("dct16_wgs_per_cu", 128));
+  const size_t cap = wg_cap(inverse ? tuning("idct16_wgs_per_cu", 64) : tuning("dct16_wgs_per_cu", 128));
   if (wgs > cap) wgs = cap;
   if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<16, true>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
   else hipLaunchKernelGGL((dct32_mfma_kernel<16, false>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);

@@ -96,12 +96,16 @@ int serve_workers_launch(const u8 *planes, size_t plane_bytes, int n_slots, u32 
 int serve_launch(bool constrained, const u8 *planes, size_t plane_bytes, int n_slots, u32 stride, int w, int h,
                  const serve_unit *units, int count, hipStream_t st);
 
+// Workgroup cap of a grid-stride launch from a "*_wgs_per_cu" value; a value of 0 counts as 1 (a grid of zero
+// workgroups would not run at all).
+static inline size_t wg_cap(long long per_cu) { return (size_t)num_cus() * (size_t)(per_cu > 0 ? per_cu : 1); }
+
 // Grid sizing for streaming kernels: enough workgroups to fill 256 CUs several
 // times over, capped so that grid-stride loops amortise the launch.
 static inline unsigned stream_grid(size_t work_items, unsigned items_per_block, unsigned max_blocks_per_cu = 128)
 {
   size_t need = (work_items + items_per_block - 1) / items_per_block;
-  size_t cap = (size_t)num_cus() * max_blocks_per_cu;
+  size_t cap = wg_cap(max_blocks_per_cu);
   if (need < 1) need = 1;
   return (unsigned)(need < cap ? need : cap);
 }

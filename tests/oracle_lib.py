@@ -276,13 +276,14 @@ def coeff_abs_sum(c):
 
 
 def quantize_residual_batch(ref_in, pred_in, w, qp, color, scan_order_, cu_is_intra, slice_is_intra=0,
-                            signhide=0, use_trskip=0):
-    """ref_in/pred_in uint8 [count, w*w] (stride w) -> (rec [count,w*w], coeff [count,w*w], has [count])"""
+                            signhide=0, use_trskip=0, quant_coeff=None, dequant_coeff=None):
+    """ref_in/pred_in uint8 [count, w*w] (stride w) -> (rec [count,w*w], coeff [count,w*w], has [count]);
+    quant_coeff / dequant_coeff: the scaling-list tables of the quantisation / dequantisation (None: flat)"""
     ref_in, pred_in = _u8(ref_in).reshape(-1, w * w), _u8(pred_in).reshape(-1, w * w)
     rec = np.zeros_like(ref_in)
     coeff = np.zeros(ref_in.shape, dtype=np.int16)
     has = np.zeros(ref_in.shape[0], dtype=np.int32)
-    p, keep = _qp(qp, slice_is_intra, signhide)
+    p, keep = _qp(qp, slice_is_intra, signhide, quant_coeff, dequant_coeff)
     for i in range(ref_in.shape[0]):
         has[i] = lib().orc_quantize_residual(C.byref(p), int(cu_is_intra), w, color, scan_order_, int(use_trskip),
                                              w, w, _p(ref_in[i], u8p), _p(pred_in[i], u8p), _p(rec[i], u8p),
@@ -291,13 +292,13 @@ def quantize_residual_batch(ref_in, pred_in, w, qp, color, scan_order_, cu_is_in
 
 
 def quantize_residual_many(ref_in, pred_in, w, qp, color, scan_order_, cu_is_intra, slice_is_intra=0, signhide=0, use_trskip=0,
-                           threads=None):
+                           threads=None, quant_coeff=None, dequant_coeff=None):
     """quantize_residual_batch for whole launches (C loop, one range of TUs per host thread)"""
     ref_in, pred_in = _u8(ref_in).reshape(-1, w * w), _u8(pred_in).reshape(-1, w * w)
     rec = np.zeros_like(ref_in)
     coeff = np.zeros(ref_in.shape, dtype=np.int16)
     has = np.zeros(ref_in.shape[0], dtype=np.int32)
-    p, keep = _qp(qp, slice_is_intra, signhide)
+    p, keep = _qp(qp, slice_is_intra, signhide, quant_coeff, dequant_coeff)
     L, bs = lib(), w * w
     L.orc_dct_matrix(w)
     L.orc_scan_order(scan_order_, {4: 2, 8: 3, 16: 4, 32: 5}[w])

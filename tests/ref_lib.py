@@ -245,13 +245,14 @@ def scaling_tables(log2_tr, list_type, qp_rem, n):
 
 
 def quantize_residual_batch(ref_in, pred_in, w, qp, color, scan_order_, cu_is_intra, slice_is_intra=0,
-                            signhide=0, use_trskip=0, name="generic"):
+                            signhide=0, use_trskip=0, name="generic", sl=0):
+    """sl=1: the reference's default scaling lists (scaling_tables() then returns the processed tables it used)"""
     ref_in, pred_in = _u8(ref_in).reshape(-1, w * w), _u8(pred_in).reshape(-1, w * w)
     rec = np.zeros_like(ref_in)
     coeff = _aligned(np.zeros(ref_in.shape, dtype=np.int16))
     has = np.zeros(ref_in.shape[0], dtype=np.int32)
     for i in range(ref_in.shape[0]):
-        has[i] = lib().ref_quantize_residual(name.encode(), qp, int(slice_is_intra), int(signhide), 0,
+        has[i] = lib().ref_quantize_residual(name.encode(), qp, int(slice_is_intra), int(signhide), int(sl),
                                              int(cu_is_intra), w, color, scan_order_, int(use_trskip), w, w,
                                              _p(ref_in[i], u8p), _p(pred_in[i], u8p), _p(rec[i], u8p),
                                              _p(coeff[i], i16p))

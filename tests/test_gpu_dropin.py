@@ -208,6 +208,8 @@ ENCODER_CONFIGS = [
     # transform skip with RDOQ quantising the skipped 4x4 blocks (quant-generic.c:206-221: kvz_transformskip, then kvz_rdoq)
     (128, 64, 4, "preset=medium,transform-skip=1,rdoq=1,rdoq-skip=0,rd=1,qp=26,threads=0"),
     (128, 128, 3, "preset=medium,rdoq=0,scaling-list=default,qp=28,threads=2"),        # scaling-list tables through the accessors
+    # custom lists that differ per list (U from V, intra from inter) and are asymmetric: the list choice and the table layout
+    (128, 64, 4, "preset=medium,rdoq=0,scaling-list=custom,cqmfile=%s,qp=26,threads=2" % os.path.join(ROOT, "tests", "golden", "custom_lists.cqm")),
     (128, 64, 4, "preset=fast,rdoq=0,me=dia,full-intra-search=1,mv-rdo=1,qp=35,threads=0"),
     (64, 64, 3, "preset=medium,rdoq=0,lossless=1,threads=0"),
     (192, 128, 3, "preset=medium,rdoq=0,tiles=2x2,qp=31,threads=3"),

@@ -182,6 +182,53 @@ def test_coeff_abs_sum_kat():
     assert O.coeff_abs_sum(c) == expected == R.coeff_abs_sum(c)
 
 
+_CHROMA_SCALE = (list(range(30)) + [29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37] +
+                 list(range(38, 52)))                      # transform.c:44-50
+
+
+def _scaled_qp(type_, qp):
+    return qp if type_ == 0 else _CHROMA_SCALE[min(max(qp, 0), 57)]
+
+
+def sl_tables(w, color, intra, qp):
+    """The tables the fused quantize_residual is given for a TU, chosen the way strategy.hip:flatten_state chooses them:
+    quantisation with list type_q (0 luma, 2 chroma), dequantisation with type_dq (0 luma, 2 U, 3 V), each through
+    "\\0\\3\\1\\2"[type] (quant-generic.c:46, :293) at its own scaled QP % 6.  The reference must have run with sl=1 first."""
+    log2 = {4: 2, 8: 3, 16: 4, 32: 5}[w]
+    type_q, type_dq = (0, 0) if color == 0 else (2, 1 + color)
+    lt = lambda t: (0 if intra else 3) + (0, 3, 1, 2)[t]
+    qt, _ = R.scaling_tables(log2, lt(type_q), _scaled_qp(type_q, qp) % 6, w)
+    _, dt = R.scaling_tables(log2, lt(type_dq), _scaled_qp(type_dq, qp) % 6, w)
+    return qt, dt
+
+
+@pytest.mark.parametrize("w", [4, 8, 16, 32])
+def test_quantize_residual_scaling_list(w):
+    """The fused path with the reference's default scaling lists: the oracle, fed the tables sl_tables picks, equals the
+    reference at sl=1 -- intra and inter lists, both chroma lists, sign hiding, transform skip, and QPs on both sides of
+    the dequantisation's switch from rounding shift to clip-and-shift (luma qp >= 30 / 36 / 42 / 48 at w = 4 .. 32)"""
+    g = rng(60 + w)
+    ref_in = g.integers(0, 256, (8, w * w), dtype=np.uint8)
+    pred = np.clip(ref_in.astype(np.int32) + g.integers(-60, 61, ref_in.shape), 0, 255).astype(np.uint8)
+    pred[0] = ref_in[0]
+    pred[1] = 255 - ref_in[1]
+    ref_in[2], pred[2] = 255, 0
+    ref_in[3, ::2], pred[3, ::2] = 0, 255
+    switch = 6 * {4: 5, 8: 6, 16: 7, 32: 8}[w]
+    for qp in (4, switch - 1, switch, 51):
+        for color in ((0,) if w == 32 else (0, 1, 2)):
+            for intra in (0, 1):
+                for signhide, scan in ((0, 0), (1, 0), (1, 1), (1, 2)):
+                    for trskip in ((0, 1) if w == 4 else (0,)):
+                        r = R.quantize_residual_batch(ref_in, pred, w, qp, color, scan, intra, intra, signhide, trskip, sl=1)
+                        qt, dt = sl_tables(w, color, intra, qp)
+                        o = O.quantize_residual_batch(ref_in, pred, w, qp, color, scan, intra, intra, signhide, trskip,
+                                                      quant_coeff=qt, dequant_coeff=dt)
+                        for a, b, nm in zip(o, r, ("rec", "coeff", "has")):
+                            np.testing.assert_array_equal(a, b, err_msg="%s qp=%d color=%d intra=%d signhide=%d scan=%d trskip=%d"
+                                                          % (nm, qp, color, intra, signhide, scan, trskip))
+
+
 @pytest.mark.parametrize("w", [4, 8, 16, 32])
 def test_quantize_residual(w):
     g = rng(50 + w)
@@ -651,3 +698,44 @@ def test_candidate_helpers_vs_the_reference_unit_test_functions():
     assert tuple(R.mv_cand_helpers([(x, y, w, h)], pw, ph)[2][0]) == want
     assert [bool(v) for v in R.mv_cand_helpers([g for g, _ in MV_CAND_KAT_A0], 1920, 1080)[0]] == [e for _, e in MV_CAND_KAT_A0]
     assert [bool(v) for v in R.mv_cand_helpers([g for g, _ in MV_CAND_KAT_B0], 1920, 1080)[1]] == [e for _, e in MV_CAND_KAT_B0]
+
+
+class _ScalingList(C.Structure):
+    # scaling_list_t (scalinglist.h:34-42)
+    _fields_ = [("enable", C.c_int8), ("use_default_list", C.c_int8), ("dc", (C.c_int32 * 6) * 4),
+                ("coeff", (C.c_void_p * 6) * 4), ("quant_coeff", ((C.c_void_p * 6) * 6) * 4),
+                ("de_quant_coeff", ((C.c_void_p * 6) * 6) * 4), ("error_scale", ((C.c_void_p * 6) * 6) * 4)]
+
+
+def test_custom_cqm_fixture_is_what_the_drop_in_encode_needs():
+    """tests/golden/custom_lists.cqm (the scaling-list=custom encode of test_gpu_dropin.py) parses with the reference's
+    own kvz_scalinglist_parse, and its lists tell apart what the default lists cannot: every list differs from every
+    other (U from V, intra from inter), none is symmetric in raster order, entries 1 and 255 occur, and the 16x16 / 32x32
+    DC values differ from coefficient 0"""
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "custom_lists.cqm")
+    L, libc = R.lib(), C.CDLL(None)
+    libc.fopen.restype, libc.fopen.argtypes = C.c_void_p, [C.c_char_p, C.c_char_p]
+    libc.fclose.argtypes = [C.c_void_p]
+    L.kvz_scalinglist_parse.argtypes = [C.c_void_p, C.c_void_p]
+    sl = _ScalingList()
+    L.kvz_scalinglist_init(C.byref(sl))
+    fp = libc.fopen(path.encode(), b"rb")
+    assert fp
+    try:
+        assert L.kvz_scalinglist_parse(C.byref(sl), C.c_void_p(fp)) == 1 and sl.enable == 1
+        lists = []
+        for size_id, n_lists in enumerate((6, 6, 6, 2)):
+            n = 4 if size_id == 0 else 8
+            for list_id in range(n_lists):
+                m = np.ctypeslib.as_array(C.cast(sl.coeff[size_id][list_id], C.POINTER(C.c_int32)), shape=(n * n,)).copy()
+                assert not (m.reshape(n, n) == m.reshape(n, n).T).all(), (size_id, list_id)
+                if size_id >= 2:
+                    assert sl.dc[size_id][list_id] != m[0], (size_id, list_id)
+                lists.append(tuple(m))
+        assert len(set(lists)) == len(lists)
+        allv = np.concatenate([np.array(v) for v in lists])
+        assert allv.min() == 1 and allv.max() == 255
+    finally:
+        libc.fclose(C.c_void_p(fp))
+        L.kvz_scalinglist_destroy(C.byref(sl))
