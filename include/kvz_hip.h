@@ -370,8 +370,13 @@ typedef struct {
 /* kvz_sample_quarterpel_luma / kvz_sample_octpel_chroma and their 14-bit
  * variants (generic/ipol-generic.c:122-190, :660-728), with the source window
  * fetched like kvz_get_extended_block (ipol-generic.c:731-784: coordinates
- * clamped to the plane).  Output block i is written contiguously (stride =
- * width) at dst + out_offsets[i] (elements). */
+ * clamped to the plane; ref_stride may exceed ref_w, and nothing right of
+ * ref_w or below ref_h is read).  Output block i is written contiguously
+ * (stride = width) at dst + out_offsets[i] (elements); the offsets may come in
+ * any order and at any alignment, and nothing outside the w*h elements of each
+ * block is written.  Supported shapes: 1..64 (luma) / 1..32 (chroma) on each
+ * side.  A descriptor of any other shape (a side of 0 or less, or too large)
+ * is skipped: nothing is written for it. */
 KVZ_HIP_API int kvz_hip_sample_luma_batch(const kvz_hip_pixel *ref, uint32_t ref_stride, int ref_w, int ref_h,
                                           const kvz_hip_ipol_block *blocks, const uint64_t *out_offsets, size_t count,
                                           int out_14bit, void *dst, kvz_hip_stream s);
@@ -388,7 +393,10 @@ KVZ_HIP_API int kvz_hip_sample_chroma_batch(const kvz_hip_pixel *ref, uint32_t r
  * stay in LDS, only costs leave the CU.  costs[17*i + 0] integer position,
  * [1..8] half-pel neighbours, [9..16] quarter-pel neighbours of the best
  * half-pel position; best[2*i + {0,1}] = chosen hpel / qpel index (0 = centre),
- * ties and order as in the reference, MV bit costs taken as zero. */
+ * ties and order as in the reference, MV bit costs taken as zero.  A
+ * descriptor of any other shape (4x4, 12x12, a side that is not a multiple of
+ * 4, 0 or less, or larger than 64) is flagged: its 17 costs are 0xFFFFFFFF and
+ * best[2*i + {0,1}] = -1; its neighbours are computed as usual. */
 KVZ_HIP_API int kvz_hip_search_frac_batch(const kvz_hip_pixel *pic, uint32_t pic_stride,
                                           const kvz_hip_pixel *ref, uint32_t ref_stride, int ref_w, int ref_h,
                                           const kvz_hip_block_pair *pairs, size_t count,

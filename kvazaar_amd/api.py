@@ -241,8 +241,9 @@ def quantize_residual_batch(ref_in, pred_in, w, qp, color, scan_order, cu_is_int
 
 
 # ------------------------------------------------------------------ ipol
-def sample_batch(kind, ref, blocks):
-    """kind: luma|luma14|chroma|chroma14; blocks: (x, y, frac_x, frac_y, w, h); returns list of arrays"""
+def sample_batch(kind, ref, blocks, ref_w=None, ref_h=None):
+    """kind: luma|luma14|chroma|chroma14; blocks: (x, y, frac_x, frac_y, w, h); returns list of arrays.
+    The plane is ref[:ref_h, :ref_w] (default: all of ref) with row stride ref.shape[1]."""
     L = _lib.init()
     ref = np.ascontiguousarray(ref, dtype=np.uint8)
     b = np.ascontiguousarray(np.asarray(blocks, dtype=np.int32).reshape(-1, 6))
@@ -254,14 +255,16 @@ def sample_batch(kind, ref, blocks):
     r, d, o = DeviceBuffer.from_numpy(ref), DeviceBuffer.from_numpy(b), DeviceBuffer.from_numpy(offs[:-1].copy())
     dst = DeviceBuffer(int(offs[-1]) * esize)
     f = L.kvz_hip_sample_luma_batch if kind.startswith("luma") else L.kvz_hip_sample_chroma_batch
-    check(f(r.ptr, ref.shape[1], ref.shape[1], ref.shape[0], d.ptr, o.ptr, count, int(out14), dst.ptr, None),
+    check(f(r.ptr, ref.shape[1], ref.shape[1] if ref_w is None else ref_w, ref.shape[0] if ref_h is None else ref_h,
+            d.ptr, o.ptr, count, int(out14), dst.ptr, None),
           "sample %s batch" % kind)
     flat = dst.to_numpy(np.int16 if out14 else np.uint8, (int(offs[-1]),))
     return [flat[int(offs[i]):int(offs[i + 1])].reshape(int(b[i, 5]), int(b[i, 4])) for i in range(count)]
 
 
-def search_frac_batch(pic, ref, pairs):
+def search_frac_batch(pic, ref, pairs, ref_w=None, ref_h=None):
     """pairs: (x1, y1, x2, y2, w, h) with (x2,y2) the integer-pel position in ref.
+    The reference plane is ref[:ref_h, :ref_w] (default: all of ref) with row stride ref.shape[1].
     Returns (costs uint32 [count,17], best int32 [count,2])"""
     L = _lib.init()
     pic = np.ascontiguousarray(pic, dtype=np.uint8)
@@ -270,8 +273,9 @@ def search_frac_batch(pic, ref, pairs):
     count = pa.shape[0]
     a, b, d = DeviceBuffer.from_numpy(pic), DeviceBuffer.from_numpy(ref), DeviceBuffer.from_numpy(pa)
     co, be = DeviceBuffer(4 * 17 * count), DeviceBuffer(8 * count)
-    check(L.kvz_hip_search_frac_batch(a.ptr, pic.shape[1], b.ptr, ref.shape[1], ref.shape[1], ref.shape[0], d.ptr,
-                                      count, co.ptr, be.ptr, None), "search_frac batch")
+    check(L.kvz_hip_search_frac_batch(a.ptr, pic.shape[1], b.ptr, ref.shape[1], ref.shape[1] if ref_w is None else ref_w,
+                                      ref.shape[0] if ref_h is None else ref_h, d.ptr, count, co.ptr, be.ptr, None),
+          "search_frac batch")
     return co.to_numpy(np.uint32, (count, 17)), be.to_numpy(np.int32, (count, 2))
 
 

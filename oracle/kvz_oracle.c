@@ -1864,6 +1864,33 @@ void orc_quantize_residual_many(const orc_quant_params *p, int cu_is_intra, int 
                                           ref_in + i * bs, pred_in + i * bs, rec_out + i * bs, coeff_out + i * bs);
 }
 
+void orc_sample_many(int kind, const orc_pixel *frame, int stride, int pad, const int32_t *blocks, const uint64_t *offs,
+                     size_t count, void *dst)
+{
+  for (size_t i = 0; i < count; ++i) {
+    const int32_t *b = blocks + 6 * i;
+    const orc_pixel *src = frame + (long)(b[1] + pad) * stride + (b[0] + pad);
+    const int16_t mv[2] = { (int16_t)b[2], (int16_t)b[3] };
+    orc_pixel *d8 = (orc_pixel *)dst + offs[i];
+    int16_t *d16 = (int16_t *)dst + offs[i];
+    switch (kind) {
+    case 0: orc_sample_quarterpel_luma(src, stride, b[4], b[5], d8, b[4], mv); break;
+    case 1: orc_sample_14bit_quarterpel_luma(src, stride, b[4], b[5], d16, b[4], mv); break;
+    case 2: orc_sample_octpel_chroma(src, stride, b[4], b[5], d8, b[4], mv); break;
+    default: orc_sample_14bit_octpel_chroma(src, stride, b[4], b[5], d16, b[4], mv); break;
+    }
+  }
+}
+void orc_search_frac_many(const orc_pixel *pic, int pic_stride, const orc_pixel *ref, int ref_w, int ref_h,
+                          const int32_t *pairs, size_t count, unsigned *costs, int *best)
+{
+  for (size_t i = 0; i < count; ++i) {
+    const int32_t *p = pairs + 6 * i;
+    orc_search_frac_costs(pic, pic_stride, ref, ref_w, ref_h, p[0], p[1], p[4], p[5], p[2] - p[0], p[3] - p[1],
+                          costs + 17 * i, best + 2 * i);
+  }
+}
+
 /* =====================================================================
  * AMVP / merge candidate derivation (inter.c:546-1446), flattened state
  * ===================================================================== */

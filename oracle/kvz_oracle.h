@@ -352,6 +352,14 @@ int orc_cabac_table(int kind, int i);
 void orc_quantize_residual_many(const orc_quant_params *p, int cu_is_intra, int width, int color, int scan_order, int use_trskip,
                                 const orc_pixel *ref_in, const orc_pixel *pred_in, orc_pixel *rec_out, orc_coeff *coeff_out,
                                 int32_t *has_coeffs, size_t count);
+/* sample blocks (x, y, frac_x, frac_y, w, h) [count][6] from `frame` (stride `stride`) with src = &frame[y + pad][x + pad]
+ * (the caller pads the plane far enough for every window); kind 0 luma, 1 luma 14-bit, 2 chroma, 3 chroma 14-bit; block i
+ * goes to element offs[i] of dst (uint8 or int16) */
+void orc_sample_many(int kind, const orc_pixel *frame, int stride, int pad, const int32_t *blocks, const uint64_t *offs,
+                     size_t count, void *dst);
+/* orc_search_frac_costs over pairs (x1, y1, x2, y2, w, h) [count][6], mv = (x2 - x1, y2 - y1): costs [count][17], best [count][2] */
+void orc_search_frac_many(const orc_pixel *pic, int pic_stride, const orc_pixel *ref, int ref_w, int ref_h,
+                          const int32_t *pairs, size_t count, unsigned *costs, int *best);
 
 /* the reference's own unit test of the candidate helpers (tests/mv_cand_tests.c:26-260), see kvz_oracle.c */
 int orc_is_a0_cand_coded(int x, int y, int width, int height);

@@ -82,6 +82,11 @@ def lib():
         L.orc_search_frac_costs.restype = None
         L.orc_search_frac_costs.argtypes = [u8p, C.c_int, u8p, C.c_int, C.c_int] + [C.c_int] * 6 + \
             [u32p, C.POINTER(C.c_int)]
+        L.orc_sample_many.restype = None
+        L.orc_sample_many.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.orc_search_frac_many.restype = None
+        L.orc_search_frac_many.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p]
         L.orc_cost_nxn_many.restype = None
         L.orc_cost_nxn_many.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.orc_transform_many.restype = None
@@ -350,6 +355,35 @@ def search_frac_costs(pic, ref, x, y, w, h, mvx, mvy):
     lib().orc_search_frac_costs(_p(pic, u8p), pic.shape[1], _p(ref, u8p), ref.shape[1], ref.shape[0],
                                 x, y, w, h, mvx, mvy, _p(costs, u32p), best)
     return costs, (best[0], best[1])
+
+
+SAMPLE_KINDS = ("luma", "luma14", "chroma", "chroma14")
+
+
+def sample_many(kind, padded, pad, blocks, offs, out, threads=None):
+    """sample() of every block (x, y, frac_x, frac_y, w, h) into the flat array `out` at element offs[i], the loop in C;
+    block positions are in the unpadded frame, `padded` is that frame with `pad` pixels on every side"""
+    padded = _u8(padded)
+    blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 6)
+    offs = np.ascontiguousarray(offs, dtype=np.uint64)
+    assert out.dtype == (np.int16 if kind.endswith("14") else np.uint8) and out.flags.c_contiguous
+    L, k = lib(), SAMPLE_KINDS.index(kind)
+    run_ranges(blocks.shape[0], lambda lo, hi: L.orc_sample_many(k, padded.ctypes.data, padded.shape[1], pad, blocks.ctypes.data + 24 * lo,
+                                                                 offs.ctypes.data + 8 * lo, hi - lo, out.ctypes.data), threads)
+    return out
+
+
+def search_frac_many(pic, ref, pairs, threads=None):
+    """search_frac_costs of every pair (x1, y1, x2, y2, w, h), the loop in C: (costs uint32 [count, 17], best int32 [count, 2])"""
+    pic, ref = _u8(pic), _u8(ref)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 6)
+    costs = np.zeros((pairs.shape[0], 17), dtype=np.uint32)
+    best = np.zeros((pairs.shape[0], 2), dtype=np.int32)
+    L = lib()
+    run_ranges(pairs.shape[0], lambda lo, hi: L.orc_search_frac_many(pic.ctypes.data, pic.shape[1], ref.ctypes.data, ref.shape[1], ref.shape[0],
+                                                                      pairs.ctypes.data + 24 * lo, hi - lo, costs.ctypes.data + 68 * lo,
+                                                                      best.ctypes.data + 8 * lo), threads)
+    return costs, best
 
 
 def ctu_sad_grid(pic, ref, ctus, mv_offsets):

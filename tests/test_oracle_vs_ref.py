@@ -14,6 +14,11 @@ from patterns import intra_ref_cases, intra_ref_positions, lcg_bytes, rng
 pytestmark = pytest.mark.skipif(not R.available(), reason="oracle/_ref not built")
 
 SIZES = (4, 8, 16, 32, 64)
+# shapes tests/test_gpu_ipol_variants.py sends through the sample and fractional search kernels beyond the older lists
+SAMPLE_LUMA_SHAPES = ((24, 32), (32, 24), (48, 64), (64, 16), (12, 16), (17, 3), (64, 5))
+SAMPLE_CHROMA_SHAPES = ((6, 8), (8, 6), (2, 8), (8, 2), (32, 8), (1, 1), (31, 32))
+FRAC_LARGE_SHAPES = ((64, 64), (64, 32), (32, 64), (64, 16), (16, 64), (64, 48), (48, 64), (32, 8), (8, 32), (32, 16), (16, 32),
+                     (32, 24), (24, 32))
 
 
 def _blocks(n, count, seed, mode):
@@ -252,14 +257,42 @@ def test_sample_filters(kind):
     frame = g.integers(0, 256, (96, 96), dtype=np.uint8)
     frame[40:60, 40:60] = np.where(g.integers(0, 2, (20, 20)) > 0, 255, 0)   # adversarial extremes
     nfrac = 4 if kind.startswith("luma") else 8
-    sizes = ((8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 4)) if kind.startswith("luma") else \
-            ((4, 4), (8, 8), (16, 16), (32, 32), (8, 4), (2, 2))
+    # + the shapes the GPU variant tests sample: AMP / SMP and odd shapes, down to 1x1
+    sizes = ((8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 4)) + SAMPLE_LUMA_SHAPES if kind.startswith("luma") else \
+            ((4, 4), (8, 8), (16, 16), (32, 32), (8, 4), (2, 2)) + SAMPLE_CHROMA_SHAPES
     for (w, h) in sizes:
         for fx in range(nfrac):
             for fy in range(nfrac):
                 o = O.sample(kind, frame, 12, 10, w, h, fx, fy)
                 r = R.sample(kind, frame, 12, 10, w, h, fx, fy)
                 np.testing.assert_array_equal(o, r, err_msg="%s %dx%d frac=(%d,%d)" % (kind, w, h, fx, fy))
+
+
+@pytest.mark.parametrize("kind", ["luma", "luma14", "chroma", "chroma14"])
+def test_sample_on_edge_padded_plane_equals_extended_block(kind):
+    """the construction the GPU tests check against: O.sample on np.pad(frame, mode="edge") equals the reference's own route
+    for a window that leaves the frame, kvz_get_extended_block (which then builds the window) and the sample function on it"""
+    g = rng(63)
+    frame = g.integers(0, 256, (37, 53), dtype=np.uint8)
+    frame[:, :3] = np.where(g.integers(0, 2, (37, 3)) > 0, 255, 0)
+    pad = 120
+    padded = np.pad(frame, pad, mode="edge")
+    luma = kind.startswith("luma")
+    fs, nfrac = (8, 4) if luma else (4, 8)
+    shapes = ((8, 8), (64, 64), (16, 4), (24, 32)) + SAMPLE_LUMA_SHAPES if luma else ((2, 2), (32, 32), (4, 2)) + SAMPLE_CHROMA_SHAPES
+    n = 0
+    for k, (w, h) in enumerate(shapes):
+        # every border and corner, just over the edge and far outside
+        for (x, y) in ((-1, 10), (53 - w + 1, 5), (4, -2), (6, 37 - h + 1), (-w - 40, -h - 50), (53 + 30, 37 + 45),
+                       (-3 - w // 2, 37 - h // 2), (53 - w // 2, -h)):
+            fx, fy = (k + x) % nfrac, (k + 3 * y) % nfrac
+            win, used, (stride, _, tl) = R.get_extended_block(frame, x, y, 0, 0, fs, w, h)
+            assert used, (w, h, x, y)
+            r = R.sample(kind, win, tl % stride, tl // stride, w, h, fx, fy)
+            o = O.sample(kind, padded, x + pad, y + pad, w, h, fx, fy)
+            np.testing.assert_array_equal(o, r, err_msg="%s %dx%d at (%d,%d) frac=(%d,%d)" % (kind, w, h, x, y, fx, fy))
+            n += 1
+    assert n == 8 * len(shapes)
 
 
 @pytest.mark.parametrize("pattern", ["random", "extreme"])
@@ -275,6 +308,22 @@ def test_frac_block_filters(pattern):
                 r = R.filter_frac_steps(frame, 10, 9, w, h, (ox, oy))
                 np.testing.assert_array_equal(o[:, :, :h, :w], r[:, :, :h, :w],
                                               err_msg="%dx%d off=(%d,%d)" % (w, h, ox, oy))
+
+
+def test_search_frac_costs_large_and_rectangular_shapes():
+    """the shapes of the medium and big GPU kernels, at all four borders and corners, with vectors far outside the plane"""
+    g = rng(82)
+    ref = g.integers(0, 256, (136, 152), dtype=np.uint8)
+    ref[:, -5:] = np.where(g.integers(0, 2, (136, 5)) > 0, 255, 0)
+    pic = ((ref.astype(np.int32) + np.roll(ref, (1, 2), axis=(0, 1))) // 2).astype(np.uint8)
+    H, W = ref.shape
+    for k, (w, h) in enumerate(FRAC_LARGE_SHAPES):
+        for (x, y) in ((0, 0), (W - w, 0), (0, H - h), (W - w, H - h), (W // 2 - w // 2, H // 2 - h // 2)):
+            for (mvx, mvy) in ((0, 0), (-3 - k, 2), (-(x + w + 90), 7), (W + 60 - x, -(y + h + 70)), (5, H - y + 40)):
+                o = O.search_frac_costs(pic, ref, x, y, w, h, mvx, mvy)
+                r = R.search_frac_costs(pic, ref, x, y, w, h, mvx, mvy)
+                np.testing.assert_array_equal(o[0], r[0], err_msg=str((w, h, x, y, mvx, mvy)))
+                assert o[1] == r[1], (w, h, x, y, mvx, mvy)
 
 
 def test_search_frac_costs():
