@@ -3,7 +3,8 @@
 // Reference: the encoder runs one CTU job per threadqueue worker (src/encoderstate.c:777-828; workers are pthreads,
 // threadqueue.c:263; frames in flight under --owf, encoder.c:59-119), and each worker reaches search_pu_inter
 // (search_inter.c:1451-1520) with one PU at a time and walks its reference pictures in order (:1502-1507).  This file is the
-// piece between those workers and the kernels of me_search.hip (declared in include/kvz_hip.h, "search service").
+// piece between those workers and the kernels of serve_kernels.hip (declared in include/kvz_hip.h, "search service"; what this
+// file and the kernels share is serve_ring.h).
 //
 //   * No dispatcher thread.  A caller appends its request to the pending list and then either finds the launch path free --
 //     it takes EVERYTHING pending (flat combining) and launches it -- or waits for its results while another caller
@@ -18,7 +19,7 @@
 //     fewer and larger ones do not).
 //
 // Resident workers (tuning "service_workers" > 0): the same requests without a launch on their way.  Workgroups of
-// me_search.hip's serve_worker_kernel stay on the device and take units by ticket from a ring of slots in page-locked memory:
+// serve_kernels.hip's serve_worker_kernel stay on the device and take units by ticket from a ring of slots in page-locked memory:
 //   host, under ring_mu:  wait until slot.seq == 0, write the unit, slot.seq = serve_seq(ticket), ... ctl->tail += n      (publish)
 //   worker:               ticket = head++ while head < tail (device atomics; ctl->tail is read across PCIe by one worker at a
 //                         time and mirrored in device memory), copy the unit, slot.seq = 0, search, write the results and `done`.
@@ -28,8 +29,7 @@
 //   looking while it waits) and starts the workers that are missing.  So a published unit is seen either by a worker's last look or
 //   by a caller that finds the worker gone.  alive[w] has one writer at a time: the host sets it when it launches worker w, which it
 //   only does when it reads 0; the worker clears it once.
-#include "kvz_hip_internal.h"
-#include "serve_seq.h"
+#include "serve_ring.h"
 
 #include <immintrin.h>
 #include <sched.h>
@@ -251,9 +251,9 @@ int ensure_workers(kvz_hip_me_service *svc)
     int cur = -1;
     if (hipGetDevice(&cur) != hipSuccess || cur != svc->device) (void)hipSetDevice(svc->device);
     // poll period per worker: with the ticket count in device memory every worker looks every 0.5 us; across PCIe they take turns
-    rc = serve_workers_launch_push(svc->planes, svc->plane_bytes, svc->n_slots, (u32)svc->w, svc->w, svc->h, svc->dring ? svc->dring : svc->wring, svc->wring,
-                                   svc->dpush, WRING_SLOTS - 1, ctl, svc->wdev, ids, n, svc->linger_ticks, svc->life_ticks,
-                                   svc->dpush ? 50ull : 50ull * (unsigned long long)svc->n_workers, svc->wstreams[svc->wnext++ % N_WSTREAMS]);
+    rc = serve_workers_launch(svc->planes, svc->plane_bytes, svc->n_slots, (u32)svc->w, svc->w, svc->h, svc->dring ? svc->dring : svc->wring, svc->wring,
+                              svc->dpush, WRING_SLOTS - 1, ctl, svc->wdev, ids, n, svc->linger_ticks, svc->life_ticks,
+                              svc->dpush ? 50ull : 50ull * (unsigned long long)svc->n_workers, svc->wstreams[svc->wnext++ % N_WSTREAMS]);
     svc->st_launches.fetch_add(1, std::memory_order_relaxed);
     if (rc != KVZ_HIP_OK) {
       for (int i = 0; i < n; ++i) __atomic_store_n(&ctl->alive[ids.id[i]], 0u, __ATOMIC_RELAXED);
