@@ -795,6 +795,78 @@ KVZ_HIP_API int kvz_hip_deblock_frame(kvz_hip_pixel *rec_y, uint32_t stride_y, k
                                       const kvz_hip_deblock_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
+/* motion compensation (inter recon) of PUs and of a whole picture     */
+/*   reference: kvz_inter_recon_cu (inter.c:492-540) through           */
+/*   inter_recon_unipred / kvz_inter_recon_bipred (inter.c:314-477),   */
+/*   the sample filters of ipol-generic.c:122-190, :660-728 and the    */
+/*   blend of inter_recon_bipred_generic (picture-generic.c:538-588)   */
+/* ------------------------------------------------------------------ */
+#define KVZ_HIP_MAX_REF_PICTURES 16
+/* One reference picture (kvz_picture, image.h:53-74): DEVICE planes.  width / height are the luma size, multiples of 8;
+ * the chroma planes are width/2 x height/2 (4:2:0; u, v unused and may be NULL for 4:0:0).  Strides may exceed the
+ * widths; nothing right of the width or below the height of a plane is ever read. */
+typedef struct {
+  const kvz_hip_pixel *y, *u, *v;
+  uint32_t stride_y, stride_c;
+  int32_t width, height;
+} kvz_hip_ref_picture;          /* 40 bytes */
+/* One PU as kvz_inter_recon_cu hands it to inter_recon_unipred / kvz_inter_recon_bipred (inter.c:501-538). */
+typedef struct {
+  int32_t x, y, width, height;  /* luma rectangle in PICTURE coordinates; x, y multiples of 4 */
+  int16_t mv[2][2];             /* inter.mv: [list][x, y], quarter-pel */
+  uint8_t mv_dir;               /* inter.mv_dir: 1 L0, 2 L1, 3 both */
+  uint8_t ref[2];               /* per list: index into the table of reference pictures, i.e. ref_LX[list][mv_ref[list]] */
+  uint8_t pad;
+} kvz_hip_inter_pu;             /* 28 bytes */
+/* Writes the Y, U and V prediction of `count` PUs into the destination planes, at the PUs' own positions, bit-exact
+ * with the reference's generic strategy at bit depth 8:
+ *   uni-prediction (inter_recon_unipred with hi_prec_out == NULL, inter.c:314-421): luma kvz_sample_quarterpel_luma on
+ *     the window of kvz_get_extended_block when mv & 3 is non-zero in either component, else the pixels with each
+ *     coordinate clamped to the picture (inter_cp_with_ext_border, inter.c:277-298; inside the picture the plain blit);
+ *     chroma kvz_sample_octpel_chroma at (x >> 1, y >> 1) + ((mv >> 2) >> 1) with fraction mv & 7 when mv & 7 is
+ *     non-zero in either component, else the clamped copy;
+ *   bi-prediction (kvz_inter_recon_bipred, inter.c:435-477): per reference and per plane the 14-bit sample
+ *     (kvz_sample_14bit_quarterpel_luma / _octpel_chroma) when that plane's fraction is non-zero, else the clamped pixel
+ *     << 6; result clip((s0 + s1 + 64) >> 7) (picture-generic.c:538-588).  A luma-integer, chroma-fractional vector
+ *     (mv & 7 == 4) mixes the two kinds in one PU, as the reference does.  The 14-bit samples never leave the chip.
+ * refs is a HOST table of n_refs (1..16) pictures of one size, which is the size of the picture being predicted; it
+ * is copied at the call.  pus is a DEVICE array.  PU shapes: every shape of the inter search -- sides multiples of 4 in
+ * 4..64, never both 4 mod 8 -- inside the picture; vectors may point anywhere.  A descriptor of another shape, off
+ * the 4-pixel grid, outside the picture, with mv_dir outside 1..3 or with a used ref index >= n_refs is skipped:
+ * nothing is written for it.  Only the pixels of valid PUs are written; the destination planes must not alias a
+ * reference plane.  chroma: 1 = 4:2:0, 0 = 4:0:0 (pred_u / pred_v unused, may be NULL).  count == 0 is a no-op; a
+ * missing pointer or a malformed table returns KVZ_HIP_ERR_INVALID.  Asynchronous on s, no host synchronisation,
+ * usable between kvz_hip_graph_begin / _end.
+ * Coordinates are picture-wide: the reference adds state->tile->offset_x / _y before it clamps against the whole
+ * picture (inter.c:328-331), so a tile-relative caller gets the same pixels by passing picture coordinates. */
+KVZ_HIP_API int kvz_hip_inter_recon_batch(const kvz_hip_ref_picture *refs, int n_refs, const kvz_hip_inter_pu *pus, size_t count,
+                                          kvz_hip_pixel *pred_y, uint32_t stride_y, kvz_hip_pixel *pred_u, kvz_hip_pixel *pred_v,
+                                          uint32_t stride_c, int chroma, kvz_hip_stream s);
+typedef struct {
+  int32_t chroma;               /* 0: 4:0:0 (pred_u / pred_v unused), 1: 4:2:0 */
+  int32_t n_refs;               /* pictures in the table, 1..16 */
+  uint8_t ref_LX[2][16];        /* state->frame->ref_LX (encoderstate.h:100) */
+} kvz_hip_inter_recon_params;   /* 40 bytes */
+/* kvz_inter_recon_cu (inter.c:492-540) for every inter CU of a picture, in one asynchronous call: the prediction of
+ * the picture from its CU array.  cus: DEVICE, one kvz_hip_cu_info per 4x4 SCU, row-major, ceil(width / 4) records
+ * per row, 4-byte aligned (as kvz_hip_deblock_frame takes it).  A CU is 64 >> depth wide at the SCU position rounded
+ * down to that size; part_size is read from the CU's first record, the PUs are those of PU_GET_X / _Y / _W / _H
+ * (cu.h:69-104) for all eight part modes, and each PU's mv_dir, mv and mv_ref are read from the record at the PU's own
+ * top-left SCU (inter.c:507); its pictures are refs[params->ref_LX[list][mv_ref[list]]].  Records whose type is not
+ * CU_INTER (intra, or 0 = not coded yet) contribute nothing and their destination pixels are left untouched.  A CU
+ * that would leave the picture is skipped, and so is a PU whose shape kvz_hip_inter_recon_batch would skip (an 8x8 CU
+ * in NxN or an AMP mode) or whose reference resolves outside the table.  The PUs are enumerated on the device: no
+ * host round trip, and a captured call (kvz_hip_graph_begin / _end) may be replayed after the CONTENTS of cus changed.
+ * The records of all SCUs of one PU must agree about the CU's depth and type (cu_array_t holds copies of one
+ * cu_info_t, cu.c:167-190); a map that disagrees inside a PU is a caller error: the output inside that CU is
+ * unspecified, but no access leaves the planes.  refs, params: HOST, copied at the call.  width, height: multiples of 8
+ * and the size of every reference picture.  Coordinates are picture-wide, as for kvz_hip_inter_recon_batch. */
+KVZ_HIP_API int kvz_hip_inter_recon_frame(kvz_hip_pixel *pred_y, uint32_t stride_y, kvz_hip_pixel *pred_u, kvz_hip_pixel *pred_v,
+                                          uint32_t stride_c, int width, int height, const kvz_hip_cu_info *cus,
+                                          const kvz_hip_ref_picture *refs, const kvz_hip_inter_recon_params *params,
+                                          kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */
 /* ------------------------------------------------------------------ */
 /* kvz_strategyselector_register (strategyselector.h:87, strategyselector.c:216-256) */

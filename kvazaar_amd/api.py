@@ -514,6 +514,80 @@ def deblock_frame(y, u, v, cus, prm):
     return (dy.to_numpy(np.uint8, y.shape), du.to_numpy(np.uint8, u.shape) if du else None, dv.to_numpy(np.uint8, v.shape) if dv else None)
 
 
+# ---- motion compensation (inter recon) ----
+REF_PICTURE = np.dtype([("y", "<u8"), ("u", "<u8"), ("v", "<u8"), ("stride_y", "<u4"), ("stride_c", "<u4"),
+                        ("width", "<i4"), ("height", "<i4")])                                  # kvz_hip_ref_picture
+INTER_PU = np.dtype([("x", "<i4"), ("y", "<i4"), ("width", "<i4"), ("height", "<i4"), ("mv", "<i2", (2, 2)),
+                     ("mv_dir", "u1"), ("ref", "u1", (2,)), ("pad", "u1")])                    # kvz_hip_inter_pu
+INTER_RECON_PARAMS = np.dtype([("chroma", "<i4"), ("n_refs", "<i4"), ("ref_LX", "u1", (2, 16))])   # kvz_hip_inter_recon_params
+
+
+def ref_picture_table(planes, width, height):
+    """kvz_hip_ref_picture records for device planes: planes = [(y, u, v, stride_y, stride_c)] with device pointers (u, v: 0 / None for 4:0:0)"""
+    t = np.zeros(len(planes), dtype=REF_PICTURE)
+    for i, (y, u, v, sy, sc) in enumerate(planes):
+        t[i] = (y or 0, u or 0, v or 0, sy, sc, width, height)
+    return t
+
+
+class _Recon:
+    """stages reference pictures and a destination for the two inter recon entries"""
+
+    def __init__(self, refs, shape, chroma, dest):
+        h, w = int(shape[0]), int(shape[1])
+        self.h, self.w, self.chroma, self.keep = h, w, int(chroma), []
+        planes = []
+        for r in refs:
+            arrs = [np.ascontiguousarray(p, dtype=np.uint8) if p is not None else None for p in (tuple(r) + (None, None))[:3]]
+            bufs = [DeviceBuffer.from_numpy(p) if p is not None and (k == 0 or chroma) else None for k, p in enumerate(arrs)]
+            self.keep += bufs
+            planes.append((bufs[0].ptr, bufs[1].ptr if bufs[1] else 0, bufs[2].ptr if bufs[2] else 0, arrs[0].shape[1],
+                           arrs[1].shape[1] if bufs[1] else 0))
+        self.table = ref_picture_table(planes, w, h)
+        if dest is None:
+            dest = (np.zeros((h, w), np.uint8), np.zeros((h // 2, w // 2), np.uint8), np.zeros((h // 2, w // 2), np.uint8))
+        self.dest = [np.ascontiguousarray(p, dtype=np.uint8) if p is not None and (k == 0 or chroma) else None
+                     for k, p in enumerate((tuple(dest) + (None, None))[:3])]
+        self.dbuf = [DeviceBuffer.from_numpy(p) if p is not None else None for p in self.dest]
+
+    def dptr(self, k):
+        return self.dbuf[k].ptr if self.dbuf[k] else None
+
+    def stride_c(self):
+        return self.dest[1].shape[1] if self.dest[1] is not None else 0
+
+    def result(self):
+        return tuple(b.to_numpy(np.uint8, p.shape) if b else None for b, p in zip(self.dbuf, self.dest))
+
+
+def inter_recon_batch(refs, pus, shape, chroma=1, dest=None):
+    """kvz_hip_inter_recon_batch.  refs: [(y, u, v)] uint8 planes of the reference pictures (u, v None for 4:0:0), each at least
+    shape = (height, width) large -- a larger array gives a stride beyond the width; pus: INTER_PU records; dest: optional initial
+    (y, u, v) destination planes (default zeros of the picture size; again a wider array gives a stride).  Returns (y, u, v)."""
+    L = _lib.init()
+    pus = np.ascontiguousarray(pus, dtype=INTER_PU)
+    st = _Recon(refs, shape, chroma, dest)
+    d = DeviceBuffer.from_numpy(pus.view(np.uint8))
+    check(L.kvz_hip_inter_recon_batch(st.table.ctypes.data, len(st.table), d.ptr, len(pus), st.dptr(0), st.dest[0].shape[1],
+                                      st.dptr(1), st.dptr(2), st.stride_c(), int(chroma), None), "inter_recon batch")
+    return st.result()
+
+
+def inter_recon_frame(refs, cus, ref_LX, width, height, chroma=1, dest=None):
+    """kvz_hip_inter_recon_frame.  refs, dest: as inter_recon_batch; cus: kvz_hip_cu_info records [height / 4, width / 4] (20 bytes
+    each); ref_LX: uint8 [2, 16].  Returns (y, u, v)."""
+    L = _lib.init()
+    cus = np.ascontiguousarray(cus)
+    assert cus.dtype.itemsize == 20 and cus.shape == (height // 4, width // 4)
+    st = _Recon(refs, (height, width), chroma, dest)
+    prm = np.zeros(1, dtype=INTER_RECON_PARAMS)
+    prm["chroma"], prm["n_refs"], prm["ref_LX"] = int(chroma), len(st.table), np.asarray(ref_LX, dtype=np.uint8).reshape(2, 16)
+    c = DeviceBuffer.from_numpy(cus.view(np.uint8))
+    check(L.kvz_hip_inter_recon_frame(st.dptr(0), st.dest[0].shape[1], st.dptr(1), st.dptr(2), st.stride_c(), width, height, c.ptr,
+                                      st.table.ctypes.data, prm.ctypes.data, None), "inter_recon frame")
+    return st.result()
+
+
 # ---- tile halo exchange: batched rectangle copies on device pointers ----
 def copy_rects(rects, stream=None):
     """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most

@@ -232,6 +232,91 @@ def main():
             print("%-26s %10s %12.1f %10.1f %8.4f" % (name, "-" if v is None else v, blocks / ms / 1e3, blocks * bpb / ms / 1e6, ms))
     if tune_key:
         L.kvz_hip_set_tuning(tune_key.encode(), -1)
+    if not args.only or any(o in "inter_recon_frame_p inter_recon_frame_b" for o in args.only.split(",")):
+        inter_recon_rows(L, st, dev, max(args.rounds, 5))
+
+
+def inter_recon_rows(L, st, dev, rounds, frames=64):
+    """Motion compensation of whole pictures (kvz_hip_inter_recon_frame) against the chain of entries that could produce the same
+    planes before it existed, on the same PU list, interleaved round by round, medians.  1080p pictures of a random quadtree
+    (depths 0..3, every part mode, random quarter-pel vectors), `frames` of them stacked in one tall picture per launch (1088 rows
+    apart, so that the LCU grid of every picture starts on a multiple of 64).  _p: one reference; _b: the same map bi-predicted from
+    two.  Algorithmic bytes: 1.5 W H written + 1.5 W H read per reference."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inter_recon_cases as IC
+    from kvazaar_amd import api
+    W, H, PITCH = 1920, 1080, 1088
+    TH = PITCH * frames
+    g = torch.Generator(device=dev); g.manual_seed(7)
+    planes = [[torch.randint(0, 256, (TH >> c, W >> c), dtype=torch.uint8, device=dev, generator=g) for c in (0, 1, 1)] for _ in range(2)]
+    dest = [torch.empty((TH >> c, W >> c), dtype=torch.uint8, device=dev) for c in (0, 1, 1)]
+    table = api.ref_picture_table([(p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), W, W // 2) for p in planes], W, TH)
+    print("%-26s %10s %12s %10s %8s %8s" % ("kernel", "frames", "frames/s", "GB/s", "ms", "vs chain"))
+    for name, n_refs in (("inter_recon_frame_p", 1), ("inter_recon_frame_b", 2)):
+        one = np.zeros((PITCH // 4, W // 4), dtype=IC.CU_INFO)
+        cus, ref_LX = IC.random_cu_map(W, H, 31, 1, False, intra_share=0.0, blank_share=0.0, bad_share=0.0, far=0.0)
+        if n_refs == 2:                                                   # the same map, every PU from both lists
+            rs = np.random.default_rng(32)
+            cus["mv_dir"][cus["type"] == IC.CU_INTER] = 3
+            cus["mv"][:, :, 1, :] = rs.integers(-160, 161, cus["mv"][:, :, 1, :].shape)
+            ref_LX[1, 0] = 1
+        one[:H // 4] = cus
+        pus1 = IC.walk_pus(one, ref_LX, W, PITCH)
+        pus = np.tile(pus1, frames)
+        pus["y"] += np.repeat(np.arange(frames, dtype=np.int32) * PITCH, len(pus1))
+        cus_d = torch.from_numpy(np.tile(one, (frames, 1)).view(np.uint8).copy()).to(dev)
+        prm = np.zeros(1, dtype=api.INTER_RECON_PARAMS)
+        prm["chroma"], prm["n_refs"], prm["ref_LX"] = 1, n_refs, ref_LX
+
+        def fused():
+            return L.kvz_hip_inter_recon_frame(dest[0].data_ptr(), W, dest[1].data_ptr(), dest[2].data_ptr(), W // 2, W, TH, cus_d.data_ptr(),
+                                               table.ctypes.data, prm.ctypes.data, st)
+        # the chain: per reference sample_luma_batch + 2 x sample_chroma_batch into compact blocks (14-bit for _b), then 3 x bipred_blend_batch
+        area = pus["width"].astype(np.int64) * pus["height"]
+        offs = [torch.from_numpy(np.concatenate([[0], np.cumsum(area >> (2 * c))[:-1]]).astype(np.int64)).to(dev) for c in (0, 1)]
+        total = [int(area.sum()) >> (2 * c) for c in (0, 1)]
+        blocks = []
+        for lst in range(n_refs):
+            per = []
+            for c in (0, 1):
+                b = np.zeros((len(pus), 6), dtype=np.int32)
+                mv = pus["mv"][:, lst, :].astype(np.int32)
+                b[:, 0], b[:, 1] = (pus["x"] >> c) + (mv[:, 0] >> (2 + c)), (pus["y"] >> c) + (mv[:, 1] >> (2 + c))
+                b[:, 2], b[:, 3] = mv[:, 0] & (7 if c else 3), mv[:, 1] & (7 if c else 3)
+                b[:, 4], b[:, 5] = pus["width"] >> c, pus["height"] >> c
+                per.append(torch.from_numpy(b).to(dev))
+            blocks.append(per)
+        esz = 2 if n_refs == 2 else 1
+        mid = [[torch.empty(total[1 if k else 0] * esz, dtype=torch.uint8, device=dev) for k in range(3)] for _ in range(n_refs)]
+        out = [torch.empty(total[1 if k else 0], dtype=torch.uint8, device=dev) for k in range(3)]
+
+        def chain():
+            for lst in range(n_refs):
+                for k in range(3):
+                    c = 1 if k else 0
+                    f = L.kvz_hip_sample_chroma_batch if k else L.kvz_hip_sample_luma_batch
+                    rc = f(planes[lst][k].data_ptr(), W >> c, W >> c, TH >> c, blocks[lst][c].data_ptr(), offs[c].data_ptr(), len(pus),
+                           int(n_refs == 2), mid[lst][k].data_ptr(), st)
+                    if rc:
+                        return rc
+            if n_refs == 2:
+                for k in range(3):
+                    rc = L.kvz_hip_bipred_blend_batch(8 if k == 0 else 4, 4 if k == 0 else 2, 1, mid[0][k].data_ptr(), 1, mid[1][k].data_ptr(),
+                                                      out[k].data_ptr(), total[1 if k else 0] // (32 if k == 0 else 8), st)
+                    if rc:
+                        return rc
+            return 0
+        torch.cuda.synchronize()
+        t = {"fused": [], "chain": []}
+        for _ in range(rounds):
+            t["fused"].append(timed(L, st, lambda: _lib.check(fused(), name), iters=5, warm=1))
+            t["chain"].append(timed(L, st, lambda: _lib.check(chain(), name + " chain"), iters=5, warm=1))
+        ms, ms_chain = float(np.median(t["fused"])), float(np.median(t["chain"]))
+        nbytes = 1.5 * W * H * frames * (1 + n_refs)
+        print("%-26s %10d %12.1f %10.1f %8.4f %8.2f" % (name, frames, frames / ms * 1e3, nbytes / ms / 1e6, ms, ms_chain / ms))
+        print("%-26s %10d %12.1f %10.1f %8.4f %8s" % (name + "(chain)", frames, frames / ms_chain * 1e3, nbytes / ms_chain / 1e6, ms_chain, "-"))
+        print("#   %d PUs per picture; fraction of the 8 TB/s HBM roofline: fused %.3f, chain %.3f" % (len(pus1), nbytes / ms / 1e6 / 8000, nbytes / ms_chain / 1e6 / 8000))
 
 
 if __name__ == "__main__":

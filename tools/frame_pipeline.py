@@ -3,7 +3,7 @@
 
   eager    every entry enqueued on one stream, frame after frame
   graph    the frame's launch sequence captured once (kvz_hip_graph_begin/_end), replayed per frame
-  graph4   the same, with the four independent stages (motion search, intra rough search, TU
+  graph4   the same, with the four independent stages (motion search, intra rough search, prediction + TU
            reconstruction + cost, SAO statistics) on forked streams = parallel branches of the graph
   graph7   the four motion-search launches (one per PU size class) on a branch each as well
   eager4/7 the forked streams without the graph
@@ -80,6 +80,22 @@ def build_stages(L, dev):
         stages["intra"].append(("intra_rough_%dx%d" % (n, n), cnt,
                                 lambda s, lg=lg, cnt=cnt, refs_d=refs_d, costs_d=costs_d: L.kvz_hip_intra_rough_batch(
                                     lg, 3, refs_d.data_ptr(), flat_cur.data_ptr(), cnt, costs_d.data_ptr(), None, s)))
+
+    # prediction: the motion compensation of the whole picture from its CU array, the producer of the TU stage's pred_in (it
+    # leads that stage's branch in the forked forms)
+    import inter_recon_cases as IC
+    from kvazaar_amd import api
+    rc_cus, rc_LX = IC.random_cu_map(W, H, 31, 1, False, intra_share=0.1, blank_share=0.0, bad_share=0.0, far=0.0)
+    rc_cus_d = torch.from_numpy(rc_cus.view(np.uint8).copy()).to(dev)
+    rc_ref = [ref] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
+    rc_dst = [torch.empty((H >> c, W >> c), dtype=torch.uint8, device=dev) for c in (0, 1, 1)]
+    rc_tab = api.ref_picture_table([(rc_ref[0].data_ptr(), rc_ref[1].data_ptr(), rc_ref[2].data_ptr(), W, W // 2)], W, H)
+    rc_prm = np.zeros(1, dtype=api.INTER_RECON_PARAMS)
+    rc_prm["chroma"], rc_prm["n_refs"], rc_prm["ref_LX"] = 1, 1, rc_LX
+    keep += [rc_cus_d, rc_ref, rc_dst, rc_tab, rc_prm]
+    stages["tu"].append(("inter_recon_frame", 1, lambda s: L.kvz_hip_inter_recon_frame(
+        rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data,
+        rc_prm.ctypes.data, s)))
 
     qp = QuantParams(); qp.qp = 27
     keep.append(qp)
