@@ -867,6 +867,70 @@ KVZ_HIP_API int kvz_hip_inter_recon_frame(kvz_hip_pixel *pred_y, uint32_t stride
                                           kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
+/* residual coding and reconstruction of a picture's inter CUs         */
+/*   reference: kvz_quantize_lcu_residual (transform.c:424-482, called */
+/*   at search.c:587) over quantize_tr_residual (transform.c:281-406)  */
+/*   and the rdoq-off path of kvz_quantize_residual                    */
+/*   (quant-generic.c:180-273); flags as lcu_set_coeff leaves them     */
+/*   (search.c:173-190); cost inputs of search.c:580-642               */
+/* ------------------------------------------------------------------ */
+typedef struct {
+  int32_t qp;               /* state->qp: one QP per call */
+  int32_t slice_is_intra;   /* state->frame->slicetype == KVZ_SLICE_I */
+  int32_t signhide;         /* encoder->cfg.signhide_enable */
+  int32_t scaling_list;     /* must be 0: flat lists only */
+  int32_t chroma;           /* 0: 4:0:0 (U / V pointers unused), 1: 4:2:0 */
+  int32_t reserved;
+} kvz_hip_inter_residual_params;   /* 24 bytes; the first four fields are those of kvz_hip_quant_params */
+/* What the rd=0 cost of a CU and its zero-coefficient alternative are made of (search.c:580-642), as raw integers: the caller
+ * applies the chroma weight and lambda.  c = U + V. */
+typedef struct {
+  uint32_t ssd_y, ssd_c;             /* sum of kvz_pixels_calc_ssd(source, reconstruction) over the CU's TUs */
+  uint32_t zero_ssd_y, zero_ssd_c;   /* the same against the PREDICTION: the input of cu_zero_coeff_cost */
+  uint32_t coeff_abs_y, coeff_abs_c; /* sum of kvz_coeff_abs_sum over the CU's TUs */
+} kvz_hip_inter_residual_cost;     /* 24 bytes */
+/* kvz_quantize_lcu_residual for every inter CU of a picture, in one asynchronous call, between kvz_hip_inter_recon_frame and
+ * kvz_hip_deblock_frame: prediction -> residual coding -> deblocking of a picture are three calls on one stream, driven by
+ * one CU array, with no host involvement.
+ * src: HOST, copied at the call; the source picture (DEVICE planes, const); its width / height (multiples of 8) are the
+ *   picture's.  rec_y / rec_u / rec_v: DEVICE planes that hold the PREDICTION on entry (what kvz_hip_inter_recon_frame wrote)
+ *   and the reconstruction on return -- in place, as lcu->rec in the reference.  cus: DEVICE, one kvz_hip_cu_info per 4x4 SCU,
+ *   row-major, ceil(width / 4) per row, 4-byte aligned; READ AND WRITTEN.  params: HOST, copied at the call.
+ * Which CUs: records of type CU_INTER; a CU is 64 >> depth wide at the SCU position rounded down to that size, and a CU that
+ *   would leave the picture is skipped (the rules of kvz_hip_inter_recon_frame).  Everything that belongs to other records
+ *   is left untouched: rec, coefficients, flags, costs.
+ * Transform tree (transform.c:448-481): the luma leaf depth is max(depth, tr_depth, 1), at most 4 -- luma TUs 32 / 16 / 8 / 4
+ *   wide -- with tr_depth READ FROM THE MAP (from the record at the TU's own top-left SCU), not derived from part_size.  Chroma
+ *   TUs are half as wide; with 4x4 luma TUs the chroma of the 8x8 area is one 4x4 TU per plane (transform.c:293-313).
+ * Per TU: kvz_quantize_residual, rdoq off (quant-generic.c:180-273), cu_is_intra = 0, diagonal scan (kvz_get_scan_order of
+ *   an inter CU), no transform skip; bit-exact with the generic strategy at bit depth 8.  OUT OF SCOPE: lossless coding,
+ *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID) and per-CU QP (the qp field of
+ *   the records is not read).  Intra CUs need their neighbours' reconstruction and are not handled, as in
+ *   kvz_hip_inter_recon_frame.
+ * Outputs:
+ *   rec planes: the reconstruction inside the inter CUs (a TU without coefficients keeps its prediction).
+ *   coeff_y / coeff_u / coeff_v: DEVICE, 16-byte aligned, the layout of lcu->coeff: per LCU, in raster order of the
+ *     ceil(width / 64) x ceil(height / 64) LCUs, 4096 luma and 1024 + 1024 chroma values; the w * w values of a TU at (lx, ly)
+ *     inside its LCU are contiguous and row-major at xy_to_zorder(64, lx, ly) (chroma: xy_to_zorder(32, lx / 2, ly / 2)),
+ *     cu.h:373-410.  A TU without coefficients gets zeros.
+ *   cus[i].cbf_y of every SCU of an inter CU = has_coeffs of the luma leaf TU that covers it: what lcu_set_coeff
+ *     (search.c:173-190) leaves for the deblocking filter, so kvz_hip_deblock_frame can run next on the same array.
+ *   cbf_out (optional, may be NULL): DEVICE, one byte per SCU: bit 0 Y, bit 1 U, bit 2 V of the covering leaf TUs.
+ *   costs (optional, may be NULL): DEVICE, shaped like cus; the record at the index of each inter CU's top-left SCU
+ *     receives the CU's sums.  Integer sums: the result does not depend on scheduling.
+ * Asynchronous on s; no host synchronisation, no allocation and no scratch memory.  Usable between kvz_hip_graph_begin / _end,
+ * and a captured call may be replayed after the CONTENTS of cus, of the source and of the prediction changed: the TUs are
+ * found on the device by launches of a fixed shape.  The records of all SCUs of one CU must agree; a map that disagrees
+ * inside a CU is a caller error with unspecified output inside that CU, but no access leaves the planes or arrays.
+ * A missing required pointer, a size that is not a multiple of 8, a stride below the width or scaling_list != 0 returns
+ * KVZ_HIP_ERR_INVALID and nothing is written. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                             kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                             kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
+                                             uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                             const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */
 /* ------------------------------------------------------------------ */
 /* kvz_strategyselector_register (strategyselector.h:87, strategyselector.c:216-256) */

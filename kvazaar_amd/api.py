@@ -588,6 +588,62 @@ def inter_recon_frame(refs, cus, ref_LX, width, height, chroma=1, dest=None):
     return st.result()
 
 
+# ---- residual coding of a picture's inter CUs ----
+INTER_RESIDUAL_PARAMS = np.dtype([("qp", "<i4"), ("slice_is_intra", "<i4"), ("signhide", "<i4"), ("scaling_list", "<i4"),
+                                  ("chroma", "<i4"), ("reserved", "<i4")])                      # kvz_hip_inter_residual_params
+INTER_RESIDUAL_COST = np.dtype([("ssd_y", "<u4"), ("ssd_c", "<u4"), ("zero_ssd_y", "<u4"), ("zero_ssd_c", "<u4"),
+                                ("coeff_abs_y", "<u4"), ("coeff_abs_c", "<u4")])                # kvz_hip_inter_residual_cost
+
+
+def inter_residual_params(qp, slice_is_intra=0, signhide=0, chroma=1, scaling_list=0):
+    p = np.zeros(1, dtype=INTER_RESIDUAL_PARAMS)
+    p["qp"], p["slice_is_intra"], p["signhide"], p["scaling_list"], p["chroma"] = qp, slice_is_intra, signhide, scaling_list, chroma
+    return p
+
+
+def coeff_shapes(width, height):
+    """shapes of the luma and chroma coefficient arrays: (LCUs, 4096) and (LCUs, 1024)"""
+    n = ((width + 63) // 64) * ((height + 63) // 64)
+    return (n, 4096), (n, 1024)
+
+
+def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None):
+    """kvz_hip_inter_residual_frame.  src: (y, u, v) uint8 planes of the source picture (its luma shape is the picture size;
+    u, v None for 4:0:0); pred: (y, u, v) planes holding the prediction, at least as large (a wider array gives a stride);
+    cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
+    (default zeros).  Returns a dict: rec (y, u, v), coeff (y, u, v) as [LCUs, 4096 / 1024] int16, cus (with cbf_y set), cbf_out
+    uint8 [height / 4, width / 4], costs INTER_RESIDUAL_COST [height / 4, width / 4]."""
+    L = _lib.init()
+    chroma = int(chroma)
+    height, width = src[0].shape
+    cus = np.ascontiguousarray(cus)
+    assert cus.dtype.itemsize == 20 and cus.shape == (height // 4, width // 4)
+    n = 3 if chroma else 1
+    s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
+    r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
+    ds, dr = [DeviceBuffer.from_numpy(p) for p in s], [DeviceBuffer.from_numpy(p) for p in r]
+    table = ref_picture_table([(ds[0].ptr, ds[1].ptr if chroma else 0, ds[2].ptr if chroma else 0, s[0].shape[1],
+                                s[1].shape[1] if chroma else 0)], width, height)
+    shapes = coeff_shapes(width, height)
+    co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
+          else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
+    dco = [DeviceBuffer.from_numpy(c) for c in co]
+    cb = np.zeros(cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(cus.shape)
+    cs = np.zeros(cus.shape, INTER_RESIDUAL_COST) if costs is None else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(cus.shape)
+    dcb, dcs, dcu = DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(cs.view(np.uint8)), DeviceBuffer.from_numpy(cus.view(np.uint8))
+    prm = inter_residual_params(qp, slice_is_intra, signhide, chroma)
+    check(L.kvz_hip_inter_residual_frame(table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None,
+                                         dr[2].ptr if chroma else None, r[1].shape[1] if chroma else 0, dcu.ptr, dco[0].ptr,
+                                         dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr,
+                                         prm.ctypes.data, None), "inter_residual frame")
+    pad = (None,) * (3 - n)
+    return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
+            "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
+            "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
+            "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
+            "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+
+
 # ---- tile halo exchange: batched rectangle copies on device pointers ----
 def copy_rects(rects, stream=None):
     """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most

@@ -234,6 +234,8 @@ def main():
         L.kvz_hip_set_tuning(tune_key.encode(), -1)
     if not args.only or any(o in "inter_recon_frame_p inter_recon_frame_b" for o in args.only.split(",")):
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
+    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k" for o in args.only.split(",")):
+        inter_residual_rows(L, st, dev, max(args.rounds, 5))
 
 
 def inter_recon_rows(L, st, dev, rounds, frames=64):
@@ -317,6 +319,108 @@ def inter_recon_rows(L, st, dev, rounds, frames=64):
         print("%-26s %10d %12.1f %10.1f %8.4f %8.2f" % (name, frames, frames / ms * 1e3, nbytes / ms / 1e6, ms, ms_chain / ms))
         print("%-26s %10d %12.1f %10.1f %8.4f %8s" % (name + "(chain)", frames, frames / ms_chain * 1e3, nbytes / ms_chain / 1e6, ms_chain, "-"))
         print("#   %d PUs per picture; fraction of the 8 TB/s HBM roofline: fused %.3f, chain %.3f" % (len(pus1), nbytes / ms / 1e6 / 8000, nbytes / ms_chain / 1e6 / 8000))
+
+
+def inter_residual_rows(L, st, dev, rounds, iters=6):
+    """Residual coding of whole pictures (kvz_hip_inter_residual_frame: all-inter random quadtree with tr_depth as the search sets it and
+    a share of deeper trees, 4:2:0, source = prediction + noise of one amplitude per CU) against kvz_hip_quantize_residual_batch over the
+    SAME TU population laid out contiguously, one call per size and plane, summed: the same arithmetic without plane addressing and
+    without the gather a caller would add -- a lower bound of what the picture cost before the entry existed.  Interleaved round by
+    round in one process, medians.  The entry works in place, so every timed call gets a fresh copy of the prediction (copied outside
+    the timed region).  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
+    Algorithmic bytes: 5 per sample = 7.5 per luma pixel, + 20 per 16 luma pixels of map."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inter_recon_cases as IC
+    import inter_residual_cases as RC
+    from patterns import deblock_params
+    from kvazaar_amd import api
+    print("%-28s %10s %12s %10s %8s %8s" % ("kernel", "TUs", "frames/s", "GB/s", "ms", "contig/ms"))
+    for name, W, H in (("inter_residual_frame_1080p", 1920, 1080), ("inter_residual_frame_4k", 3840, 2160)):
+        cus, ref_LX = RC.make_map(W, H, 41, intra_share=0.0, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+        pred = RC.smooth_planes(W, H, 42)
+        src = RC.make_source(pred, cus, 43)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+        src_d, master = [up(p) for p in src], [up(p) for p in pred]
+        recs = [[torch.empty_like(m) for m in master] for _ in range(iters + 1)]
+        cus_d = up(cus)
+        shapes = api.coeff_shapes(W, H)
+        co_d = [torch.empty(shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+        cbf_d = torch.empty(cus.shape, dtype=torch.uint8, device=dev)
+        cost_d = torch.empty(cus.shape + (6,), dtype=torch.int32, device=dev)
+        table = api.ref_picture_table([(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2)], W, H)
+        prm = api.inter_residual_params(32, 0, 0, 1)
+        turn = [0]
+
+        def frame():
+            r = recs[turn[0] % len(recs)]
+            turn[0] += 1
+            return L.kvz_hip_inter_residual_frame(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
+                                                  co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
+                                                  prm.ctypes.data, st)
+        # the same TUs, contiguous, per (plane, size)
+        groups = {}
+        for t in RC.walk_tus(cus, W, H):
+            groups.setdefault((t[0], t[3]), []).append(t)
+        contig = []
+        qp = _lib.QuantParams()
+        qp.qp = 32
+        for (p, n), lst in sorted(groups.items()):
+            a = np.array(lst, dtype=np.int64)
+            xs, ys = a[:, 1] >> (1 if p else 0), a[:, 2] >> (1 if p else 0)
+            rb, pb = RC._blocks(src[p], xs, ys, n)[0], RC._blocks(pred[p], xs, ys, n)[0]
+            rb_d, pb_d = up(rb), up(pb)
+            contig.append((n, p, len(lst), rb_d, pb_d, torch.empty_like(pb_d), torch.empty(len(lst) * n * n, dtype=torch.int16, device=dev),
+                           torch.empty(len(lst), dtype=torch.int32, device=dev)))
+
+        def batches():
+            for (n, p, count, rb_d, pb_d, rec_d, c_d, has_d) in contig:
+                rc = L.kvz_hip_quantize_residual_batch(C.byref(qp), 0, n, p, 0, 0, rb_d.data_ptr(), pb_d.data_ptr(), rec_d.data_ptr(), c_d.data_ptr(),
+                                                       has_d.data_ptr(), count, st)
+                if rc:
+                    return rc
+            return 0
+
+        def refresh():
+            for r in recs:
+                for d, m in zip(r, master):
+                    d.copy_(m)
+            torch.cuda.synchronize()
+            turn[0] = 0
+        t = {"frame": [], "contig": []}
+        for _ in range(rounds):
+            refresh()
+            t["frame"].append(timed(L, st, lambda: _lib.check(frame(), name), iters=iters - 1, warm=1))
+            t["contig"].append(timed(L, st, lambda: _lib.check(batches(), name + " contiguous"), iters=iters - 1, warm=1))
+        ms, ms_c = float(np.median(t["frame"])), float(np.median(t["contig"]))
+        n_tus = sum(c[2] for c in contig)
+        nbytes = 7.5 * W * H + 20.0 * W * H / 16
+        print("%-28s %10d %12.1f %10.1f %8.4f %8.2f" % (name, n_tus, 1e3 / ms, nbytes / ms / 1e6, ms, ms_c / ms))
+        print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "(contig)", n_tus, 1e3 / ms_c, 7.5 * W * H / ms_c / 1e6, ms_c, "-"))
+        print("#   fraction of the 8 TB/s HBM roofline: frame %.3f, contiguous sum %.3f; %d launches against %d" %
+              (nbytes / ms / 1e6 / 8000, 7.5 * W * H / ms_c / 1e6 / 8000, 5, len(contig)))
+        if W != 1920:
+            continue
+        # the chain on one stream: kvz_hip_inter_recon_frame -> kvz_hip_inter_residual_frame -> kvz_hip_deblock_frame
+        g = torch.Generator(device=dev); g.manual_seed(9)
+        ref = [torch.randint(0, 256, (H >> c, W >> c), dtype=torch.uint8, device=dev, generator=g) for c in (0, 1, 1)]
+        rtab = api.ref_picture_table([(ref[0].data_ptr(), ref[1].data_ptr(), ref[2].data_ptr(), W, W // 2)], W, H)
+        rprm = np.zeros(1, dtype=api.INTER_RECON_PARAMS)
+        rprm["chroma"], rprm["n_refs"], rprm["ref_LX"] = 1, 1, ref_LX
+        dprm = deblock_params(qp=32)
+        dprm["ref_LX"] = ref_LX
+        r = recs[0]
+
+        def chain():
+            rc = L.kvz_hip_inter_recon_frame(r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, W, H, cus_d.data_ptr(), rtab.ctypes.data,
+                                             rprm.ctypes.data, st)
+            rc = rc or L.kvz_hip_inter_residual_frame(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
+                                                      co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
+                                                      prm.ctypes.data, st)
+            return rc or L.kvz_hip_deblock_frame(r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, W, H, cus_d.data_ptr(), dprm.ctypes.data, st)
+        torch.cuda.synchronize()
+        tc = [timed(L, st, lambda: _lib.check(chain(), "chain"), iters=5, warm=1) for _ in range(rounds)]
+        print("%-28s %10s %12.1f %10s %8.4f %8s" % ("recon+residual+deblock_1080p", "-", 1e3 / float(np.median(tc)), "-", float(np.median(tc)), "-"))
 
 
 if __name__ == "__main__":
