@@ -223,6 +223,19 @@ KVZ_HIP_API int kvz_hip_sad_nxn_dual_batch(int n, const kvz_hip_pixel *preds, si
 KVZ_HIP_API int kvz_hip_satd_nxn_dual_batch(int n, const kvz_hip_pixel *preds, size_t pred_stride, size_t item_stride,
                                             const kvz_hip_pixel *orig, size_t count, uint32_t *costs, kvz_hip_stream s);
 
+/* PLANES.  Every entry that takes a picture plane takes it as a pointer, a row stride in bytes and (where it clamps) a
+ * width and a height: a rectangle inside any larger device buffer, e.g. the extended buffer of a shard.  Unless an entry
+ * says otherwise below
+ *   - the pointer may have ANY alignment (an odd address included) and the stride may be ANY value >= the width, odd
+ *     ones included: pixels are fetched with byte-addressed vector loads, never with loads that need an aligned address;
+ *   - every plane of a call has its own stride (pic / ref, ref0 / ref1, rec / new_rec, luma / chroma are independent);
+ *   - nothing left of the pointer, right of the width (the bytes between width and stride), above the first or below
+ *     the last row is read or written.
+ * The exceptions document their rule at the entry and refuse what breaks it with KVZ_HIP_ERR_INVALID:
+ * kvz_hip_deblock_frame and the CU-map entries built like it (4-byte aligned planes and strides).  The search service
+ * owns its planes (width a multiple of 4, PU x a multiple of 4) and is not concerned.
+ * tests/test_gpu_plane_layout.py holds each of these entries to this on padded, offset and odd layouts. */
+
 /* One block pair inside two planes; the unit of the frame-level entries below. */
 typedef struct {
   int32_t x1, y1;          /* top-left of the block in plane 1 (the picture being coded) */
@@ -232,7 +245,9 @@ typedef struct {
 
 /* reg_sad_func (picture-generic.c:86-99) over a list of block pairs that lie
  * INSIDE their planes: costs[i] = reg_sad(p1 + y1*stride1 + x1, p2 + y2*stride2 + x2, w, h, ..).
- * Any width/height >= 1 (tests/sad_tests.c:369-376 shapes, 64x63, 1x1). */
+ * Any width/height >= 1 (tests/sad_tests.c:369-376 shapes, 64x63, 1x1).
+ * Planes: any base alignment, any strides >= the widths in use, stride1 and stride2 independent (PLANES above); the
+ * same holds for the three entries that follow. */
 KVZ_HIP_API int kvz_hip_reg_sad_batch(const kvz_hip_pixel *plane1, uint32_t stride1,
                                       const kvz_hip_pixel *plane2, uint32_t stride2,
                                       const kvz_hip_block_pair *pairs, size_t count,
@@ -259,7 +274,8 @@ KVZ_HIP_API int kvz_hip_pixels_calc_ssd_batch(const kvz_hip_pixel *plane1, uint3
  * including its behaviour for widths/heights that are not multiples of 8:
  * item i compares 4 candidate blocks preds + (4*i + k)*pred_item_stride
  * (row stride pred_stride, 64 in search_inter.c:1076) with the block at
- * (x1,y1) of `orig`; costs[4*i + k]. */
+ * (x1,y1) of `orig`; costs[4*i + k].  orig: any base alignment and stride; preds: any pred_stride >= the width and
+ * any pred_item_stride >= height * pred_stride, the bytes in the gaps are not read. */
 KVZ_HIP_API int kvz_hip_satd_any_size_quad_batch(const kvz_hip_pixel *preds, uint32_t pred_stride, size_t pred_item_stride,
                                                  const kvz_hip_pixel *orig, uint32_t orig_stride,
                                                  const kvz_hip_block_pair *pairs, size_t count,
@@ -275,7 +291,9 @@ KVZ_HIP_API int kvz_hip_satd_any_size_quad_batch(const kvz_hip_pixel *preds, uin
  * (edge replicated).  PUs not entirely inside `pic` (ragged last CTU row/column)
  * get 0xFFFFFFFF.  The CTU's source block and its search window are fetched from
  * HBM once and stay in LDS; larger PUs are sums of the 8x8 SADs.
- * |mv_offsets| <= 64 in each component. */
+ * |mv_offsets| <= 64 in each component.
+ * pic and ref: any base alignment, any stride >= the width, independent of each other; the window is clamped against
+ * ref_w / ref_h, never against the stride. */
 typedef struct {
   int32_t x, y;            /* CTU top-left in the picture (multiples of 8) */
   int32_t mvx, mvy;        /* search centre, full-pel */
@@ -485,7 +503,11 @@ typedef struct {
  * kvz_image_calc_sad + calc_mvd_cost, then search_frac (:965-1128) -- or, for
  * fme_level 0, the SATD re-cost of :1236-1248.  Same visiting order and
  * tie-breaks as the reference, so results[i] equals what the reference leaves
- * in inter_search_info_t.  pus / results are device arrays. */
+ * in inter_search_info_t.  pus / results are device arrays.
+ * pic and ref: any base alignment, any stride >= the width (odd ones included), independent of each other, for every
+ * algorithm, with mv_rdo and with a tile -- the exhaustive search (algorithm 3) included: its kernels here stage the
+ * current block in LDS with byte-addressed loads.  (Only the search service prices the block from scalar dword loads;
+ * it owns its planes and keeps them 4-byte aligned itself.) */
 KVZ_HIP_API int kvz_hip_search_pu_batch(const kvz_hip_pixel *pic, uint32_t pic_stride, int pic_w, int pic_h,
                                         const kvz_hip_pixel *ref, uint32_t ref_stride, int ref_w, int ref_h,
                                         const kvz_hip_me_pu *pus, size_t count, const kvz_hip_me_params *params,
@@ -496,7 +518,8 @@ KVZ_HIP_API int kvz_hip_search_pu_batch(const kvz_hip_pixel *pic, uint32_t pic_s
  * dependency front of several frames in flight (--owf), of several tiles, of several encoder instances -- shares a launch:
  * a front of a dozen PUs leaves the chip idle, and host threads stop scaling at the runtime's launch rate, but fronts of
  * many pictures merged into one launch cost what one does.  A plane index outside 0 .. n_planes - 1 flags the PU
- * (reserved -1).  mv_rdo is not available here. */
+ * (reserved -1).  mv_rdo is not available here.  The planes of one table share a stride and a size but each may start
+ * at any address of its own buffer: any base alignment, any stride >= the width, pic_stride and ref_stride independent. */
 KVZ_HIP_API int kvz_hip_search_pu_multi_batch(const kvz_hip_pixel *const *pics, uint32_t pic_stride, int pic_w, int pic_h,
                                               const kvz_hip_pixel *const *refs, uint32_t ref_stride, int ref_w, int ref_h, int n_planes,
                                               const kvz_hip_me_pu *pus, size_t count, const kvz_hip_me_params *params,
@@ -656,7 +679,7 @@ KVZ_HIP_API int kvz_hip_inter_candidates_multi_batch(const kvz_hip_inter_picture
  * else the edge-clamped pixels << 6, blended and clipped) scored with kvz_satd_any_size against the source block
  * (:1359-1362).  The caller adds the MV bit costs (:1366-1389).  Quarter-pel vectors; both reference planes have
  * ref_w x ref_h pixels; width, height multiples of 4 in 4..64 and not both 4 mod 8 (every PU shape), block inside the
- * picture (else cost 0xFFFFFFFF). */
+ * picture (else cost 0xFFFFFFFF).  pic, ref0 and ref1: any base alignment, three independent strides >= the widths. */
 typedef struct {
   int32_t x, y, width, height;
   int16_t mv0[2], mv1[2];
@@ -698,7 +721,8 @@ typedef struct { int32_t x, y; } kvz_hip_intra_pos;
  * hold anything.  Entries 0..2N of both arrays are the reference's, the rest
  * is zero.  A position outside the picture or off the 4-pixel grid yields an
  * all-zero record.  refs feeds kvz_hip_intra_predict_batch / _rough_batch on
- * the same stream without a host round trip. */
+ * the same stream without a host round trip.  rec: any base alignment, any stride >= the width of the plane (pixels
+ * are read one byte at a time); nothing right of the plane's width is read. */
 KVZ_HIP_API int kvz_hip_intra_build_reference_batch(int log2_width, int color, const kvz_hip_pixel *rec, int stride,
                                                     int pic_width, int pic_height, const kvz_hip_intra_pos *pus, size_t count,
                                                     kvz_hip_intra_ref *refs, kvz_hip_stream s);
@@ -760,7 +784,9 @@ typedef struct { int32_t x, y, width, height, sao_index; } kvz_hip_sao_block;
  * each block.  Edge blocks read one pixel beyond the block in the directions of
  * their class, so the caller trims them at the picture border like
  * kvz_sao_reconstruct (sao.c:296-318); a descriptor whose reads would leave the
- * plane is skipped.  color 0 Y, 1 U, 2 V. */
+ * plane is skipped -- "the plane" is plane_w x plane_h, not the stride: a read of the bytes between plane_w and the
+ * stride counts as outside.  color 0 Y, 1 U, 2 V.  rec and new_rec: any base alignment, independent strides >=
+ * plane_w; new_rec is written inside the executed blocks only (its other pixels and its padding keep their bytes). */
 KVZ_HIP_API int kvz_hip_sao_reconstruct_color_batch(const kvz_hip_pixel *rec, uint32_t stride, int plane_w, int plane_h,
                                                     kvz_hip_pixel *new_rec, uint32_t new_stride,
                                                     const kvz_hip_sao_block *blocks, size_t count,
@@ -788,7 +814,9 @@ typedef struct {
 /* Filters the planes in place: every vertical edge of the frame, then every
  * horizontal edge (two launches) -- the order the reference's LCU walk with its
  * deferred rightmost 4 pixels (filter.c:711-779) implements.  width / height
- * multiples of 8, planes / strides / cus 4-byte aligned; bitdepth 8, lossless
+ * multiples of 8, planes / strides / cus 4-byte aligned (anything else returns KVZ_HIP_ERR_INVALID and writes
+ * nothing); stride_y and stride_c are independent (stride_c need not be stride_y / 2), rec_u and rec_v share
+ * stride_c; the bytes between width and stride are neither read nor written.  Bitdepth 8, lossless
  * and PCM blocks are not handled (kvz_filter_deblock_lcu asserts !lossless). */
 KVZ_HIP_API int kvz_hip_deblock_frame(kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v,
                                       uint32_t stride_c, int width, int height, const kvz_hip_cu_info *cus,

@@ -56,6 +56,51 @@ class DeviceBuffer:
             pass
 
 
+class PlaneView:
+    """A plane that is a rectangle inside a larger uint8 buffer, the way the C ABI takes planes (pointer, stride, size):
+    `buf` is the whole 2-D buffer and its row length the stride, the plane is buf[top:top + height, left:left + width], and the
+    pointer handed to the entry is buffer + top * stride + left.  Every wrapper below that takes a plane as a 2-D array takes a
+    PlaneView in its place; a plane the entry writes then comes back as the WHOLE buffer, so that the caller can look at the
+    bytes around the plane as well (crop() cuts the plane out again)."""
+
+    def __init__(self, buf, width, height, left=0, top=0):
+        self.buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        self.width, self.height, self.left, self.top = int(width), int(height), int(left), int(top)
+        assert self.buf.ndim == 2 and self.left >= 0 and self.top >= 0 and self.width >= 0 and self.height >= 0
+        assert self.left + self.width <= self.buf.shape[1] and self.top + self.height <= self.buf.shape[0]
+
+    @property
+    def stride(self):
+        return self.buf.shape[1]
+
+    @property
+    def offset(self):
+        return self.top * self.stride + self.left
+
+    def crop(self, buf=None):
+        b = self.buf if buf is None else buf
+        return b[self.top:self.top + self.height, self.left:self.left + self.width]
+
+
+class _Staged:
+    """one plane in device memory: .ptr is what the entry gets, .stride / .w / .h describe it, .shape is the buffer's"""
+
+    def __init__(self, plane):
+        if isinstance(plane, PlaneView):
+            host, off = plane.buf, plane.offset
+            self.stride, self.w, self.h = plane.stride, plane.width, plane.height
+        else:
+            host, off = np.ascontiguousarray(plane, dtype=np.uint8), 0
+            self.stride, self.w, self.h = host.shape[1], host.shape[1], host.shape[0]
+        self.shape = host.shape
+        self.buf = DeviceBuffer.from_numpy(host)
+        self.ptr = self.buf.ptr + off
+
+    def download(self):
+        """the whole buffer (= the plane when it was handed over as a compact array)"""
+        return self.buf.to_numpy(np.uint8, self.shape)
+
+
 def _pairs_array(pairs):
     """pairs: iterable of (x1, y1, x2, y2, w, h) -> contiguous BlockPair array as numpy int32 [n,6]"""
     a = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 6))
@@ -87,18 +132,16 @@ def cost_nxn_dual_batch(kind, n, preds, orig, pred_stride=1024, item_stride=2048
 
 
 def _pair_call(fname, plane1, plane2, pairs, clamp):
+    """plane1 / plane2: 2-D uint8 arrays (stride = width) or PlaneViews"""
     L = _lib.init()
-    plane1 = np.ascontiguousarray(plane1, dtype=np.uint8)
-    plane2 = np.ascontiguousarray(plane2, dtype=np.uint8)
     pa = _pairs_array(pairs)
     count = pa.shape[0]
-    a, b, d, o = (DeviceBuffer.from_numpy(plane1), DeviceBuffer.from_numpy(plane2), DeviceBuffer.from_numpy(pa),
-                  DeviceBuffer(4 * count))
+    a, b, d, o = _Staged(plane1), _Staged(plane2), DeviceBuffer.from_numpy(pa), DeviceBuffer(4 * count)
     f = getattr(L, fname)
     if clamp:
-        rc = f(a.ptr, plane1.shape[1], b.ptr, plane2.shape[1], plane2.shape[1], plane2.shape[0], d.ptr, count, o.ptr, None)
+        rc = f(a.ptr, a.stride, b.ptr, b.stride, b.w, b.h, d.ptr, count, o.ptr, None)
     else:
-        rc = f(a.ptr, plane1.shape[1], b.ptr, plane2.shape[1], d.ptr, count, o.ptr, None)
+        rc = f(a.ptr, a.stride, b.ptr, b.stride, d.ptr, count, o.ptr, None)
     check(rc, fname)
     return o.to_numpy(np.uint32, (count,))
 
@@ -121,15 +164,13 @@ def pixels_calc_ssd_batch(plane1, plane2, pairs):
 
 
 def satd_any_size_quad_batch(preds, orig, pairs, pred_stride=64, pred_item_stride=64 * 64):
-    """preds: uint8 [count*4, pred_item_stride]; orig: 2-D plane; pairs use (x1,y1,w,h)"""
+    """preds: uint8 [count*4, pred_item_stride]; orig: 2-D plane or PlaneView; pairs use (x1,y1,w,h)"""
     L = _lib.init()
     preds = np.ascontiguousarray(preds, dtype=np.uint8)
-    orig = np.ascontiguousarray(orig, dtype=np.uint8)
     pa = _pairs_array(pairs)
     count = pa.shape[0]
-    p, g, d, o = (DeviceBuffer.from_numpy(preds), DeviceBuffer.from_numpy(orig), DeviceBuffer.from_numpy(pa),
-                  DeviceBuffer(16 * count))
-    check(L.kvz_hip_satd_any_size_quad_batch(p.ptr, pred_stride, pred_item_stride, g.ptr, orig.shape[1], d.ptr, count,
+    p, g, d, o = DeviceBuffer.from_numpy(preds), _Staged(orig), DeviceBuffer.from_numpy(pa), DeviceBuffer(16 * count)
+    check(L.kvz_hip_satd_any_size_quad_batch(p.ptr, pred_stride, pred_item_stride, g.ptr, g.stride, d.ptr, count,
                                              o.ptr, None), "satd_any_size_quad batch")
     return o.to_numpy(np.uint32, (count, 4))
 
@@ -146,17 +187,14 @@ def bipred_blend_batch(w, h, hi0, s0, hi1, s1):
 
 
 def ctu_sad_grid_batch(pic, ref, ctus, mv_offsets):
-    """ctus: (x, y, mvx, mvy) rows; mv_offsets: (dx, dy) rows -> uint32 [n_ctu, n_mv, 85]"""
+    """pic, ref: 2-D planes or PlaneViews; ctus: (x, y, mvx, mvy) rows; mv_offsets: (dx, dy) rows -> uint32 [n_ctu, n_mv, 85]"""
     L = _lib.init()
-    pic = np.ascontiguousarray(pic, dtype=np.uint8)
-    ref = np.ascontiguousarray(ref, dtype=np.uint8)
     c = np.ascontiguousarray(np.asarray(ctus, dtype=np.int32).reshape(-1, 4))
     mv = np.ascontiguousarray(np.asarray(mv_offsets, dtype=np.int16).reshape(-1, 2))
     n, k = c.shape[0], mv.shape[0]
-    a, b, dc, dm, o = (DeviceBuffer.from_numpy(pic), DeviceBuffer.from_numpy(ref), DeviceBuffer.from_numpy(c),
-                       DeviceBuffer.from_numpy(mv), DeviceBuffer(4 * 85 * n * k))
-    check(L.kvz_hip_ctu_sad_grid_batch(a.ptr, pic.shape[1], pic.shape[1], pic.shape[0], b.ptr, ref.shape[1], ref.shape[1],
-                                       ref.shape[0], dc.ptr, n, dm.ptr, k, o.ptr, None), "ctu_sad_grid batch")
+    a, b, dc, dm, o = _Staged(pic), _Staged(ref), DeviceBuffer.from_numpy(c), DeviceBuffer.from_numpy(mv), DeviceBuffer(4 * 85 * n * k)
+    check(L.kvz_hip_ctu_sad_grid_batch(a.ptr, a.stride, a.w, a.h, b.ptr, b.stride, b.w, b.h, dc.ptr, n, dm.ptr, k, o.ptr, None),
+          "ctu_sad_grid batch")
     return o.to_numpy(np.uint32, (n, k, 85))
 
 
@@ -367,12 +405,11 @@ def inter_candidates_multi_batch(pictures, pus):
 
 # ---- motion search of whole PUs ----
 def search_pu_batch(pic, ref, pus, params, cabac=None, cost_to_beat=None):
-    """pus: structured array laid out as kvz_hip_me_pu (64 bytes each), params: one kvz_hip_me_params record (96 bytes).
+    """pic, ref: 2-D planes or PlaneViews; pus: structured array laid out as kvz_hip_me_pu (64 bytes each), params: one
+    kvz_hip_me_params record (96 bytes).
     cabac: kvz_hip_me_cabac snapshots (--mv-rdo); cost_to_beat: uint32 per PU (the best cost of the pictures searched before).
     Returns the raw results as int32 [count, 8] (= kvz_hip_me_result)."""
     L = _lib.init()
-    pic = np.ascontiguousarray(pic, dtype=np.uint8)
-    ref = np.ascontiguousarray(ref, dtype=np.uint8)
     pus = np.ascontiguousarray(pus)
     params = np.ascontiguousarray(params)
     assert pus.dtype.itemsize == 64 and params.nbytes == 96
@@ -388,32 +425,30 @@ def search_pu_batch(pic, ref, pus, params, cabac=None, cost_to_beat=None):
         params.view(np.uint8).reshape(-1)[80:88] = np.frombuffer(np.uint64(cb.ptr).tobytes(), dtype=np.uint8)
         if int(params.view(np.int32).reshape(-1)[19]) == 0:      # n_cabac: the number of snapshots handed over
             params.view(np.int32).reshape(-1)[19] = len(cabac)
-    a, b, d = DeviceBuffer.from_numpy(pic), DeviceBuffer.from_numpy(ref), DeviceBuffer.from_numpy(pus.view(np.uint8))
+    a, b, d = _Staged(pic), _Staged(ref), DeviceBuffer.from_numpy(pus.view(np.uint8))
     out = DeviceBuffer(max(1, 32 * count))
-    check(L.kvz_hip_search_pu_batch(a.ptr, pic.shape[1], pic.shape[1], pic.shape[0], b.ptr, ref.shape[1], ref.shape[1], ref.shape[0],
+    check(L.kvz_hip_search_pu_batch(a.ptr, a.stride, a.w, a.h, b.ptr, b.stride, b.w, b.h,
                                     d.ptr, count, params.ctypes.data, out.ptr, None), "search_pu batch")
     return out.to_numpy(np.int32, (count, 8))
 
 
 def search_pu_multi_batch(pics, refs, pus, params):
-    """kvz_hip_search_pu_multi_batch: pics / refs = lists of equally sized 2-D planes, pus carry their pair in pad >> 2.
-    Returns int32 [count, 8]."""
+    """kvz_hip_search_pu_multi_batch: pics / refs = lists of 2-D planes or PlaneViews of one size and one stride per list (the
+    base offsets of PlaneViews may differ), pus carry their pair in pad >> 2.  Returns int32 [count, 8]."""
     L = _lib.init()
-    pics = [np.ascontiguousarray(p, dtype=np.uint8) for p in pics]
-    refs = [np.ascontiguousarray(r, dtype=np.uint8) for r in refs]
-    assert len(pics) == len(refs) and all(p.shape == pics[0].shape for p in pics) and all(r.shape == refs[0].shape for r in refs)
+    dp, dr = [_Staged(p) for p in pics], [_Staged(r) for r in refs]
+    assert len(dp) == len(dr) and all((p.stride, p.w, p.h) == (dp[0].stride, dp[0].w, dp[0].h) for p in dp)
+    assert all((r.stride, r.w, r.h) == (dr[0].stride, dr[0].w, dr[0].h) for r in dr)
     pus = np.ascontiguousarray(pus)
     params = np.ascontiguousarray(params)
     assert pus.dtype.itemsize == 64 and params.nbytes == 96
     count = pus.shape[0]
-    dp, dr = [DeviceBuffer.from_numpy(p) for p in pics], [DeviceBuffer.from_numpy(r) for r in refs]
     tp = DeviceBuffer.from_numpy(np.array([b.ptr for b in dp], dtype=np.uint64))
     tr = DeviceBuffer.from_numpy(np.array([b.ptr for b in dr], dtype=np.uint64))
     d = DeviceBuffer.from_numpy(pus.view(np.uint8))
     out = DeviceBuffer(max(1, 32 * count))
-    h, w = pics[0].shape
-    rh, rw = refs[0].shape
-    check(L.kvz_hip_search_pu_multi_batch(tp.ptr, w, w, h, tr.ptr, rw, rw, rh, len(pics), d.ptr, count, params.ctypes.data, out.ptr, None),
+    check(L.kvz_hip_search_pu_multi_batch(tp.ptr, dp[0].stride, dp[0].w, dp[0].h, tr.ptr, dr[0].stride, dr[0].w, dr[0].h, len(dp), d.ptr, count,
+                                          params.ctypes.data, out.ptr, None),
           "search_pu multi batch")
     return out.to_numpy(np.int32, (count, 8))
 
@@ -465,53 +500,53 @@ def sao_band_ddistortion_batch(orig, rec, bw, bh, band_pos, bands):
     return o.to_numpy(np.int32, (count,))
 
 
-def sao_reconstruct_color_batch(plane, blocks, infos, color):
-    """plane uint8 2-D; blocks int32 [count, 5] (x, y, w, h, sao_index); infos int32 [n, 14]; returns the filtered plane
-    (pixels outside every block are copied from `plane`)"""
+def sao_reconstruct_color_batch(plane, blocks, infos, color, new_rec=None):
+    """plane: uint8 2-D plane or PlaneView (rec); blocks int32 [count, 5] (x, y, w, h, sao_index); infos int32 [n, 14];
+    new_rec: the initial destination, a 2-D array or PlaneView of the plane's size (default: a copy of `plane`, so pixels
+    outside every block read as the input's).  Returns the destination after the call (the whole buffer of a PlaneView)."""
     L = _lib.init()
-    plane = np.ascontiguousarray(plane, dtype=np.uint8)
     blocks = np.ascontiguousarray(blocks, dtype=np.int32).reshape(-1, 5)
     infos = np.ascontiguousarray(infos, dtype=np.int32).reshape(-1, 14)
-    a, d = DeviceBuffer.from_numpy(plane), DeviceBuffer.from_numpy(plane)
+    a, d = _Staged(plane), _Staged(plane if new_rec is None else new_rec)
+    assert (d.w, d.h) == (a.w, a.h)
     b, f = DeviceBuffer.from_numpy(blocks), DeviceBuffer.from_numpy(infos)
-    check(L.kvz_hip_sao_reconstruct_color_batch(a.ptr, plane.shape[1], plane.shape[1], plane.shape[0], d.ptr, plane.shape[1],
+    check(L.kvz_hip_sao_reconstruct_color_batch(a.ptr, a.stride, a.w, a.h, d.ptr, d.stride,
                                                 b.ptr, blocks.shape[0], f.ptr, infos.shape[0], color, None), "sao_reconstruct")
-    return d.to_numpy(np.uint8, plane.shape)
+    return d.download()
 
 
 def bipred_cost_batch(pic, ref0, ref1, cands):
-    """cands: iterable of (x, y, w, h, mv0x, mv0y, mv1x, mv1y) (quarter-pel vectors) -> uint32 [count] SATD costs"""
+    """pic, ref0, ref1: 2-D planes or PlaneViews (the references of one size, each with its own stride);
+    cands: iterable of (x, y, w, h, mv0x, mv0y, mv1x, mv1y) (quarter-pel vectors) -> uint32 [count] SATD costs"""
     L = _lib.init()
-    pic = np.ascontiguousarray(pic, dtype=np.uint8)
-    ref0 = np.ascontiguousarray(ref0, dtype=np.uint8)
-    ref1 = np.ascontiguousarray(ref1, dtype=np.uint8)
-    assert ref0.shape == ref1.shape
     rec = np.zeros(len(cands), dtype=np.dtype([("g", "<i4", (4,)), ("mv", "<i2", (4,))]))
     for i, c in enumerate(cands):
         rec[i]["g"] = c[:4]
         rec[i]["mv"] = c[4:8]
-    a, b, d, e = DeviceBuffer.from_numpy(pic), DeviceBuffer.from_numpy(ref0), DeviceBuffer.from_numpy(ref1), DeviceBuffer.from_numpy(rec.view(np.uint8))
+    a, b, d, e = _Staged(pic), _Staged(ref0), _Staged(ref1), DeviceBuffer.from_numpy(rec.view(np.uint8))
+    assert (b.w, b.h) == (d.w, d.h)
     out = DeviceBuffer(max(1, 4 * len(rec)))
-    check(L.kvz_hip_bipred_cost_batch(a.ptr, pic.shape[1], pic.shape[1], pic.shape[0], b.ptr, ref0.shape[1], d.ptr, ref1.shape[1],
-                                      ref0.shape[1], ref0.shape[0], e.ptr, len(rec), out.ptr, None), "bipred_cost batch")
+    check(L.kvz_hip_bipred_cost_batch(a.ptr, a.stride, a.w, a.h, b.ptr, b.stride, d.ptr, d.stride,
+                                      b.w, b.h, e.ptr, len(rec), out.ptr, None), "bipred_cost batch")
     return out.to_numpy(np.uint32, (len(rec),))
 
 
 # ---- deblocking ----
 def deblock_frame(y, u, v, cus, prm):
-    """y, u, v: uint8 planes (u, v None with prm['chroma'] == 0); cus: kvz_hip_cu_info records [h/4, w/4] (20 bytes each);
-    prm: one kvz_hip_deblock_params record (64 bytes).  Returns the filtered planes."""
+    """y, u, v: uint8 planes or PlaneViews (u, v None with prm['chroma'] == 0; u and v share one stride); cus: kvz_hip_cu_info
+    records [h/4, w/4] (20 bytes each); prm: one kvz_hip_deblock_params record (64 bytes).  Returns the filtered planes (the
+    whole buffer of a PlaneView)."""
     L = _lib.init()
-    y = np.ascontiguousarray(y, dtype=np.uint8)
     cus = np.ascontiguousarray(cus)
     prm = np.ascontiguousarray(prm)
     assert cus.dtype.itemsize == 20 and prm.nbytes == 64
-    dy, dc = DeviceBuffer.from_numpy(y), DeviceBuffer.from_numpy(cus.view(np.uint8))
-    du = DeviceBuffer.from_numpy(np.ascontiguousarray(u, dtype=np.uint8)) if u is not None else None
-    dv = DeviceBuffer.from_numpy(np.ascontiguousarray(v, dtype=np.uint8)) if v is not None else None
-    check(L.kvz_hip_deblock_frame(dy.ptr, y.shape[1], du.ptr if du else None, dv.ptr if dv else None, u.shape[1] if u is not None else 0,
-                                  y.shape[1], y.shape[0], dc.ptr, prm.ctypes.data, None), "deblock_frame")
-    return (dy.to_numpy(np.uint8, y.shape), du.to_numpy(np.uint8, u.shape) if du else None, dv.to_numpy(np.uint8, v.shape) if dv else None)
+    dy, dc = _Staged(y), DeviceBuffer.from_numpy(cus.view(np.uint8))
+    du = _Staged(u) if u is not None else None
+    dv = _Staged(v) if v is not None else None
+    assert du is None or dv is None or du.stride == dv.stride
+    check(L.kvz_hip_deblock_frame(dy.ptr, dy.stride, du.ptr if du else None, dv.ptr if dv else None, du.stride if du else 0,
+                                  dy.w, dy.h, dc.ptr, prm.ctypes.data, None), "deblock_frame")
+    return (dy.download(), du.download() if du else None, dv.download() if dv else None)
 
 
 # ---- motion compensation (inter recon) ----

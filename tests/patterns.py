@@ -772,3 +772,70 @@ def speed_test_inter_pairs(bw, bh, iterations, w=3840, h=2160):
     x2 = x1 + np.tile(mv[:, 0], iterations); y2 = y1 + np.tile(mv[:, 1], iterations)
     out = np.stack([x1, y1, x2, y2, np.full_like(x1, bw), np.full_like(x1, bh)], axis=1)
     return np.ascontiguousarray(out.astype(np.int32))
+
+
+# ---- plane layouts: a compact plane as a rectangle inside a larger, poisoned buffer (pointer + stride + size, as the C ABI takes planes) ----
+PLANE_LAYOUTS = ("A", "B", "C")
+
+
+def plane_layout(name, width, k=0):
+    """-> (stride, left, top) of layout `name` for a plane `width` bytes wide; k = 0, 1, 2.. gives strides that grow with k,
+    so that the planes of one call all get different ones.
+      A (padded): left 0, the stride is the width plus a multiple of 4 that is no multiple of 16; 4 rows above, so the base is
+                  16-byte aligned when the width is a multiple of 4;
+      B (offset): left 4, top 1, the stride a multiple of 4 but not of 16, chosen so that the base (stride + 4) is 4- but not
+                  16-byte aligned;
+      C (odd):    left 1, top 2, an odd stride: an odd base."""
+    left, top = {"A": (0, 4), "B": (4, 1), "C": (1, 2)}[name]
+    ok = {"A": lambda s: (s - width) % 4 == 0 and (s - width) % 16 != 0, "B": lambda s: s % 16 in (4, 8), "C": lambda s: s % 2 == 1}[name]
+    s = width + left + 3                                       # at least 4 bytes of poison to the right of every row
+    while True:
+        s += 1
+        if ok(s):
+            if k == 0:
+                return s, left, top
+            k -= 1
+
+
+class EmbeddedPlane:
+    """buf[top:top + height, left:left + width] is the plane, everything else poison"""
+
+    def __init__(self, buf, width, height, left, top):
+        self.buf, self.width, self.height, self.left, self.top = buf, width, height, left, top
+        self.stride = buf.shape[1]
+        self.offset = top * self.stride + left
+
+    def crop(self, buf=None):
+        b = self.buf if buf is None else buf
+        return b[self.top:self.top + self.height, self.left:self.left + self.width]
+
+    def poison_intact(self, buf):
+        """True when `buf` (the buffer after a call) still holds the poison everywhere outside the plane"""
+        m = np.ones(self.buf.shape, bool)
+        m[self.top:self.top + self.height, self.left:self.left + self.width] = False
+        return buf.shape == self.buf.shape and bool((buf[m] == self.buf[m]).all())
+
+
+def embed_plane(plane, stride, left, top, seed, bottom=2, span=None):
+    """The compact 2-D uint8 `plane` inside a buffer of rows `stride` bytes long: `top` rows of poison above it, `left` bytes before and
+    stride - left - width bytes after every row, at least `bottom` (>= 2) rows below.  span: the largest stride any plane of the same call
+    has -- the buffer gets as many more rows below as it takes for base + (height + 2) * span to lie inside it, so that a kernel that
+    walks this plane with another plane's stride, or reads a row's padding, reads poison and never leaves the allocation.
+    The poison comes from a random stream of its own (seed); the bytes that touch the plane are made to differ from the edge pixel
+    beside them, so that reading one instead of the replicated edge always changes a SAD."""
+    plane = np.ascontiguousarray(plane, dtype=np.uint8)
+    h, w = plane.shape
+    assert stride >= left + w and bottom >= 2
+    need = top * stride + left + (h + 2) * max(stride, span or 0)
+    rows = max(top + h + bottom, -(-need // stride))
+    g = np.random.default_rng([int(seed), 0x9015])
+    buf = g.integers(0, 256, (rows, stride), dtype=np.uint8)
+    buf[top:top + h, left:left + w] = plane
+    if left:
+        buf[top:top + h, left - 1] = plane[:, 0] ^ 0x80
+    if left + w < stride:
+        buf[top:top + h, left + w] = plane[:, -1] ^ 0x80
+    if top:
+        buf[top - 1, left:left + w] = plane[0] ^ 0x80
+    buf[top + h, left:left + w] = plane[-1] ^ 0x80
+    return EmbeddedPlane(buf, w, h, left, top)
