@@ -232,7 +232,8 @@ KVZ_HIP_API int kvz_hip_satd_nxn_dual_batch(int n, const kvz_hip_pixel *preds, s
  *   - nothing left of the pointer, right of the width (the bytes between width and stride), above the first or below
  *     the last row is read or written.
  * The exceptions document their rule at the entry and refuse what breaks it with KVZ_HIP_ERR_INVALID:
- * kvz_hip_deblock_frame and the CU-map entries built like it (4-byte aligned planes and strides).  The search service
+ * kvz_hip_deblock_frame, the CU-map entries built like it and the whole-picture SAO entries kvz_hip_sao_stats_frame /
+ * kvz_hip_sao_frame (4-byte aligned planes and strides).  The search service
  * owns its planes (width a multiple of 4, PU x a multiple of 4) and is not concerned.
  * tests/test_gpu_plane_layout.py holds each of these entries to this on padded, offset and odd layouts. */
 
@@ -792,6 +793,9 @@ KVZ_HIP_API int kvz_hip_sao_reconstruct_color_batch(const kvz_hip_pixel *rec, ui
                                                     const kvz_hip_sao_block *blocks, size_t count,
                                                     const kvz_hip_sao_info *infos, int n_infos, int color, kvz_hip_stream s);
 
+/* The whole-picture SAO entries, kvz_hip_sao_stats_frame and kvz_hip_sao_frame, take a kvz_hip_ref_picture and are declared
+ * with the picture chain below, after kvz_hip_inter_residual_frame. */
+
 /* ------------------------------------------------------------------ */
 /* deblocking of a reconstructed frame                                 */
 /*   reference: kvz_filter_deblock_lcu (filter.c:770-779) called for   */
@@ -957,6 +961,85 @@ KVZ_HIP_API int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz
                                              kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
                                              uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                                              const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* (2) SAO group, continued: sample adaptive offset of a whole picture */
+/*   reference: sao.c:164-337, :355-400, :580-644 with                 */
+/*   sao-generic.c:34-109 below them; SURVEY.md section 8(f) row 4     */
+/* ------------------------------------------------------------------ */
+/* ---- SAO of a whole picture: the stage after kvz_hip_deblock_frame.  Two asynchronous calls that take plane pointers,
+ * strides and per-LCU arrays in raster order over the ceil(width / 64) x ceil(height / 64) LCUs (n_lcu of them) and do no
+ * host work.  The mode and merge DECISION (sao_search_best_mode, sao.c:467-578, with its CABAC bit costs sao_mode_bits_*)
+ * stays with the host: the ddistortion of any candidate is cnt * o * o - 2 * o * sum over the statistics below
+ * (sao-generic.c:67-71, :171-178), so the host prices the searched classes, the band candidate and both merge neighbours
+ * from the tables without touching a pixel.
+ * Planes, for both entries: the rule of kvz_hip_deblock_frame -- planes and strides 4-byte aligned (anything else returns
+ * KVZ_HIP_ERR_INVALID and writes nothing), every stride independent and >= its width, the bytes between width and stride
+ * never read (nor written).  width / height multiples of 8, at least 8.  Bit depth 8. ---- */
+
+/* Statistics of one plane of one LCU.  The block is the LCU's part of the plane as sao_search_luma / sao_search_chroma
+ * (sao.c:580-644) blit it: 64 x 64 luma pixels clipped at the right and bottom picture edge to width - 64 * lcu_x by
+ * height - 64 * lcu_y, half that in each direction for chroma (the smallest block is 8 x 8 luma, 4 x 4 chroma). */
+typedef struct {
+  int32_t edge[4][2][5];   /* [eo_class][0 sum, 1 count][category]: calc_sao_edge_dir (sao-generic.c:82-109) on the block:
+                            * its interior 1 .. w-2 x 1 .. h-2 only, so no pixel of a neighbouring LCU is read */
+  int32_t band[2][32];     /* [0 sum, 1 count][band]: calc_sao_bands (sao.c:247-261), every pixel of the block */
+} kvz_hip_sao_lcu_stats;   /* 416 bytes */
+/* The bit-independent results of sao_search_edge_sao and calc_sao_band_offsets for one plane of one LCU, in the reference's
+ * integer arithmetic: offset = (sum + (cnt >> 1)) / cnt with C's truncating division, clipped to +-7 (SAO_ABS_OFFSET_MAX at
+ * bit depth 8), 0 for an empty category.  For chroma the host adds the U and V records (the reference sums over buf_cnt). */
+typedef struct {
+  int32_t edge_offsets[4][5];  /* per eo_class and category (sao.c:368-389): categories 1-2 keep positive, 3-4 negative
+                                * offsets only; [0] = 0 */
+  int32_t edge_ddist[4];       /* per eo_class: sum over categories 1..4 of cnt * o * o - 2 * o * sum (sao.c:397), WITHOUT
+                                * the mode bits */
+  int32_t band_offsets[4];     /* calc_sao_band_offsets (sao.c:188-240).  Its loop of :213-222 compares with a best_dist that
+                                * it never updates, so the offset it records for a band is the last one visited, +-1 with
+                                * the sign of the rounded mean: that is what this field holds */
+  int32_t band_position;       /* the first minimum over the start bands 0 .. 27 */
+  int32_t band_ddist;          /* its return value */
+} kvz_hip_sao_lcu_cand;      /* 120 bytes */
+/* Statistics and candidates of every LCU and plane of a picture, in one launch.
+ * src: HOST, copied at the call; the source picture (DEVICE planes, const), as kvz_hip_inter_residual_frame takes it; its
+ *   width / height are the picture's.  rec_y / rec_u / rec_v: the deblocked reconstruction (DEVICE, const).  chroma: 0 for
+ *   4:0:0 (the chroma pointers are unused), 1 for 4:2:0.
+ * stats (DEVICE, required) / cands (DEVICE, optional, may be NULL): one record per (plane, LCU) at index
+ *   color * n_lcu + lcu, color 0 Y, 1 U, 2 V; n_lcu records with chroma == 0, 3 * n_lcu otherwise.  Every field of every
+ *   record is written; nothing is accumulated into what was there.  Integer sums: no result depends on scheduling.
+ * WHAT THE STATISTICS ARE OF: the planes handed in.  The reference's live encoder calls kvz_sao_search_lcu on an LCU whose
+ *   right and bottom edges are not yet deblocked (encoderstate.c:639-647, filter.c:711-779); after a whole-picture
+ *   kvz_hip_deblock_frame this call sees other pixels there.  Like the three picture entries before it, this one is not wired
+ *   into a live encode: parity is defined against the reference's functions applied to blocks blitted from the same planes.
+ * Asynchronous on s; no host synchronisation, no allocation, no scratch memory; usable between kvz_hip_graph_begin / _end and
+ * replayable after the contents of the planes changed (the launch shape depends on width, height and chroma only).
+ * A NULL required pointer, a size that is not a multiple of 8 or below 8, a stride below the width or a misaligned plane or
+ * stride returns KVZ_HIP_ERR_INVALID and nothing is written. */
+KVZ_HIP_API int kvz_hip_sao_stats_frame(const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                        const kvz_hip_pixel *rec_u, const kvz_hip_pixel *rec_v, uint32_t stride_c, int chroma,
+                                        kvz_hip_sao_lcu_stats *stats, kvz_hip_sao_lcu_cand *cands, kvz_hip_stream s);
+/* kvz_sao_reconstruct (sao.c:278-337) for every LCU and plane of a picture, as encoder_sao_reconstruct
+ * (encoderstate.c:245-441) applies it, in one launch: dst <- SAO(rec).
+ * rec_*: the deblocked planes (DEVICE, const).  sao_luma[n_lcu], sao_chroma[n_lcu]: DEVICE, 4-byte aligned, in raster order
+ *   over the LCUs, as frame->sao_luma / sao_chroma hold them after kvz_sao_search_lcu -- a merged LCU carries its candidate's
+ *   parameters (sao.c:684-699).  chroma: 0 for 4:0:0 (chroma planes and sao_chroma unused), 1 for 4:2:0.
+ * Per pixel: filtered with the record of the LCU it lies in (x >> 6, y >> 6 luma; x >> 5, y >> 5 chroma); its neighbours
+ *   are read from the deblocked plane across LCU boundaries (what the reference keeps its *_before_sao buffers for).  An
+ *   edge-offset pixel whose neighbour a or b would lie outside the plane keeps its deblocked value -- per pixel, what the
+ *   row and column trimming of sao.c:297-324 amounts to.  Band offset (kvz_calc_sao_offset_array, sao.c:164-180) applies
+ *   everywhere; SAO_TYPE_NONE copies.  V uses band_position[1] and offsets[5..9]; Y and U use [0] and offsets[0..4].
+ * dst_*: receive every pixel of the width x height (chroma: width / 2 x height / 2) planes, filtered or copied: a complete
+ *   picture, the next frame's reference; the bytes between width and stride keep their contents.  Strides of their own.
+ *   Out of place only: dst_* == rec_* returns KVZ_HIP_ERR_INVALID, any other overlap is a caller error.
+ * Malformed records: a type other than 1 or 2, type 2 with an eo_class outside 0..3, or type 1 with the plane's
+ *   band_position outside 0..31 is treated as SAO_TYPE_NONE (a copy).  No record content makes an access leave the planes
+ *   or arrays.
+ * Asynchronous on s; no host synchronisation, no allocation, no scratch memory; usable between kvz_hip_graph_begin / _end and
+ * replayable after the contents of the planes and of the SAO arrays changed.  Errors as kvz_hip_sao_stats_frame. */
+KVZ_HIP_API int kvz_hip_sao_frame(const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
+                                  const kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_pixel *dst_y, uint32_t dst_stride_y,
+                                  kvz_hip_pixel *dst_u, kvz_hip_pixel *dst_v, uint32_t dst_stride_c, int width, int height,
+                                  const kvz_hip_sao_info *sao_luma, const kvz_hip_sao_info *sao_chroma, int chroma,
+                                  kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */

@@ -679,6 +679,67 @@ def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhid
             "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
 
 
+# ---- SAO of a whole picture ----
+SAO_LCU_STATS = np.dtype([("edge", "<i4", (4, 2, 5)), ("band", "<i4", (2, 32))])                # kvz_hip_sao_lcu_stats
+SAO_LCU_CAND = np.dtype([("edge_offsets", "<i4", (4, 5)), ("edge_ddist", "<i4", (4,)), ("band_offsets", "<i4", (4,)),
+                         ("band_position", "<i4"), ("band_ddist", "<i4")])                      # kvz_hip_sao_lcu_cand
+SAO_INFO = np.dtype([("type", "<i4"), ("eo_class", "<i4"), ("band_position", "<i4", (2,)), ("offsets", "<i4", (10,))])   # kvz_hip_sao_info
+
+
+def lcu_count(width, height):
+    return ((width + 63) // 64) * ((height + 63) // 64)
+
+
+def _stage_planes(planes, chroma):
+    st = [_Staged(p) for p in planes[:3 if chroma else 1]]
+    assert not chroma or (st[1].stride == st[2].stride and (st[1].w, st[1].h) == (st[2].w, st[2].h) == (st[0].w // 2, st[0].h // 2))
+    return st
+
+
+def sao_stats_frame(src, rec, chroma=1, with_cands=True):
+    """kvz_hip_sao_stats_frame.  src, rec: (y, u, v) uint8 planes or PlaneViews of the source and the deblocked picture (u, v None
+    for 4:0:0; u and v share one stride).  Returns (stats, cands): SAO_LCU_STATS / SAO_LCU_CAND records [planes, LCUs] (cands None
+    without with_cands)."""
+    L = _lib.init()
+    chroma = int(chroma)
+    s, r = _stage_planes(src, chroma), _stage_planes(rec, chroma)
+    w, h = s[0].w, s[0].h
+    assert (r[0].w, r[0].h) == (w, h)
+    table = ref_picture_table([(s[0].ptr, s[1].ptr if chroma else 0, s[2].ptr if chroma else 0, s[0].stride, s[1].stride if chroma else 0)], w, h)
+    n = (3 if chroma else 1) * lcu_count(w, h)
+    ds = DeviceBuffer(n * SAO_LCU_STATS.itemsize)
+    dc = DeviceBuffer(n * SAO_LCU_CAND.itemsize) if with_cands else None
+    check(L.kvz_hip_sao_stats_frame(table.ctypes.data, r[0].ptr, r[0].stride, r[1].ptr if chroma else None, r[2].ptr if chroma else None,
+                                    r[1].stride if chroma else 0, chroma, ds.ptr, dc.ptr if dc else None, None), "sao_stats_frame")
+    shape = (3 if chroma else 1, n // (3 if chroma else 1))
+    stats = ds.to_numpy(np.uint8, (n * SAO_LCU_STATS.itemsize,)).view(SAO_LCU_STATS).reshape(shape)
+    cands = dc.to_numpy(np.uint8, (n * SAO_LCU_CAND.itemsize,)).view(SAO_LCU_CAND).reshape(shape) if dc else None
+    return stats, cands
+
+
+def sao_frame(rec, sao_luma, sao_chroma=None, chroma=1, dst=None):
+    """kvz_hip_sao_frame.  rec: (y, u, v) uint8 planes or PlaneViews of the deblocked picture; sao_luma / sao_chroma: int32
+    [LCUs, 14] or SAO_INFO records in raster order; dst: the initial destination planes (arrays or PlaneViews of the picture's
+    size; default zeros).  Returns the destination (y, u, v) after the call (the whole buffer of a PlaneView)."""
+    L = _lib.init()
+    chroma = int(chroma)
+    r = _stage_planes(rec, chroma)
+    w, h = r[0].w, r[0].h
+    if dst is None:
+        dst = [np.zeros((h >> (1 if k else 0), w >> (1 if k else 0)), np.uint8) for k in range(3)]
+    d = _stage_planes(dst, chroma)
+    assert (d[0].w, d[0].h) == (w, h)
+    n = lcu_count(w, h)
+    infos = [np.ascontiguousarray(a).view(np.int32).reshape(n, 14) if a is not None and np.asarray(a).dtype == SAO_INFO
+             else (np.ascontiguousarray(a, dtype=np.int32).reshape(n, 14) if a is not None else None) for a in (sao_luma, sao_chroma)]
+    di = [DeviceBuffer.from_numpy(a) if a is not None else None for a in infos]
+    check(L.kvz_hip_sao_frame(r[0].ptr, r[0].stride, r[1].ptr if chroma else None, r[2].ptr if chroma else None, r[1].stride if chroma else 0,
+                              d[0].ptr, d[0].stride, d[1].ptr if chroma else None, d[2].ptr if chroma else None, d[1].stride if chroma else 0,
+                              w, h, di[0].ptr, di[1].ptr if di[1] else None, chroma, None), "sao_frame")
+    out = [p.download() for p in d]
+    return tuple(out + [None] * (3 - len(out)))
+
+
 # ---- tile halo exchange: batched rectangle copies on device pointers ----
 def copy_rects(rects, stream=None):
     """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most

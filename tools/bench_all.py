@@ -236,6 +236,8 @@ def main():
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k" for o in args.only.split(",")):
         inter_residual_rows(L, st, dev, max(args.rounds, 5))
+    if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p" for o in args.only.split(",")):
+        sao_frame_rows(L, st, dev, max(args.rounds, 5))
 
 
 def inter_recon_rows(L, st, dev, rounds, frames=64):
@@ -421,6 +423,115 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
         torch.cuda.synchronize()
         tc = [timed(L, st, lambda: _lib.check(chain(), "chain"), iters=5, warm=1) for _ in range(rounds)]
         print("%-28s %10s %12.1f %10s %8.4f %8s" % ("recon+residual+deblock_1080p", "-", 1e3 / float(np.median(tc)), "-", float(np.median(tc)), "-"))
+
+
+def sao_frame_rows(L, st, dev, rounds, iters=20):
+    """SAO of a whole 1080p 4:2:0 picture (kvz_hip_sao_stats_frame, kvz_hip_sao_frame) against the way the block-list entries offer:
+    statistics -- every LCU block of the three planes of source and reconstruction blitted contiguously with kvz_hip_copy_rects_batch
+    (16 rectangles per call), then kvz_hip_sao_edge_stats / edge_ddistortion / band_stats / band_ddistortion_batch per plane and block
+    shape (the last LCU row of 1080p is 56 high); reconstruction -- a copy of each plane and one kvz_hip_sao_reconstruct_color_batch per
+    plane over host-trimmed rectangles.  Old and new interleaved round by round in one process; median and min..max over the rounds.
+    Algorithmic bytes: statistics read source + reconstruction (3 per luma pixel), reconstruction reads and writes the picture (3)."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sao_frame_cases as SC
+    from patterns import sao_records
+    from kvazaar_amd import api
+    W, H = 1920, 1080
+    g = torch.Generator(device=dev); g.manual_seed(17)
+    src = [torch.randint(0, 256, (H >> c, W >> c), dtype=torch.uint8, device=dev, generator=g) for c in (0, 1, 1)]
+    rec = [(p.to(torch.int16) + torch.randint(-8, 9, p.shape, dtype=torch.int16, device=dev, generator=g)).clamp_(0, 255).to(torch.uint8) for p in src]
+    dst = [torch.empty_like(p) for p in rec]
+    n_lcu = api.lcu_count(W, H)
+    table = api.ref_picture_table([(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), W, W // 2)], W, H)
+    stats = torch.empty(3 * n_lcu * 104, dtype=torch.int32, device=dev)
+    cands = torch.empty(3 * n_lcu * 30, dtype=torch.int32, device=dev)
+    luma, chro = sao_records(n_lcu, 5), sao_records(n_lcu, 6)
+    luma_d, chro_d = torch.from_numpy(luma).to(dev), torch.from_numpy(chro).to(dev)
+
+    def new_stats():
+        return L.kvz_hip_sao_stats_frame(table.ctypes.data, rec[0].data_ptr(), W, rec[1].data_ptr(), rec[2].data_ptr(), W // 2, 1, stats.data_ptr(),
+                                         cands.data_ptr(), st)
+
+    def new_frame():
+        return L.kvz_hip_sao_frame(rec[0].data_ptr(), W, rec[1].data_ptr(), rec[2].data_ptr(), W // 2, dst[0].data_ptr(), W, dst[1].data_ptr(),
+                                   dst[2].data_ptr(), W // 2, W, H, luma_d.data_ptr(), chro_d.data_ptr(), 1, st)
+    # ---- the block-list way ----
+    blit, groups, keep = [], [], []
+    for color in range(3):
+        blocks = SC.lcu_blocks(W, H, color)
+        stride = W >> (1 if color else 0)
+        for shape in sorted({b[2:] for b in blocks}):
+            idx = [i for i, b in enumerate(blocks) if b[2:] == shape]
+            bw, bh = shape
+            o_d = torch.empty(len(idx) * bw * bh, dtype=torch.uint8, device=dev)
+            r_d = torch.empty_like(o_d)
+            for plane, out in ((src[color], o_d), (rec[color], r_d)):
+                for k, i in enumerate(idx):
+                    x, y = blocks[i][:2]
+                    blit.append((plane.data_ptr() + y * stride + x, out.data_ptr() + k * bw * bh, stride, bw, bw, bh))
+            out = [torch.empty(len(idx) * n, dtype=torch.int32, device=dev) for n in (40, 4, 64, 1)]
+            offs = torch.ones(len(idx) * 20, dtype=torch.int32, device=dev)
+            bpos = torch.zeros(len(idx), dtype=torch.int32, device=dev)
+            bands = torch.ones(len(idx) * 4, dtype=torch.int32, device=dev)
+            keep += [o_d, r_d, out, offs, bpos, bands]
+            groups.append((bw, bh, len(idx), o_d, r_d, out, offs, bpos, bands))
+    rects = (_lib.RectCopy * len(blit))(*[_lib.RectCopy(*b) for b in blit])
+    chunks = [(C.byref(rects, i * C.sizeof(_lib.RectCopy)), min(_lib.MAX_RECTS, len(blit) - i)) for i in range(0, len(blit), _lib.MAX_RECTS)]
+
+    def old_stats():
+        for ptr, n in chunks:
+            rc = L.kvz_hip_copy_rects_batch(ptr, n, st)
+            if rc:
+                return rc
+        for (bw, bh, n, o_d, r_d, out, offs, bpos, bands) in groups:
+            rc = (L.kvz_hip_sao_edge_stats_batch(o_d.data_ptr(), r_d.data_ptr(), bw, bh, n, out[0].data_ptr(), st) or
+                  L.kvz_hip_sao_edge_ddistortion_batch(o_d.data_ptr(), r_d.data_ptr(), bw, bh, n, offs.data_ptr(), out[1].data_ptr(), st) or
+                  L.kvz_hip_sao_band_stats_batch(o_d.data_ptr(), r_d.data_ptr(), bw, bh, n, out[2].data_ptr(), st) or
+                  L.kvz_hip_sao_band_ddistortion_batch(o_d.data_ptr(), r_d.data_ptr(), bw, bh, n, bpos.data_ptr(), bands.data_ptr(), out[3].data_ptr(), st))
+            if rc:
+                return rc
+        return 0
+    trimmed = []
+    for color in range(3):
+        infos = luma if color == 0 else chro
+        ph, pw = H >> (1 if color else 0), W >> (1 if color else 0)
+        r = []
+        for i, (x, y, bw, bh) in enumerate(SC.lcu_blocks(W, H, color)):
+            if infos[i][0] == 2:
+                x, y, bw, bh = SC.trim(x, y, bw, bh, int(infos[i][1]), pw, ph)
+            r.append((x, y, bw, bh, i))
+        trimmed.append(torch.from_numpy(np.array(r, dtype=np.int32)).to(dev))
+
+    def old_frame():
+        for color in range(3):
+            ph, pw = H >> (1 if color else 0), W >> (1 if color else 0)
+            rc = (L.kvz_hip_memcpy_d2d(dst[color].data_ptr(), rec[color].data_ptr(), pw * ph, st) or
+                  L.kvz_hip_sao_reconstruct_color_batch(rec[color].data_ptr(), pw, pw, ph, dst[color].data_ptr(), pw, trimmed[color].data_ptr(), n_lcu,
+                                                        (luma_d if color == 0 else chro_d).data_ptr(), n_lcu, color, st))
+            if rc:
+                return rc
+        return 0
+    torch.cuda.synchronize()
+    # what both ways compute is the same
+    _lib.check(new_frame(), "sao_frame")
+    _lib.check(L.kvz_hip_stream_sync(st), "sync")
+    want = [d.clone() for d in dst]
+    _lib.check(old_frame(), "block-list reconstruction")
+    _lib.check(L.kvz_hip_stream_sync(st), "sync")
+    assert all(torch.equal(a, b) for a, b in zip(want, dst)), "sao_frame differs from the block-list reconstruction"
+    t = {k: [] for k in ("new_stats", "old_stats", "new_frame", "old_frame")}
+    fns = {"new_stats": new_stats, "old_stats": old_stats, "new_frame": new_frame, "old_frame": old_frame}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            t[k].append(timed(L, st, lambda fn=fn, k=k: _lib.check(fn(), k), iters=iters, warm=3))
+    print("%-28s %10s %12s %10s %8s %16s %8s" % ("kernel", "launches", "frames/s", "GB/s", "ms", "min..max ms", "old/new"))
+    nbytes = 3.0 * W * H
+    for new, old, name, n_new, n_old in (("new_stats", "old_stats", "sao_stats_frame_1080p", 1, len(chunks) + 4 * len(groups)),
+                                         ("new_frame", "old_frame", "sao_frame_1080p", 1, 6)):
+        ms, ms_o = float(np.median(t[new])), float(np.median(t[old]))
+        print("%-28s %10d %12.1f %10.1f %8.4f %7.4f..%7.4f %8.2f" % (name, n_new, 1e3 / ms, nbytes / ms / 1e6, ms, min(t[new]), max(t[new]), ms_o / ms))
+        print("%-28s %10d %12.1f %10.1f %8.4f %7.4f..%7.4f %8s" % (name + "(blocks)", n_old, 1e3 / ms_o, nbytes / ms_o / 1e6, ms_o, min(t[old]), max(t[old]), "-"))
 
 
 if __name__ == "__main__":

@@ -136,6 +136,24 @@ def build_stages(L, dev):
     keep += [dby, dbu, dbv, dbc, dbp]
     stages["sao"].insert(0, ("deblock_frame", 1, lambda s: L.kvz_hip_deblock_frame(
         dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, W, DH, dbc.data_ptr(), dbp.ctypes.data, s)))
+    # SAO of the deblocked picture, the two whole-picture calls: statistics + candidates of every LCU and plane, then the
+    # reconstruction into the next frame's reference (records: every LCU an edge or band record, as after a decision)
+    from patterns import sao_records
+    n_lcu = api.lcu_count(W, DH)
+    so_src = [(p.to(torch.int16) + torch.randint(-6, 7, p.shape, dtype=torch.int16, device=dev, generator=g)).clamp_(0, 255).to(torch.uint8)
+              for p in (dby, dbu, dbv)]
+    so_tab = api.ref_picture_table([(so_src[0].data_ptr(), so_src[1].data_ptr(), so_src[2].data_ptr(), W, W // 2)], W, DH)
+    so_stats = torch.empty(3 * n_lcu * 104, dtype=torch.int32, device=dev)
+    so_cands = torch.empty(3 * n_lcu * 30, dtype=torch.int32, device=dev)
+    so_luma = torch.from_numpy(sao_records(n_lcu, 3)).to(dev)
+    so_chroma = torch.from_numpy(sao_records(n_lcu, 4)).to(dev)
+    so_dst = [torch.empty_like(p) for p in (dby, dbu, dbv)]
+    keep += [so_src, so_tab, so_stats, so_cands, so_luma, so_chroma, so_dst]
+    stages["sao"].insert(1, ("sao_stats_frame", 3 * n_lcu, lambda s: L.kvz_hip_sao_stats_frame(
+        so_tab.ctypes.data, dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, 1, so_stats.data_ptr(), so_cands.data_ptr(), s)))
+    stages["sao"].insert(2, ("sao_frame", 1, lambda s: L.kvz_hip_sao_frame(
+        dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, so_dst[0].data_ptr(), W, so_dst[1].data_ptr(), so_dst[2].data_ptr(), W // 2,
+        W, DH, so_luma.data_ptr(), so_chroma.data_ptr(), 1, s)))
     return stages, keep
 
 
