@@ -233,7 +233,8 @@ KVZ_HIP_API int kvz_hip_satd_nxn_dual_batch(int n, const kvz_hip_pixel *preds, s
  *     the last row is read or written.
  * The exceptions document their rule at the entry and refuse what breaks it with KVZ_HIP_ERR_INVALID:
  * kvz_hip_deblock_frame, the CU-map entries built like it and the whole-picture SAO entries kvz_hip_sao_stats_frame /
- * kvz_hip_sao_frame (4-byte aligned planes and strides).  The search service
+ * kvz_hip_sao_frame (4-byte aligned planes and strides).  kvz_hip_inter_residual_frame and kvz_hip_intra_recon_frame take
+ * the general rule.  The search service
  * owns its planes (width a multiple of 4, PU x a multiple of 4) and is not concerned.
  * tests/test_gpu_plane_layout.py holds each of these entries to this on padded, offset and odd layouts. */
 
@@ -938,7 +939,7 @@ typedef struct {
  *   an inter CU), no transform skip; bit-exact with the generic strategy at bit depth 8.  OUT OF SCOPE: lossless coding,
  *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID) and per-CU QP (the qp field of
  *   the records is not read).  Intra CUs need their neighbours' reconstruction and are not handled, as in
- *   kvz_hip_inter_recon_frame.
+ *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.
  * Outputs:
  *   rec planes: the reconstruction inside the inter CUs (a TU without coefficients keeps its prediction).
  *   coeff_y / coeff_u / coeff_v: DEVICE, 16-byte aligned, the layout of lcu->coeff: per LCU, in raster order of the
@@ -961,6 +962,59 @@ KVZ_HIP_API int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz
                                              kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
                                              uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                                              const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* prediction, residual coding and reconstruction of a picture's       */
+/* intra CUs                                                           */
+/*   reference: kvz_intra_recon_cu (intra.c:652-706): per leaf TU      */
+/*   intra_recon_tb_leaf (intra.c:590-638) and quantize_tr_residual    */
+/*   (transform.c:281-406)                                             */
+/* ------------------------------------------------------------------ */
+/* kvz_intra_recon_cu for every intra CU of a picture, in coding order, in one asynchronous call: after
+ * kvz_hip_inter_residual_frame and before kvz_hip_deblock_frame, on the same planes, the same CU array and the same coefficient
+ * arrays.  Inter CUs do not depend on intra CUs, so the inter part of the picture is complete before this call; an intra TU reads
+ * whatever the planes hold around it, as in the reference (there is no constrained intra prediction).
+ * Arguments, sizes, the coefficient layout and the error rules are those of kvz_hip_inter_residual_frame; params is the same struct
+ * (scaling_list must be 0, the qp field of the records is not read).  Planes: any base alignment and any strides >= the widths
+ * (PLANES above); cus 4-byte aligned, the coefficient arrays 16-byte aligned.
+ * intra_modes: DEVICE, required, two bytes per 4x4 SCU in the raster of cus: [2 i] = intra.mode, [2 i + 1] = intra.mode_chroma,
+ *   the actual mode 0..34 as cu_info_t holds it (not the syntax index).  A luma TU uses the luma byte of the SCU at its own
+ *   top-left -- which gives the four PUs of an NxN CU their own modes; part_size is not read.  A chroma TU uses the chroma byte
+ *   of the SCU at its luma top-left; with 4x4 luma TUs that is the first SCU of the 8x8 area (transform.c:293-300, intra.c:694).
+ *   A TU whose mode is above 34 is skipped: its pixels, coefficients and flags are unspecified, but no access leaves the planes.
+ * Which CUs: records of type CU_INTRA with depth 0..3 whose CU lies inside the picture (the rules of the inter entries with the
+ *   type swapped).  Everything that belongs to other records is left untouched: rec, coefficients, flags, costs.
+ * Transform tree: luma leaf depth min(4, max(depth, tr_depth, 1)), tr_depth read from the record at the TU's own top-left SCU;
+ *   prediction happens at the leaf TU size.  Chroma TUs are half as wide; with 4x4 luma TUs there is one 4x4 chroma TU per plane
+ *   per 8x8 area.
+ * Per TU, bit-exact with the generic strategy at bit depth 8: the reference pixels as kvz_hip_intra_build_reference_batch defines
+ *   them, taken from the rec plane of that colour (availability follows position alone); kvz_intra_predict with filter_boundary
+ *   for luma; kvz_quantize_residual, rdoq off, cu_is_intra = 1 (DST for 4x4 luma), under the scan of kvz_get_scan_order
+ *   (encoderstate.c:1384-1398: luma TUs 8 or 4 wide and chroma TUs 4 wide scan vertically for modes 6..14 and horizontally for
+ *   22..30), which matters through sign hiding.  No transform skip, no lossless mode.
+ * Outputs:
+ *   rec planes: the reconstruction inside the intra CUs (a TU without coefficients keeps its prediction); their contents on
+ *     entry are never used.
+ *   coeff_y / coeff_u / coeff_v: the LCU layout of kvz_hip_inter_residual_frame; zeros for a TU without coefficients.
+ *   cus[i].cbf_y of every SCU of an intra CU = has_coeffs of the covering luma leaf.
+ *   cbf_out (optional): the bytes of the intra CUs' SCUs are SET to bit 0 Y, bit 1 U, bit 2 V of the covering leaf TUs.  Bits are
+ *     set with atomic ORs on aligned dwords: if the array is not 4-byte aligned, up to 3 bytes in front of and behind it are
+ *     accessed too (OR with 0, their values do not change) and must be mapped; the same holds for kvz_hip_inter_residual_frame.
+ *   costs (optional): the record at each intra CU's top-left SCU receives ssd_*, coeff_abs_* and zero_ssd_* = the SSD of the
+ *     source against the intra prediction.
+ * Order: the LCUs are done in wavefronts t = lcu_x + 2 lcu_y, one launch per wavefront -- ceil(width / 64) + 2 (ceil(height / 64)
+ *   - 1) launches, whatever the map holds -- and Y, U, V side by side.  Asynchronous on s; no host synchronisation, no allocation
+ *   and no workspace: the call owns no device buffer (the kernel does spill a few registers per lane to the private memory that
+ *   the runtime provides to any kernel).  Usable between kvz_hip_graph_begin / _end, and a captured call may be replayed after the CONTENTS of
+ *   cus, intra_modes, the source and the planes changed.  A map whose records disagree inside a CU gives unspecified output
+ *   inside that CU, but the call completes and no access leaves the planes or arrays.
+ * A missing required pointer (intra_modes included), a misaligned cus / coeff array, a size that is not a multiple of 8, a stride
+ * below the width or scaling_list != 0 returns KVZ_HIP_ERR_INVALID and nothing is written. */
+KVZ_HIP_API int kvz_hip_intra_recon_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                          kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                          const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                          kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                          const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (2) SAO group, continued: sample adaptive offset of a whole picture */

@@ -648,6 +648,21 @@ def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhid
     cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
     (default zeros).  Returns a dict: rec (y, u, v), coeff (y, u, v) as [LCUs, 4096 / 1024] int16, cus (with cbf_y set), cbf_out
     uint8 [height / 4, width / 4], costs INTER_RESIDUAL_COST [height / 4, width / 4]."""
+    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs)
+
+
+def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None):
+    """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
+    intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
+    dict."""
+    cus = np.ascontiguousarray(cus)
+    modes = np.ascontiguousarray(modes, dtype=np.uint8)
+    assert modes.shape == cus.shape + (2,)
+    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs)
+
+
+def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs):
+    """the staging both residual stages share; modes None: the inter stage"""
     L = _lib.init()
     chroma = int(chroma)
     height, width = src[0].shape
@@ -667,10 +682,14 @@ def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhid
     cs = np.zeros(cus.shape, INTER_RESIDUAL_COST) if costs is None else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(cus.shape)
     dcb, dcs, dcu = DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(cs.view(np.uint8)), DeviceBuffer.from_numpy(cus.view(np.uint8))
     prm = inter_residual_params(qp, slice_is_intra, signhide, chroma)
-    check(L.kvz_hip_inter_residual_frame(table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None,
-                                         dr[2].ptr if chroma else None, r[1].shape[1] if chroma else 0, dcu.ptr, dco[0].ptr,
-                                         dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr,
-                                         prm.ctypes.data, None), "inter_residual frame")
+    planes = (table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
+              r[1].shape[1] if chroma else 0, dcu.ptr)
+    outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr, prm.ctypes.data, None)
+    if modes is None:
+        check(L.kvz_hip_inter_residual_frame(*planes, *outs), "inter_residual frame")
+    else:
+        dm = DeviceBuffer.from_numpy(modes)
+        check(L.kvz_hip_intra_recon_frame(*planes, dm.ptr, *outs), "intra_recon frame")
     pad = (None,) * (3 - n)
     return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
             "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,

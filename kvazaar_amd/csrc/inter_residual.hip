@@ -22,6 +22,7 @@
 #include "kvz_hip_internal.h"
 #include "transform_core.h"
 #include "quant_core.h"
+#include "lcu_layout.h"
 
 using namespace kvzhip;
 
@@ -41,18 +42,6 @@ struct resid_args {
   int cus_stride, lcus_x;
   int width, height;
 };
-
-// bits of a (4 bits) to the even positions
-__device__ __forceinline__ u32 spread4(u32 a) { a = (a | (a << 2)) & 0x33u; return (a | (a << 1)) & 0x55u; }
-// xy_to_zorder (cu.h:373-410) in units of 4x4 blocks: x, y = block coordinates inside the LCU
-__device__ __forceinline__ u32 zorder_blk(u32 x, u32 y) { return spread4(x) | (spread4(y) << 1); }
-
-// cbf_out is a byte array that several TUs of different planes set bits of: OR into the dword that holds the byte
-__device__ __forceinline__ void or_byte(u8 *base, size_t i, u32 bits)
-{
-  const uintptr_t p = (uintptr_t)(base + i);
-  atomicOr((u32 *)(p & ~(uintptr_t)3), bits << (8 * (p & 3)));
-}
 
 // the inter CU that holds the luma position (x, y), from the record of that position alone: false for another type, a
 // depth beyond 3 or a CU that would leave the picture (the rule of kvz_hip_inter_recon_frame)
@@ -83,12 +72,6 @@ __global__ __launch_bounds__(256) void inter_residual_init_kernel(resid_args a, 
     for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
   }
 }
-
-template <int N>
-__device__ __forceinline__ void load_row(const u8 *p, u32 (&w)[N / 4]) { __builtin_memcpy(w, p, N); }
-template <int N>
-__device__ __forceinline__ void store_row(u8 *p, const u32 (&w)[N / 4]) { __builtin_memcpy(p, w, N); }
-__device__ __forceinline__ int byte_of(const u32 *w, int x) { return (int)((w[x >> 2] >> (8 * (x & 3))) & 255u); }
 
 // Slots: [0, n_y) the N-aligned positions of Y, nx_y per row; then n_c of U and n_c of V, nx_c per row (n_c = 0 for
 // 4:0:0 and for N = 32).  A chroma slot (tx, ty) lies at the luma position (2 N tx, 2 N ty).

@@ -238,6 +238,40 @@ def main():
         inter_residual_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p" for o in args.only.split(",")):
         sao_frame_rows(L, st, dev, max(args.rounds, 5))
+    if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all" for o in args.only.split(",")):
+        intra_recon_rows(L, st, dev, max(args.rounds, 5))
+
+
+def intra_recon_rows(L, st, dev, rounds, iters=3):
+    """Intra prediction + residual coding of whole 1080p 4:2:0 pictures in coding order (kvz_hip_intra_recon_frame): a random quadtree
+    with about 10 % of its CUs intra (the rest inter: their LCU-workgroups leave after reading the map) and an all-intra one, modes
+    and tr_depth as tests/intra_recon_cases.py sets them.  The stage is a chain of dependent launches (one per wavefront of LCUs) and
+    of dependent TUs inside an LCU, so the figure is a latency, not a throughput: ms per picture, medians over the rounds."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import intra_recon_cases as XC
+    from kvazaar_amd import api
+    W, H = 1920, 1080
+    print("%-32s %10s %10s %12s %10s" % ("kernel", "intra %", "TUs", "frames/s", "ms"))
+    for name, share in (("intra_recon_frame_1080p_mixed", 0.1), ("intra_recon_frame_1080p_all", 1.0)):
+        cus, _, modes = XC.make_map(W, H, 51, intra_share=share, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+        src, rec = XC.make_planes(cus, 52)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+        src_d, rec_d, cus_d, modes_d = [up(p) for p in src], [up(p) for p in rec], up(cus), up(modes)
+        shapes = api.coeff_shapes(W, H)
+        co_d = [torch.empty(shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+        cbf_d = torch.empty(cus.shape, dtype=torch.uint8, device=dev)
+        cost_d = torch.empty(cus.shape + (6,), dtype=torch.int32, device=dev)
+        table = api.ref_picture_table([(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2)], W, H)
+        prm = api.inter_residual_params(32, 0, 1, 1)
+
+        def frame():                                     # in place and independent of what the intra CUs hold: no fresh copy needed
+            return L.kvz_hip_intra_recon_frame(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
+                                               cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
+                                               cbf_d.data_ptr(), cost_d.data_ptr(), prm.ctypes.data, st)
+        ms = sorted(timed(L, st, lambda: _lib.check(frame(), name), iters=iters, warm=1) for _ in range(rounds))[rounds // 2]
+        m, _, _ = XC.intra_mask(cus, W, H)
+        print("%-32s %10.1f %10d %12.1f %10.3f" % (name, 100 * m.mean(), len(XC.walk_tus(cus, modes, W, H)), 1e3 / ms, ms))
 
 
 def inter_recon_rows(L, st, dev, rounds, frames=64):

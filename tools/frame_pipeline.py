@@ -96,6 +96,21 @@ def build_stages(L, dev):
     stages["tu"].append(("inter_recon_frame", 1, lambda s: L.kvz_hip_inter_recon_frame(
         rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data,
         rc_prm.ctypes.data, s)))
+    # the intra CUs of a picture (a tenth of it; tr_depth and modes as tests/intra_recon_cases.py sets them), in coding order on a map
+    # and planes of its own: an init launch and one launch per wavefront of LCUs, 63 kernel launches at 1080p for the one call
+    import intra_recon_cases as XC
+    ir_cus, _, ir_modes = XC.make_map(W, H, 33, intra_share=0.1, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+    ir_src_h, ir_rec_h = XC.make_planes(ir_cus, 34)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+    ir_src, ir_rec, ir_cus_d, ir_modes_d = [up(p) for p in ir_src_h], [up(p) for p in ir_rec_h], up(ir_cus), up(ir_modes)
+    ir_shapes = api.coeff_shapes(W, H)
+    ir_co = [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+    ir_tab = api.ref_picture_table([(ir_src[0].data_ptr(), ir_src[1].data_ptr(), ir_src[2].data_ptr(), W, W // 2)], W, H)
+    ir_prm = api.inter_residual_params(27, 0, 0, 1)
+    keep += [ir_src, ir_rec, ir_cus_d, ir_modes_d, ir_co, ir_tab, ir_prm]
+    stages["tu"].append(("intra_recon_frame", 1, lambda s: L.kvz_hip_intra_recon_frame(
+        ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+        ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), None, None, ir_prm.ctypes.data, s)))
 
     qp = QuantParams(); qp.qp = 27
     keep.append(qp)
@@ -236,7 +251,8 @@ def main():
             L.kvz_hip_event_destroy(e0); L.kvz_hip_event_destroy(e1)
             total += ms.value / 20
             print("%-34s %9d %10.1f" % (name, units, ms.value / 20 * 1e3))
-    print("%-34s %9s %10.1f   (%d launches)" % ("sum of the entries", "", total * 1e3, n_launch))
+    print("%-34s %9s %10.1f   (%d calls; intra_recon_frame is %d kernel launches of its own)" % ("sum of the entries", "", total * 1e3, n_launch,
+                                                                                               1 + (W + 63) // 64 + 2 * ((H + 63) // 64 - 1)))
 
     results = {}
     results["eager"] = run(L, s, args.frames, lambda: enqueue_serial(stages, s))
