@@ -938,7 +938,7 @@ typedef struct {
  * Per TU: kvz_quantize_residual, rdoq off (quant-generic.c:180-273), cu_is_intra = 0, diagonal scan (kvz_get_scan_order of
  *   an inter CU), no transform skip; bit-exact with the generic strategy at bit depth 8.  OUT OF SCOPE: lossless coding,
  *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID) and per-CU QP (the qp field of
- *   the records is not read).  Intra CUs need their neighbours' reconstruction and are not handled, as in
+ *   the records is not read; a QP per LCU: kvz_hip_inter_residual_frame_qp below).  Intra CUs need their neighbours' reconstruction and are not handled, as in
  *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.
  * Outputs:
  *   rec planes: the reconstruction inside the inter CUs (a TU without coefficients keeps its prediction).
@@ -1015,6 +1015,77 @@ KVZ_HIP_API int kvz_hip_intra_recon_frame(const kvz_hip_ref_picture *src, kvz_hi
                                           const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
                                           kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                                           const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* a QP per LCU in the picture chain                                   */
+/*   reference: kvz_set_lcu_lambda_and_qp (rate_control.c:278-340,     */
+/*   called at encoderstate.c:619) sets state->qp per LCU under a      */
+/*   bitrate target or a ROI map; cur_cu->qp = state->qp               */
+/*   (search.c:451); set_cu_qps (encoderstate.c:550-609)               */
+/* ------------------------------------------------------------------ */
+/* kvz_hip_inter_residual_frame and kvz_hip_intra_recon_frame with one more argument, for pictures whose QP changes from LCU to LCU
+ * (rate control, --roi).  The rate-control model stays with the host and supplies the array.
+ * lcu_qp: DEVICE, one int8_t per LCU in raster order over the ceil(width / 64) x ceil(height / 64) LCUs (the convention of the SAO
+ *   arrays), any alignment: state->qp of each LCU.  A value outside 0..51 is clamped into 0..51 (the reference never produces one,
+ *   CLIP_TO_QP), so no value makes an access leave a table.
+ * Every TU is quantised and dequantised with the QP of the LCU it lies in: luma with that QP, chroma with its image under
+ *   kvz_get_scaled_qp (transform.c:129-143).  Everything that depends on the QP follows it per LCU: q_bits, add and the quant factor,
+ *   and the dequant scale, shift and add (quant-generic.c:40-50, :283-320), derived on the device by the function the host uses for
+ *   the one-QP entries.  params->qp is ignored when lcu_qp is given.  lcu_qp == NULL: params->qp everywhere, byte for byte the old
+ *   entry (it launches the old entry's kernels; kvz_hip_intra_recon_frame_qp calls the old entry, which then names itself in
+ *   kvz_hip_last_error).
+ * In every other respect -- planes and their alignment rules, the CU and transform tree rules, the coefficient layout, outputs,
+ *   error returns, capture -- they are the entries above.  They do NOT write cus[].qp: kvz_hip_cu_qp_frame below writes it.  A
+ *   captured call may be replayed after the contents of lcu_qp changed. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame_qp(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                                kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
+                                                uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
+                                                const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frame_qp(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                             kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                             const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                             kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                             const int8_t *lcu_qp, const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+typedef struct {
+  int32_t start_qp;    /* state->frame->QP: last_qp at the start of every chain (encoderstate.c:729), 0..51 */
+  int32_t chain_lcus;  /* LCUs per chain, in raster order: 0 = the whole picture is one chain (one slice, one tile, no WPP);
+                          ceil(width / 64) = every LCU row is a chain of its own (WPP: each row is a leaf state) */
+} kvz_hip_cu_qp_params; /* 8 bytes */
+/* set_cu_qps (encoderstate.c:550-609) for every LCU of a picture with max_qp_delta_depth == 0 -- the quantization group is the LCU;
+ * zero is the only non-negative value the reference sets (encoder.c:381): the QP map that kvz_hip_deblock_frame reads with
+ * per_cu_qp = 1 (get_qp_y_pred, filter.c:263-282), and per LCU the QP predictor that the entropy coder codes cu_qp_delta against
+ * (encode_coding_tree.c:511-529).  The chain for such a picture: prediction -> kvz_hip_inter_residual_frame_qp ->
+ * kvz_hip_intra_recon_frame_qp -> kvz_hip_cu_qp_frame -> kvz_hip_deblock_frame (per_cu_qp = 1) -> SAO.
+ * cus: DEVICE, the picture's records, 4-byte aligned; depth is read, qp is WRITTEN, type is not read.  cbf: DEVICE, the cbf_out array
+ *   of the residual entries, one byte per SCU (bits 0..2), any alignment; the caller clears it once before the residual entries, so
+ *   SCUs that neither entry covered stay 0.  width / height: multiples of 8, at least 8.  lcu_qp: as above (clamped into 0..51).
+ *   lcu_last_qp: DEVICE, required, one int8_t per LCU, WRITTEN.  params: HOST, copied at the call.
+ * The CUs of an LCU are the leaves of the walk of encoderstate.c:553-570: a node splits while the record at its top-left has a depth
+ *   greater than the node's (a depth above 3 counts as 3); nodes at or beyond the right or bottom edge of the picture are left out.
+ *   A CU is CODED iff any of its SCUs (inside the picture) has a non-zero cbf byte -- for a map whose records agree inside a CU this
+ *   is cbf_found of encoderstate.c:572-588.
+ * Per LCU, with `last` = start_qp at the first LCU of a chain and otherwise what the previous LCU of the chain leaves, and the CUs in
+ *   coding order (z-order): every SCU of a CU before the first coded CU gets qp = last; the first coded CU and every CU after it get
+ *   the LCU's QP; the LCU leaves last = its own QP if it has a coded CU and last unchanged otherwise.
+ *   Derivation.  With max_qp_delta_depth == 0, prev_qp is reset at depth 0 only, i.e. once per LCU; cbf_found = prev_qp >= 0 holds
+ *   from the first coded CU on, and those CUs keep cu->qp, which is state->qp of their LCU (search.c:451).  A CU before it gets
+ *   kvz_get_cu_ref_qp (encoderstate.c:1408-1430): the group is 64 wide, its corner is the LCU's, x_qg % 64 == y_qg % 64 == 0, both
+ *   predictors are last_qp and (2 last_qp + 1) >> 1 = last_qp.  *last_qp = cu->qp runs where is_last_cu_in_qg (encoderstate.h:332-342)
+ *   holds and reads the qp just written: the LCU's QP once a coded CU was seen, last_qp itself before.  At a ragged edge the
+ *   condition can hold for more than one CU of the LCU (right >= width or bottom >= height); a store before the first coded CU
+ *   leaves last_qp as it is, a store after it writes the LCU's QP, which no later CU of the LCU reads (they are all past the first
+ *   coded CU) and which the last such store writes again.  So the rule above is the reference's also at ragged edges.
+ * Outputs: cus[i].qp of every SCU inside the picture; lcu_last_qp[lcu] = `last` on entry to that LCU.  (Between its launches the
+ *   entry keeps its per-LCU intermediate in lcu_last_qp, so it owns no buffer.)
+ * Asynchronous on s; no allocation, no host synchronisation, no atomics; three launches whose shapes depend on width, height and
+ * chain_lcus only.  Usable between kvz_hip_graph_begin / _end, and a captured call may be replayed after the contents of the
+ * arrays changed.  OUT OF SCOPE: tiles (a chain is a raster run of the picture) and max_qp_delta_depth > 0.
+ * A NULL pointer, a misaligned cus, a size that is not a multiple of 8 or below 8, start_qp outside 0..51, a negative chain_lcus or
+ * one that is neither 0 nor a multiple of ceil(width / 64) returns KVZ_HIP_ERR_INVALID and nothing is written. */
+KVZ_HIP_API int kvz_hip_cu_qp_frame(kvz_hip_cu_info *cus, const uint8_t *cbf, int width, int height, const int8_t *lcu_qp,
+                                    int8_t *lcu_last_qp, const kvz_hip_cu_qp_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (2) SAO group, continued: sample adaptive offset of a whole picture */

@@ -137,6 +137,9 @@ SIGNATURES = {
     "kvz_hip_inter_recon_frame": (_I, [_P, _U, _P, _P, _U, _I, _I, _P, _P, _P, _P]),
     "kvz_hip_inter_residual_frame": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P]),
     "kvz_hip_intra_recon_frame": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kvz_hip_inter_residual_frame_qp": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kvz_hip_intra_recon_frame_qp": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kvz_hip_cu_qp_frame": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "kvz_hip_sao_stats_frame": (_I, [_P, _P, _U, _P, _P, _U, _I, _P, _P, _P]),
     "kvz_hip_sao_frame": (_I, [_P, _U, _P, _P, _U, _P, _U, _P, _P, _U, _I, _I, _P, _P, _I, _P]),
     "kvz_hip_set_registrar": (None, [_P]),

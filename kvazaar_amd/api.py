@@ -642,27 +642,28 @@ def coeff_shapes(width, height):
     return (n, 4096), (n, 1024)
 
 
-def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None):
+def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None):
     """kvz_hip_inter_residual_frame.  src: (y, u, v) uint8 planes of the source picture (its luma shape is the picture size;
     u, v None for 4:0:0); pred: (y, u, v) planes holding the prediction, at least as large (a wider array gives a stride);
     cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
     (default zeros).  Returns a dict: rec (y, u, v), coeff (y, u, v) as [LCUs, 4096 / 1024] int16, cus (with cbf_y set), cbf_out
-    uint8 [height / 4, width / 4], costs INTER_RESIDUAL_COST [height / 4, width / 4]."""
-    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs)
+    uint8 [height / 4, width / 4], costs INTER_RESIDUAL_COST [height / 4, width / 4].
+    lcu_qp: int8 [LCUs] in raster order -> kvz_hip_inter_residual_frame_qp: every TU takes the QP of its LCU and qp is ignored."""
+    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp)
 
 
-def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None):
+def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None):
     """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
     intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
-    dict."""
+    dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp."""
     cus = np.ascontiguousarray(cus)
     modes = np.ascontiguousarray(modes, dtype=np.uint8)
     assert modes.shape == cus.shape + (2,)
-    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs)
+    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp)
 
 
-def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs):
-    """the staging both residual stages share; modes None: the inter stage"""
+def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None):
+    """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries"""
     L = _lib.init()
     chroma = int(chroma)
     height, width = src[0].shape
@@ -684,18 +685,47 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
     prm = inter_residual_params(qp, slice_is_intra, signhide, chroma)
     planes = (table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
               r[1].shape[1] if chroma else 0, dcu.ptr)
-    outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr, prm.ctypes.data, None)
+    outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr)
+    tail = (prm.ctypes.data, None)
+    if lcu_qp is not None:
+        lq = np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(lcu_count(width, height))
+        dq = DeviceBuffer.from_numpy(lq)
+        tail = (dq.ptr,) + tail
     if modes is None:
-        check(L.kvz_hip_inter_residual_frame(*planes, *outs), "inter_residual frame")
+        entry = L.kvz_hip_inter_residual_frame if lcu_qp is None else L.kvz_hip_inter_residual_frame_qp
+        check(entry(*planes, *outs, *tail), "inter_residual frame")
     else:
         dm = DeviceBuffer.from_numpy(modes)
-        check(L.kvz_hip_intra_recon_frame(*planes, dm.ptr, *outs), "intra_recon frame")
+        entry = L.kvz_hip_intra_recon_frame if lcu_qp is None else L.kvz_hip_intra_recon_frame_qp
+        check(entry(*planes, dm.ptr, *outs, *tail), "intra_recon frame")
     pad = (None,) * (3 - n)
     return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
             "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
             "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
             "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
             "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+
+
+# ---- the QP map of a picture whose QP changes per LCU ----
+CU_QP_PARAMS = np.dtype([("start_qp", "<i4"), ("chain_lcus", "<i4")])                            # kvz_hip_cu_qp_params
+
+
+def cu_qp_frame(cus, cbf, lcu_qp, start_qp, chain_lcus=0):
+    """kvz_hip_cu_qp_frame.  cus: kvz_hip_cu_info records [height / 4, width / 4]; cbf: the cbf_out array of the residual stages,
+    uint8 of the same shape; lcu_qp: int8 [LCUs] in raster order; start_qp: the picture's QP; chain_lcus: 0 = one chain, LCUs per
+    row = a chain per LCU row.  Returns (cus with qp written, lcu_last_qp int8 [LCUs]: the QP predictor on entry to each LCU)."""
+    L = _lib.init()
+    cus = np.ascontiguousarray(cus)
+    assert cus.dtype.itemsize == 20 and cus.ndim == 2
+    height, width = 4 * cus.shape[0], 4 * cus.shape[1]
+    cb = np.ascontiguousarray(cbf, dtype=np.uint8).reshape(cus.shape)
+    n = lcu_count(width, height)
+    lq = np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(n)
+    prm = np.zeros(1, dtype=CU_QP_PARAMS)
+    prm["start_qp"], prm["chain_lcus"] = start_qp, chain_lcus
+    dcu, dcb, dq, dl = DeviceBuffer.from_numpy(cus.view(np.uint8)), DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(lq), DeviceBuffer(n)
+    check(L.kvz_hip_cu_qp_frame(dcu.ptr, dcb.ptr, width, height, dq.ptr, dl.ptr, prm.ctypes.data, None), "cu_qp frame")
+    return dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape), dl.to_numpy(np.int8, (n,))
 
 
 # ---- SAO of a whole picture ----

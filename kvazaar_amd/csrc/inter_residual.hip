@@ -73,12 +73,20 @@ __global__ __launch_bounds__(256) void inter_residual_init_kernel(resid_args a, 
   }
 }
 
+// A QP per LCU (kvz_hip_inter_residual_frame_qp): the array and what else the constants depend on.  Every TU derives its own set
+// from the QP of the LCU it lies in, with the function the host uses (flat_consts, quant_core.h) -- a workgroup holds 256 / N
+// neighbouring slots of one row, up to four LCUs for N = 4, so the constants are per TU group, not per workgroup.  The kernel takes
+// it as an optional trailing argument: without it (one QP per call) the instantiation is the kernel as it was, argument for argument.
+struct lcu_qp_source { const int8_t *lcu_qp; int slice_is_intra, signhide; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { return q; }
+
 // Slots: [0, n_y) the N-aligned positions of Y, nx_y per row; then n_c of U and n_c of V, nx_c per row (n_c = 0 for
 // 4:0:0 and for N = 32).  A chroma slot (tx, ty) lies at the luma position (2 N tx, 2 N ty).
-template <int N>
+template <int N, typename... PER_LCU>
 __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, quant_consts ky, quant_consts kc,
-                                                                int nx_y, int n_y, int nx_c, int n_c)
+                                                                int nx_y, int n_y, int nx_c, int n_c, PER_LCU... per_lcu)
 {
+  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0;
   constexpr int TPB = 256 / N, W4 = N / 4;
   constexpr int LD = lds_tile_ld(N);
   __shared__ __attribute__((aligned(16))) i16 sa[TPB * N * LD];     // residual / coefficients
@@ -109,6 +117,13 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
 
   quant_consts k = plane ? kc : ky;
   k.qtable = nullptr; k.dqtable = nullptr; k.dq_mode = 0;                  // flat lists only
+  if constexpr (LCU_QP) {
+    constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
+    // ky and kc are not used.  A slot that is no TU runs the barriers with the constants of QP 0 and reads nothing
+    const lcu_qp_source &q = only(per_lcu...);
+    const int qp = valid ? clip_lcu_qp(q.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)]) : 0;
+    k = flat_consts(qp, LOG2, plane, q.slice_is_intra, q.signhide);
+  }
   const int sh = plane ? 1 : 0, px = lx >> sh, py = ly >> sh;
   const u8 *src_row = (plane == 0 ? a.src_y : (plane == 1 ? a.src_u : a.src_v)) + (size_t)(py + row) * (plane ? a.src_stride_c : a.src_stride_y) + px;
   u8 *rec_row = (plane == 0 ? a.rec_y : (plane == 1 ? a.rec_u : a.rec_v)) + (size_t)(py + row) * (plane ? a.rec_stride_c : a.rec_stride_y) + px;
@@ -222,40 +237,45 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
   }
 }
 
-template <int N>
-void launch_size(const resid_args &a, const quant_consts &ky, const quant_consts &kc, int chroma, hipStream_t st)
+template <int N, typename... PER_LCU>
+void launch_size(const resid_args &a, const quant_consts &ky, const quant_consts &kc, int chroma, hipStream_t st, PER_LCU... q)
 {
   const int nx_y = (a.width + N - 1) / N, n_y = nx_y * ((a.height + N - 1) / N);
   const int cw = a.width >> 1, chh = a.height >> 1;
   const int nx_c = (cw + N - 1) / N, n_c = (chroma && N < 32) ? nx_c * ((chh + N - 1) / N) : 0;
   constexpr int TPB = 256 / N;
   const int slots = n_y + 2 * n_c;
-  hipLaunchKernelGGL(inter_residual_tu_kernel<N>, dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(256), 0, st, a, ky, kc, nx_y, n_y, nx_c, n_c);
+  hipLaunchKernelGGL((inter_residual_tu_kernel<N, PER_LCU...>), dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(256), 0, st, a, ky, kc, nx_y, n_y, nx_c, n_c, q...);
 }
 
-}  // namespace
-
-extern "C" {
-
-int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
-                                 kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y,
-                                 kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
-                                 const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
+template <typename... PER_LCU>
+void launch_width(int n, const resid_args &a, const quant_consts &ky, const quant_consts &kc, int chroma, hipStream_t st, PER_LCU... q)
 {
-  KVZ_CHECK_CTX();
+  if (n == 32) launch_size<32>(a, ky, kc, chroma, st, q...);
+  else if (n == 16) launch_size<16>(a, ky, kc, chroma, st, q...);
+  else if (n == 8) launch_size<8>(a, ky, kc, chroma, st, q...);
+  else launch_size<4>(a, ky, kc, chroma, st, q...);
+}
+
+// both entries: lcu_qp == nullptr is one QP per call (params->qp)
+int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                   kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                   kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
+                   const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
+{
   if (!src || !params || !rec_y || !cus || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
-    return kvzhip::invalid_arg(__func__);
+    return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
   if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
       params->scaling_list != 0)
-    return kvzhip::invalid_arg(__func__);
+    return kvzhip::invalid_arg(entry);
   if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
                  src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
-    return kvzhip::invalid_arg(__func__);
+    return kvzhip::invalid_arg(entry);
   const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
-  quant_consts ky, kc;
+  quant_consts ky = {}, kc = {};                                              // not read with a QP array
   // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants
-  if (!make_consts(&qp, 4, 0, 0, &ky) || !make_consts(&qp, 4, 2, 2, &kc)) return kvzhip::invalid_arg(__func__);
+  if (!lcu_qp && (!make_consts(&qp, 4, 0, 0, &ky) || !make_consts(&qp, 4, 2, 2, &kc))) return kvzhip::invalid_arg(entry);
   resid_args a;
   a.src_y = src->y; a.src_u = chroma ? src->u : nullptr; a.src_v = chroma ? src->v : nullptr;
   a.rec_y = rec_y; a.rec_u = chroma ? rec_u : nullptr; a.rec_v = chroma ? rec_v : nullptr;
@@ -274,14 +294,38 @@ int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *
   const int sizes[4] = { 32, 16, 8, 4 };
   for (int i = 0; i < 4; ++i) {
     const int n = sizes[i];
-    if (!make_consts(&qp, n, 0, 0, &ky) || !make_consts(&qp, n, 2, 2, &kc)) return kvzhip::invalid_arg(__func__);
-    if (n == 32) launch_size<32>(a, ky, kc, chroma, st);
-    else if (n == 16) launch_size<16>(a, ky, kc, chroma, st);
-    else if (n == 8) launch_size<8>(a, ky, kc, chroma, st);
-    else launch_size<4>(a, ky, kc, chroma, st);
+    if (lcu_qp) {
+      const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+      launch_width(n, a, ky, kc, chroma, st, per_lcu);
+    } else {
+      if (!make_consts(&qp, n, 0, 0, &ky) || !make_consts(&qp, n, 2, 2, &kc)) return kvzhip::invalid_arg(entry);
+      launch_width(n, a, ky, kc, chroma, st);
+    }
     KVZ_CHECK_LAUNCH("inter_residual_tu_kernel");
   }
   return KVZ_HIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                                 kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y,
+                                 kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                 const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
+{
+  KVZ_CHECK_CTX();
+  return residual_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, nullptr, params, s);
+}
+
+int kvz_hip_inter_residual_frame_qp(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                                    kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y,
+                                    kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                    const int8_t *lcu_qp, const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
+{
+  KVZ_CHECK_CTX();
+  return residual_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, params, s);
 }
 
 }  // extern "C"

@@ -22,381 +22,7 @@
 // workgroup wrote.  The walk is 256 iterations whatever the map says, everything that steers it is made wave-uniform
 // (readfirstlane), and every barrier is reached by all 64 lanes: lanes beyond a TU's N rows repeat the work of row
 // lane % N (identical values to identical LDS addresses) and are masked at every global access.
-#include "kvz_hip_internal.h"
-#include "transform_core.h"
-#include "quant_core.h"
-#include "lcu_layout.h"
-#include "intra_core.h"
-
-using namespace kvzhip;
-
-namespace {
-
-static_assert(sizeof(kvz_hip_inter_residual_params) == 24 && sizeof(kvz_hip_inter_residual_cost) == 24 && sizeof(kvz_hip_cu_info) == 20,
-              "layouts documented in kvz_hip.h");
-
-struct intra_args {
-  const u8 *src[3];
-  u8 *rec[3];
-  u32 src_stride[3], rec_stride[3];
-  i16 *coeff[3];
-  u32 *cus;                      // records as five dwords; cbf_y is byte 4
-  const u8 *modes;               // two bytes per SCU: intra.mode, intra.mode_chroma
-  u8 *cbf_out;                   // or nullptr
-  u32 *cost;                     // six dwords per SCU, or nullptr
-  int cus_stride, lcus_x;
-  int width, height;
-  quant_consts k[2][4];          // [luma / chroma][log2 N - 2]
-};
-
-// The LCU's tile in LDS: pixel (x, y) of the plane relative to the LCU's top-left, x = -1 .. T + T/2 - 1, y = -1 .. T - 1
-// (T = 64 luma, 32 chroma).  Column 0 stands at a dword boundary.
-constexpr int TS = 104, TILE_BYTES = 65 * TS;
-__device__ __forceinline__ int tpx(int x, int y) { return (y + 1) * TS + 4 + x; }
-
-// the intra CU that holds the luma position (x, y), from the record of that position alone: false for another type, a
-// depth beyond 3 or a CU that would leave the picture (the rule of kvz_hip_inter_residual_frame with the type swapped)
-__device__ __forceinline__ bool intra_cu_of(u32 head, int x, int y, int width, int height, int &cu_x, int &cu_y, int &leaf)
-{
-  const int depth = (head >> 8) & 255, trd = (int)(head >> 24);
-  if ((head & 255u) != 1u || depth > 3) return false;                         // CU_INTRA (cu.h:38-43)
-  const int size = 64 >> depth;
-  cu_x = x & ~(size - 1);
-  cu_y = y & ~(size - 1);
-  leaf = 64 >> min(4, max(max(depth, trd), 1));
-  return cu_x + size <= width && cu_y + size <= height;
-}
-
-// Outputs that TUs of three planes accumulate into start from zero inside the intra CUs (and keep their contents elsewhere).
-__global__ __launch_bounds__(256) void intra_recon_init_kernel(intra_args a, int n_scu)
-{
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_scu) return;
-  const int sy = i / a.cus_stride, sx = i - sy * a.cus_stride;
-  int cu_x, cu_y, leaf;
-  if (!intra_cu_of(a.cus[(size_t)i * 5], 4 * sx, 4 * sy, a.width, a.height, cu_x, cu_y, leaf)) return;
-  if (a.cbf_out) a.cbf_out[i] = 0;
-  if (a.cost && cu_x == 4 * sx && cu_y == 4 * sy) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
-  }
-}
-
-struct tu_pos {
-  int plane, sh;                 // sh = 1 for chroma
-  int lx, ly;                    // luma position in the picture
-  int tx, ty;                    // position in the tile, in pixels of the plane
-  int cu_x, cu_y;
-  int mode, scan;
-};
-
-struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { return p[(i / n) * ld + (i % n)]; } };
-
-// One leaf TU, N wide, by the whole wave.  Called under wave-uniform conditions only.
-template <int N>
-__device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS], u8 *s_ext,
-                                        u8 *s_pred, i16 *ta, i16 *tb, i16 *tq)
-{
-  constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5, LD = lds_tile_ld(N), W4 = N / 4;
-  const int lane = threadIdx.x, row = lane & (N - 1);
-  const bool own = lane < N;                                     // the lanes that touch global memory
-  const int sh = t.sh, flags = t.plane == 0 ? (KVZ_HIP_INTRA_LUMA | KVZ_HIP_INTRA_FILTER_BOUNDARY) : 0;
-
-  // ---- kvz_intra_build_reference (intra.c:334-588) from the tile, as intra_build_reference_kernel takes it from the plane ----
-  for (int i = lane; i < 4 * RS / 4; i += 64) ((u32 *)s_ref)[i] = 0u;
-  __syncthreads();
-  if (lane < 2 * N) {
-    const int ux = (t.lx & 63) >> 2, uy = (t.ly & 63) >> 2;
-    const bool has_left = t.lx > 0, has_top = t.ly > 0;
-    u8 left, top;
-    if (has_left) {
-      int avail = intra_coded_left(ux, uy) >> sh;
-      avail = min(avail, min(2 * N, (a.height - t.ly) >> sh));
-      left = tile[tpx(t.tx - 1, t.ty + min(lane, avail - 1))];
-    } else {
-      left = has_top ? tile[tpx(t.tx, t.ty - 1)] : 128;
-    }
-    if (has_top) {
-      int avail = intra_coded_above(ux, uy) >> sh;
-      avail = min(avail, min(2 * N, (a.width - t.lx) >> sh));
-      top = tile[tpx(t.tx + min(lane, avail - 1), t.ty - 1)];
-    } else {
-      top = has_left ? tile[tpx(t.tx - 1, t.ty)] : 128;
-    }
-    s_ref[0][1 + lane] = left;
-    s_ref[1][1 + lane] = top;
-    if (lane == 0) {
-      const u8 corner = (has_left && has_top) ? tile[tpx(t.tx - 1, t.ty - 1)] : (has_left ? tile[tpx(t.tx - 1, t.ty)] : left);
-      s_ref[0][0] = corner;
-      s_ref[1][0] = corner;
-    }
-  }
-  __syncthreads();
-  // smoothed references (intra.c:164-192)
-  for (int i = lane; i < 2 * (2 * N + 1); i += 64) {
-    const int s = i >= 2 * N + 1, e = i - (2 * N + 1) * s;
-    const u8 *from = s_ref[s];
-    int v;
-    if (e == 0) v = (s_ref[0][1] + 2 * s_ref[0][0] + s_ref[1][1] + 2) >> 2;
-    else if (e == 2 * N) v = from[e];
-    else v = (from[e - 1] + 2 * from[e] + from[e + 1] + 2) >> 2;
-    s_ref[2 + s][e] = (u8)v;
-  }
-  __syncthreads();
-
-  // ---- kvz_intra_predict (intra.c:281-331) ----
-  const bool fil = use_filtered(t.mode, LOG2, flags), edge = luma_edge_filters(LOG2, flags);
-  if (t.mode >= 2) {
-    const ang_t an = ang_of(t.mode);
-    for (int e = lane; e < 3 * N + 2; e += 64) s_ext[e] = ext_entry<N>(s_ref, fil, an, e - N);
-    __syncthreads();
-    const u8 *e = &s_ext[N];
-    const u8 *side = s_ref[2 * fil + (an.vertical ? 0 : 1)];
-    const bool pp = edge && (flags & KVZ_HIP_INTRA_FILTER_BOUNDARY) && an.disp == 0;
-    for (int px = lane; px < N * N; px += 64) {
-      const int y = px >> LOG2, x = px & (N - 1);
-      const int r = an.vertical ? y : x, c = an.vertical ? x : y;
-      int v = ang_px(e, an.disp, r, c);
-      if (pp && c == 0) v = post_px(v, side, r);
-      s_pred[px] = (u8)v;
-    }
-  } else if (t.mode == 1) {
-    const int dc = dc_value(s_ref, N, LOG2);
-    for (int px = lane; px < N * N; px += 64) s_pred[px] = (u8)dc_px(s_ref, dc, edge, px & (N - 1), px >> LOG2);
-  } else {
-    const u8 *left = s_ref[2 * fil], *top = s_ref[2 * fil + 1];
-    for (int px = lane; px < N * N; px += 64) s_pred[px] = (u8)planar_px(left, top, N, LOG2, px & (N - 1), px >> LOG2);
-  }
-  __syncthreads();
-
-  // ---- kvz_quantize_residual (quant-generic.c:180-273), the arithmetic of inter_residual_tu_kernel ----
-  const int px0 = t.lx >> sh, py0 = t.ly >> sh;
-  u32 sw[W4], pw[W4];
-  load_row<N>(a.src[t.plane] + (size_t)(py0 + row) * a.src_stride[t.plane] + px0, sw);      // lanes beyond N: the row of lane % N again
-#pragma unroll
-  for (int j = 0; j < W4; ++j) pw[j] = *(const u32 *)(s_pred + row * N + 4 * j);
-  u32 zssd = 0;
-#pragma unroll
-  for (int x = 0; x < N; ++x) {
-    const int d = byte_of(sw, x) - byte_of(pw, x);
-    ta[row * LD + x] = (i16)d;
-    zssd += (u32)(d * d);
-  }
-  __syncthreads();
-  if constexpr (N == 4) {
-    if (t.plane == 0) transform_2d_lds<4, 2, LD>(ta, tb, row);                // strategies-dct.c:66-85: DST for intra 4x4 luma
-    else transform_2d_lds<4, 0, LD>(ta, tb, row);
-  } else {
-    transform_2d_lds<N, 0, LD>(ta, tb, row);
-  }
-  __syncthreads();
-  int any = 0;
-#pragma unroll
-  for (int x = 0; x < N; ++x) {
-    const int v = quant_one(ta[row * LD + x], k.flat_qc, k);
-    tq[row * LD + x] = (i16)v;
-    any |= v;
-  }
-  if (k.signhide) {
-    // a lane per coefficient group, as sign_hide_kernel (quant.hip): the block's ac_sum is a sum over the lanes, the "last"
-    // group a ballot of the lanes that hold a level
-    __syncthreads();
-    constexpr int NCG = W4 * W4;
-    const bool cg_ok = lane < NCG;
-    const lds_view cv = { ta, LD, N }, qv = { tq, LD, N };
-    int pos16[16];
-    bool nz = false;
-    u32 ac = 0;
-#pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      pos16[n] = scan_pos(t.scan, LOG2, ((cg_ok ? lane : 0) << 4) + n);
-      nz = nz || qv[pos16[n]] != 0;
-      ac += (u32)quant_level(cv[pos16[n]], k.flat_qc, k);
-    }
-    ac = group_sum<64>(cg_ok ? ac : 0u);
-    const unsigned long long bal = __ballot(nz && cg_ok);
-    const bool is_last = nz && (bal & ~((2ull << lane) - 1ull)) == 0ull;
-    if (cg_ok && ac >= 2) sign_hide_cg(cv, qv, pos16, is_last, k);
-    __syncthreads();
-    any = 0;
-#pragma unroll
-    for (int x = 0; x < N; ++x) any |= tq[row * LD + x];
-  }
-  const int has = __syncthreads_or(any) ? 1 : 0;
-  u32 sab = 0;
-#pragma unroll
-  for (int x = 0; x < N; ++x) {
-    const int q = tq[row * LD + x];
-    sab += (u32)(q < 0 ? -q : q);
-    ta[row * LD + x] = (i16)dequant_one(q, row * N + x, k);
-  }
-  __syncthreads();
-  if constexpr (N == 4) {
-    if (t.plane == 0) transform_2d_lds<4, 3, LD>(ta, tb, row);
-    else transform_2d_lds<4, 1, LD>(ta, tb, row);
-  } else {
-    transform_2d_lds<N, 1, LD>(ta, tb, row);
-  }
-  __syncthreads();
-  // the reconstruction goes into the tile; a TU without coefficients keeps its prediction (quant-generic.c:262-271)
-  u32 ssd = zssd;
-  if (has) ssd = 0;
-#pragma unroll
-  for (int j = 0; j < W4; ++j) {
-    u32 o = pw[j];
-    if (has) {
-      o = 0;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int x = 4 * j + i;
-        const i16 val = (i16)((int)ta[row * LD + x] + byte_of(pw, x));             // quant-generic.c:255
-        const int c = val < 0 ? 0 : (val > 255 ? 255 : val);
-        const int d = byte_of(sw, x) - c;
-        ssd += (u32)(d * d);
-        o |= (u32)c << (8 * i);
-      }
-    }
-    *(u32 *)(tile + tpx(t.tx + 4 * j, t.ty + row)) = o;                         // tx is a multiple of 4: an aligned dword
-  }
-  if (own) {
-    const int bx = (t.lx & 63) >> (2 + sh), by = (t.ly & 63) >> (2 + sh);
-    const size_t lcu = (size_t)(t.ly >> 6) * a.lcus_x + (t.lx >> 6);
-    i16 *dst = a.coeff[t.plane] + lcu * (t.plane ? 1024 : 4096) + 16 * zorder_blk(bx, by) + row * N;
-    if (N == 4) {
-      *(uint2 *)dst = make_uint2(*(const u32 *)(tq + row * LD), *(const u32 *)(tq + row * LD + 2));
-    } else {
-#pragma unroll
-      for (int j = 0; j < N / 8; ++j) *(uint4 *)(dst + 8 * j) = lds_tile_load8<N, LD>(tq, row * N + 8 * j);
-    }
-    // flags of the SCUs the TU covers: cbf_y as lcu_set_coeff leaves it (search.c:173-190), bit `plane` of cbf_out (zeroed by
-    // the init kernel)
-    const int sx0 = t.lx >> 2, sy0 = t.ly >> 2;
-    if (t.plane == 0) {
-      if ((row & 3) == 0) {
-        for (int i = 0; i < W4; ++i) {
-          const size_t scu = (size_t)(sy0 + (row >> 2)) * a.cus_stride + sx0 + i;
-          ((u8 *)a.cus)[scu * 20 + 4] = (u8)has;
-          if (a.cbf_out && has) or_byte(a.cbf_out, scu, 1u);
-        }
-      }
-    } else if (row < N / 2 && a.cbf_out && has) {
-      for (int i = 0; i < N / 2; ++i) or_byte(a.cbf_out, (size_t)(sy0 + row) * a.cus_stride + sx0 + i, 1u << t.plane);
-    }
-  }
-  if (a.cost) {
-    // integer sums: the order of the additions does not matter
-    ssd = group_sum<64>(own ? ssd : 0u);
-    zssd = group_sum<64>(own ? zssd : 0u);
-    sab = group_sum<64>(own ? sab : 0u);
-    if (lane == 0) {
-      u32 *c = a.cost + ((size_t)(t.cu_y >> 2) * a.cus_stride + (t.cu_x >> 2)) * 6 + sh;
-      atomicAdd(c, ssd);
-      atomicAdd(c + 2, zssd);
-      atomicAdd(c + 4, sab);
-    }
-  }
-  __syncthreads();                                                              // the tile is complete for the next TU
-}
-
-// z-order index -> coordinate: the even bits of i
-__device__ __forceinline__ int compact4(int i) { i &= 0x55; i = (i | (i >> 1)) & 0x33; return (i | (i >> 2)) & 0x0f; }
-
-// wave t of the picture: grid (lcus_y, planes), LCU (t - 2 ly, ly).  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
-// the lanes beyond a TU's N rows repeat row lane % N, which is the same value to the same LDS address only while all of them are
-// one wave in lockstep; with a second wave the read-modify-write of ta / tq would race.
-constexpr int WG = 64;
-static_assert(WG == 64, "one wave per workgroup: see intra_tu");
-__global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int t)
-{
-  __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
-  __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
-  __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
-  __shared__ __attribute__((aligned(16))) u8 s_pred[32 * 32];
-  __shared__ __attribute__((aligned(16))) i16 sa[32 * lds_tile_ld(32)];     // residual / coefficients
-  __shared__ __attribute__((aligned(16))) i16 sb[32 * lds_tile_ld(32)];     // transform scratch
-  __shared__ __attribute__((aligned(16))) i16 sq[32 * lds_tile_ld(32)];     // quantized coefficients
-  __shared__ u8 s_intra[256];                                                // SCU (raster) belongs to an intra CU of this call
-
-  const int lane = threadIdx.x, plane = blockIdx.y, sh = plane ? 1 : 0;
-  const int lcu_y = blockIdx.x, lcu_x = t - 2 * lcu_y;
-  if (lcu_x < 0 || lcu_x >= a.lcus_x) return;
-  const int X0 = 64 * lcu_x, Y0 = 64 * lcu_y;
-
-  bool any = false;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int i = lane + 64 * j, x = X0 + 4 * (i & 15), y = Y0 + 4 * (i >> 4);
-    int cu_x, cu_y, leaf;
-    const bool in = x < a.width && y < a.height &&
-                    intra_cu_of(a.cus[((size_t)(y >> 2) * a.cus_stride + (x >> 2)) * 5], x, y, a.width, a.height, cu_x, cu_y, leaf);
-    s_intra[i] = in;
-    any = any || in;
-  }
-  if (!__syncthreads_or(any)) return;
-
-  // ---- the tile: rows -1 .. th - 1 as dwords (the plane's width and the tile's extent are multiples of 4), then the column left ----
-  const int T = 64 >> sh, pw = a.width >> sh, ph = a.height >> sh, x0 = X0 >> sh, y0 = Y0 >> sh;
-  const int tw = min(T, pw - x0), th = min(T, ph - y0), aw = y0 > 0 ? min(T + T / 2, pw - x0) : 0;
-  u8 *rec = a.rec[plane];
-  const size_t stride = a.rec_stride[plane];
-  constexpr int CW = (64 + 32) / 4;
-  for (int it = lane; it < (th + 1) * CW; it += 64) {
-    const int r = it / CW - 1, c4 = 4 * (it % CW);
-    if (c4 < (r < 0 ? aw : tw)) {
-      u32 v;
-      __builtin_memcpy(&v, rec + (size_t)(y0 + r) * stride + x0 + c4, 4);
-      *(u32 *)(tile + tpx(c4, r)) = v;
-    }
-  }
-  if (x0 > 0)
-    for (int r = lane - 1; r < th; r += 64)
-      if (r >= 0 || y0 > 0) tile[tpx(-1, r)] = rec[(size_t)(y0 + r) * stride + x0 - 1];
-  __syncthreads();
-
-  // ---- the walk: 256 SCUs in z-order; a leaf TU is done at its top-left SCU ----
-  for (int i = 0; i < 256; ++i) {
-    const int ux = compact4(i), uy = compact4(i >> 1);
-    tu_pos p;
-    p.plane = plane; p.sh = sh;
-    p.lx = X0 + 4 * ux; p.ly = Y0 + 4 * uy;
-    if (p.lx >= a.width || p.ly >= a.height) continue;
-    const size_t scu = (size_t)(p.ly >> 2) * a.cus_stride + (p.lx >> 2);
-    // one address for the whole wave: say so, and everything below is scalar
-    const u32 head = __builtin_amdgcn_readfirstlane(a.cus[scu * 5]);
-    int leaf = 0;
-    if (!intra_cu_of(head, p.lx, p.ly, a.width, a.height, p.cu_x, p.cu_y, leaf)) continue;
-    if ((p.lx | p.ly) & (leaf - 1)) continue;                                  // inside a TU that was done at its top-left
-    int n = leaf;
-    if (plane) {
-      // chroma TUs are half as wide; with 4x4 luma TUs the chroma of the 8x8 area is one 4x4 TU at its first SCU (transform.c:293-313)
-      if (leaf == 4 && ((p.lx | p.ly) & 7)) continue;
-      n = leaf > 8 ? leaf >> 1 : 4;
-    }
-    p.mode = (int)__builtin_amdgcn_readfirstlane((u32)a.modes[2 * scu + (plane ? 1 : 0)]);
-    if (p.mode > 34) continue;
-    // kvz_get_scan_order (encoderstate.c:1384-1398): luma TUs 8 and 4 wide, chroma TUs 4 wide
-    p.scan = (leaf <= 8) ? ((p.mode >= 6 && p.mode <= 14) ? 2 : ((p.mode >= 22 && p.mode <= 30) ? 1 : 0)) : 0;
-    p.tx = (p.lx - X0) >> sh; p.ty = (p.ly - Y0) >> sh;
-    const quant_consts *kk = a.k[plane ? 1 : 0];
-    if (n == 32) intra_tu<32>(a, p, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else if (n == 16) intra_tu<16>(a, p, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else if (n == 8) intra_tu<8>(a, p, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else intra_tu<4>(a, p, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-  }
-
-  // ---- the pixels of the intra CUs go back: a row of an SCU (4 luma, 2 chroma pixels) per item, 16 SCUs of a row side by side ----
-  const int R = 4 >> sh;
-  for (int it = lane; it < 16 * T; it += 64) {
-    const int ux = it & 15, r = it >> 4;
-    if (!s_intra[(r / R) * 16 + ux]) continue;
-    u8 *g = rec + (size_t)(y0 + r) * stride + x0 + R * ux;
-    const u8 *l = tile + tpx(R * ux, r);
-    if (sh) __builtin_memcpy(g, l, 2);
-    else __builtin_memcpy(g, l, 4);
-  }
-}
-
-}  // namespace
+#include "intra_recon_core.h"
 
 extern "C" {
 
@@ -406,44 +32,7 @@ int kvz_hip_intra_recon_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec
                               kvz_hip_inter_residual_cost *costs, const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!src || !params || !rec_y || !cus || !intra_modes || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) ||
-      ((uintptr_t)costs & 3))
-    return kvzhip::invalid_arg(__func__);
-  const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      params->scaling_list != 0)
-    return kvzhip::invalid_arg(__func__);
-  if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
-                 src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
-    return kvzhip::invalid_arg(__func__);
-  const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
-  intra_args a;
-  // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants.  The shift of
-  // the transform depends on the size: a set of constants per size
-  for (int i = 0; i < 4; ++i)
-    if (!make_consts(&qp, 4 << i, 0, 0, &a.k[0][i]) || !make_consts(&qp, 4 << i, 2, 2, &a.k[1][i])) return kvzhip::invalid_arg(__func__);
-  a.src[0] = src->y; a.src[1] = chroma ? src->u : nullptr; a.src[2] = chroma ? src->v : nullptr;
-  a.rec[0] = rec_y; a.rec[1] = chroma ? rec_u : nullptr; a.rec[2] = chroma ? rec_v : nullptr;
-  a.src_stride[0] = src->stride_y; a.src_stride[1] = a.src_stride[2] = src->stride_c;
-  a.rec_stride[0] = stride_y; a.rec_stride[1] = a.rec_stride[2] = stride_c;
-  a.coeff[0] = coeff_y; a.coeff[1] = chroma ? coeff_u : nullptr; a.coeff[2] = chroma ? coeff_v : nullptr;
-  a.cus = (u32 *)cus; a.modes = intra_modes; a.cbf_out = cbf_out; a.cost = (u32 *)costs;
-  a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
-  a.width = width; a.height = height;
-  const int lcus_y = (height + 63) >> 6;
-  hipStream_t st = ctx_stream(s);
-  if (cbf_out || costs) {
-    const int n_scu = (width >> 2) * (height >> 2);
-    hipLaunchKernelGGL(intra_recon_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
-    KVZ_CHECK_LAUNCH("intra_recon_init_kernel");
-  }
-  // the launch sequence depends on width, height and chroma alone
-  const int waves = a.lcus_x + 2 * (lcus_y - 1);
-  for (int t = 0; t < waves; ++t) {
-    hipLaunchKernelGGL(intra_recon_wave_kernel, dim3((unsigned)lcus_y, chroma ? 3u : 1u), dim3(WG), 0, st, a, t);
-    KVZ_CHECK_LAUNCH("intra_recon_wave_kernel");
-  }
-  return KVZ_HIP_OK;
+  return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-// quant_core.h -- the quantisation arithmetic shared by quant.hip (batched entries) and inter_residual.hip (whole-picture
-// entry): the flattened encoder state, quant / dequant of one coefficient and the sign-bit-hiding pass.
+// quant_core.h -- the quantisation arithmetic shared by quant.hip (batched entries), inter_residual.hip and intra_recon_core.h
+// (whole-picture entries): the flattened encoder state and the one function that derives it for flat lists, on the host and on the
+// device (flat_consts), quant / dequant of one coefficient and the sign-bit-hiding pass.
 // Reference: src/strategies/generic/quant-generic.c (cited per function), transform.c:129-143 for the scaled QP.
 #pragma once
 
@@ -16,10 +17,10 @@ struct quant_consts {
   const int32_t *dqtable;
 };
 
-// transform.c:129-143
-static int scaled_qp(int type, int qp)
+// transform.c:129-143; type 0 is luma, every other type chroma
+__host__ __device__ inline int scaled_qp(int type, int qp)
 {
-  static const unsigned char chroma_scale[58] = {
+  const unsigned char chroma_scale[58] = {
      0, 1, 2, 3, 4, 5, 6, 7, 8, 9,10,11,12,13,14,15,16,17,18,19,20,21,22,23,24,25,26,27,28,29,29,30,31,32,
     33,33,34,34,35,35,36,36,37,37,38,39,40,41,42,43,44,45,46,47,48,49,50,51 };
   if (type == 0) return qp;
@@ -28,37 +29,48 @@ static int scaled_qp(int type, int qp)
 }
 static int log2i(int w) { int l = 0; while ((1 << l) < w) ++l; return l; }
 
-// quant-generic.c:40-50 and :283-320
+// The constants of flat lists (no scaling list) for one QP, transform size and colour, quant-generic.c:40-50 and :283-320: the
+// ONE place they are derived.  The host calls it per launch (make_consts below), the per-LCU-QP kernels call it per TU or per LCU
+// with the QP they read on the device.  qp >= 0; chroma: the QP goes through kvz_get_scaled_qp first.
+__host__ __device__ inline quant_consts flat_consts(int qp, int log2_tr, int chroma, int slice_is_intra, int signhide)
+{
+  const int quant_scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };     // scalinglist.c:66
+  const int inv_quant_scales[6] = { 40, 45, 51, 57, 64, 72 };                   // scalinglist.c:67
+  const int transform_shift = 15 - 8 - log2_tr;
+  const int qps = scaled_qp(chroma ? 2 : 0, qp);
+  quant_consts c;
+  c.q_bits = 14 + qps / 6 + transform_shift;
+  c.add = (slice_is_intra ? 171 : 85) << (c.q_bits - 9);
+  c.flat_qc = quant_scales[qps % 6];
+  c.signhide = signhide;
+  c.qtable = nullptr;
+  c.dq_mode = 0; c.dqtable = nullptr;
+  c.dq_scale = inv_quant_scales[qps % 6] << (qps / 6);
+  c.dq_shift = 20 - 14 - transform_shift; c.dq_add = 1 << (c.dq_shift - 1);
+  return c;
+}
+// the LCU QP the per-LCU entries use: any value is brought into 0..51 (the reference's CLIP_TO_QP), so that no value leaves a table
+__host__ __device__ inline int clip_lcu_qp(int qp) { return qp < 0 ? 0 : (qp > 51 ? 51 : qp); }
+
+// quant-generic.c:40-50 and :283-320: flat_consts, with the scaling-list tables on top where they are given
 static bool make_consts(const kvz_hip_quant_params *p, int width, int type_q, int type_dq, quant_consts *c)
 {
-  static const int quant_scales[6] = { 26214, 23302, 20560, 18396, 16384, 14564 };     // scalinglist.c:66
-  static const int inv_quant_scales[6] = { 40, 45, 51, 57, 64, 72 };                   // scalinglist.c:67
   if (width != 4 && width != 8 && width != 16 && width != 32) return false;
   const int log2_tr = log2i(width);
-  const int transform_shift = 15 - 8 - log2_tr;
-  {
-    const int qps = scaled_qp(type_q, p->qp);
-    if (qps < 0) return false;
-    c->q_bits = 14 + qps / 6 + transform_shift;
-    c->add = (p->slice_is_intra ? 171 : 85) << (c->q_bits - 9);
-    c->flat_qc = quant_scales[qps % 6];
-    c->signhide = p->signhide;
-    c->qtable = (p->scaling_list && p->quant_coeff) ? p->quant_coeff : nullptr;
+  if (scaled_qp(type_q, p->qp) < 0) return false;
+  *c = flat_consts(p->qp, log2_tr, type_q != 0, p->slice_is_intra, p->signhide);
+  c->qtable = (p->scaling_list && p->quant_coeff) ? p->quant_coeff : nullptr;
+  if ((type_q != 0) != (type_dq != 0)) {
+    const quant_consts d = flat_consts(p->qp, log2_tr, type_dq != 0, p->slice_is_intra, p->signhide);
+    c->dq_scale = d.dq_scale; c->dq_shift = d.dq_shift; c->dq_add = d.dq_add;
   }
-  {
+  if (p->scaling_list && p->dequant_coeff) {
     const int qps = scaled_qp(type_dq, p->qp);
-    int shift = 20 - 14 - transform_shift;
-    if (p->scaling_list && p->dequant_coeff) {
-      shift += 4;
-      c->dqtable = p->dequant_coeff;
-      if (shift > qps / 6) { c->dq_mode = 1; c->dq_shift = shift - qps / 6; c->dq_add = 1 << (c->dq_shift - 1); }
-      else { c->dq_mode = 2; c->dq_shift = qps / 6 - shift; c->dq_add = 0; }
-      c->dq_scale = 0;
-    } else {
-      c->dq_mode = 0; c->dqtable = nullptr;
-      c->dq_scale = inv_quant_scales[qps % 6] << (qps / 6);
-      c->dq_shift = shift; c->dq_add = 1 << (shift - 1);
-    }
+    const int shift = c->dq_shift + 4;
+    c->dqtable = p->dequant_coeff;
+    if (shift > qps / 6) { c->dq_mode = 1; c->dq_shift = shift - qps / 6; c->dq_add = 1 << (c->dq_shift - 1); }
+    else { c->dq_mode = 2; c->dq_shift = qps / 6 - shift; c->dq_add = 0; }
+    c->dq_scale = 0;
   }
   return true;
 }

@@ -234,11 +234,11 @@ def main():
         L.kvz_hip_set_tuning(tune_key.encode(), -1)
     if not args.only or any(o in "inter_recon_frame_p inter_recon_frame_b" for o in args.only.split(",")):
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
-    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k" for o in args.only.split(",")):
+    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp" for o in args.only.split(",")):
         inter_residual_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p" for o in args.only.split(",")):
         sao_frame_rows(L, st, dev, max(args.rounds, 5))
-    if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all" for o in args.only.split(",")):
+    if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all intra_recon_frame_1080p_mixed_lcu_qp cu_qp_frame_1080p" for o in args.only.split(",")):
         intra_recon_rows(L, st, dev, max(args.rounds, 5))
 
 
@@ -246,13 +246,15 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
     """Intra prediction + residual coding of whole 1080p 4:2:0 pictures in coding order (kvz_hip_intra_recon_frame): a random quadtree
     with about 10 % of its CUs intra (the rest inter: their LCU-workgroups leave after reading the map) and an all-intra one, modes
     and tr_depth as tests/intra_recon_cases.py sets them.  The stage is a chain of dependent launches (one per wavefront of LCUs) and
-    of dependent TUs inside an LCU, so the figure is a latency, not a throughput: ms per picture, medians over the rounds."""
+    of dependent TUs inside an LCU, so the figure is a latency, not a throughput: ms per picture, medians (and min..max) over the
+    rounds.  On the mixed picture the same call with a QP per LCU (kvz_hip_intra_recon_frame_qp, QPs 22..42 drawn per LCU) and the QP
+    map from its flags (kvz_hip_cu_qp_frame) are timed in the same rounds, interleaved with the one-QP row."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import intra_recon_cases as XC
     from kvazaar_amd import api
     W, H = 1920, 1080
-    print("%-32s %10s %10s %12s %10s" % ("kernel", "intra %", "TUs", "frames/s", "ms"))
+    print("%-38s %8s %10s %12s %10s %18s" % ("kernel", "intra %", "TUs", "frames/s", "ms", "min..max ms"))
     for name, share in (("intra_recon_frame_1080p_mixed", 0.1), ("intra_recon_frame_1080p_all", 1.0)):
         cus, _, modes = XC.make_map(W, H, 51, intra_share=share, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
         src, rec = XC.make_planes(cus, 52)
@@ -269,9 +271,30 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
             return L.kvz_hip_intra_recon_frame(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
                                                cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
                                                cbf_d.data_ptr(), cost_d.data_ptr(), prm.ctypes.data, st)
-        ms = sorted(timed(L, st, lambda: _lib.check(frame(), name), iters=iters, warm=1) for _ in range(rounds))[rounds // 2]
+        lcu_qp_d = up(np.random.default_rng(53).integers(22, 43, api.lcu_count(W, H)).astype(np.int8))
+        last_d = torch.empty(api.lcu_count(W, H), dtype=torch.int8, device=dev)
+        qprm = np.zeros(1, dtype=api.CU_QP_PARAMS)
+        qprm["start_qp"] = 32
+
+        def frame_qp():
+            return L.kvz_hip_intra_recon_frame_qp(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
+                                                  cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
+                                                  cbf_d.data_ptr(), cost_d.data_ptr(), lcu_qp_d.data_ptr(), prm.ctypes.data, st)
+
+        def qp_map():                                    # cbf_d: the flags of the intra CUs as the call before left them, 0 elsewhere
+            return L.kvz_hip_cu_qp_frame(cus_d.data_ptr(), cbf_d.data_ptr(), W, H, lcu_qp_d.data_ptr(), last_d.data_ptr(), qprm.ctypes.data, st)
+        rows = [(name, frame, iters)] + ([(name + "_lcu_qp", frame_qp, iters), ("cu_qp_frame_1080p", qp_map, 20)] if share < 1.0 else [])
+        cbf_d.zero_()
+        torch.cuda.synchronize()
+        t = {r[0]: [] for r in rows}
+        for _ in range(rounds):                          # interleaved round by round
+            for (rname, fn, it) in rows:
+                t[rname].append(timed(L, st, lambda: _lib.check(fn(), rname), iters=it, warm=1))
         m, _, _ = XC.intra_mask(cus, W, H)
-        print("%-32s %10.1f %10d %12.1f %10.3f" % (name, 100 * m.mean(), len(XC.walk_tus(cus, modes, W, H)), 1e3 / ms, ms))
+        for (rname, fn, it) in rows:
+            ms = float(np.median(t[rname]))
+            print("%-38s %8.1f %10d %12.1f %10.3f %18s" % (rname, 100 * m.mean(), len(XC.walk_tus(cus, modes, W, H)), 1e3 / ms, ms,
+                                                           "%.3f..%.3f" % (min(t[rname]), max(t[rname]))))
 
 
 def inter_recon_rows(L, st, dev, rounds, frames=64):
@@ -363,7 +386,8 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
     SAME TU population laid out contiguously, one call per size and plane, summed: the same arithmetic without plane addressing and
     without the gather a caller would add -- a lower bound of what the picture cost before the entry existed.  Interleaved round by
     round in one process, medians.  The entry works in place, so every timed call gets a fresh copy of the prediction (copied outside
-    the timed region).  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
+    the timed region).  At 1080p the same picture with a QP per LCU (kvz_hip_inter_residual_frame_qp, QPs 22..42 drawn per LCU) is timed
+    in the same rounds, interleaved.  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
     Algorithmic bytes: 5 per sample = 7.5 per luma pixel, + 20 per 16 luma pixels of map."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -394,6 +418,14 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
             return L.kvz_hip_inter_residual_frame(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
                                                   co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
                                                   prm.ctypes.data, st)
+        lcu_qp_d = up(np.random.default_rng(44).integers(22, 43, api.lcu_count(W, H)).astype(np.int8))
+
+        def frame_qp():
+            r = recs[turn[0] % len(recs)]
+            turn[0] += 1
+            return L.kvz_hip_inter_residual_frame_qp(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
+                                                     co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
+                                                     lcu_qp_d.data_ptr(), prm.ctypes.data, st)
         # the same TUs, contiguous, per (plane, size)
         groups = {}
         for t in RC.walk_tus(cus, W, H):
@@ -423,16 +455,24 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
                     d.copy_(m)
             torch.cuda.synchronize()
             turn[0] = 0
-        t = {"frame": [], "contig": []}
+        t = {"frame": [], "contig": [], "lcu_qp": []}
         for _ in range(rounds):
             refresh()
             t["frame"].append(timed(L, st, lambda: _lib.check(frame(), name), iters=iters - 1, warm=1))
+            if W == 1920:
+                refresh()
+                t["lcu_qp"].append(timed(L, st, lambda: _lib.check(frame_qp(), name + "_lcu_qp"), iters=iters - 1, warm=1))
             t["contig"].append(timed(L, st, lambda: _lib.check(batches(), name + " contiguous"), iters=iters - 1, warm=1))
         ms, ms_c = float(np.median(t["frame"])), float(np.median(t["contig"]))
         n_tus = sum(c[2] for c in contig)
         nbytes = 7.5 * W * H + 20.0 * W * H / 16
         print("%-28s %10d %12.1f %10.1f %8.4f %8.2f" % (name, n_tus, 1e3 / ms, nbytes / ms / 1e6, ms, ms_c / ms))
         print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "(contig)", n_tus, 1e3 / ms_c, 7.5 * W * H / ms_c / 1e6, ms_c, "-"))
+        print("#   %s over the %d rounds: min..max %.4f..%.4f ms" % (name, rounds, min(t["frame"]), max(t["frame"])))
+        if t["lcu_qp"]:
+            ms_q = float(np.median(t["lcu_qp"]))
+            print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "_lcu_qp", n_tus, 1e3 / ms_q, nbytes / ms_q / 1e6, ms_q, "-"))
+            print("#   %s_lcu_qp over the %d rounds: min..max %.4f..%.4f ms" % (name, rounds, min(t["lcu_qp"]), max(t["lcu_qp"])))
         print("#   fraction of the 8 TB/s HBM roofline: frame %.3f, contiguous sum %.3f; %d launches against %d" %
               (nbytes / ms / 1e6 / 8000, 7.5 * W * H / ms_c / 1e6 / 8000, 5, len(contig)))
         if W != 1920:

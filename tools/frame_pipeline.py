@@ -13,7 +13,11 @@ once), so launch overhead, partial waves and tails count the way they do in an e
 tools/bench_all.py, whose batches are sized to hide them.  It is a measurement of the kernels on a
 frame-sized workload, not of an encoder: the mode decision around them is not here.
 
-  python tools/frame_pipeline.py [--frames 200]
+  python tools/frame_pipeline.py [--frames 200] [--lcu-qp]
+
+--lcu-qp: the picture chain of a frame whose QP changes per LCU (rate control, --roi): intra reconstruction through
+kvz_hip_intra_recon_frame_qp with a QP array, then kvz_hip_cu_qp_frame (the QP map and the per-LCU predictor), and deblocking
+with per_cu_qp = 1.
 """
 import argparse
 import ctypes as C
@@ -32,7 +36,7 @@ from kvazaar_amd._lib import QuantParams  # noqa: E402
 W, H = 1920, 1080
 
 
-def build_stages(L, dev):
+def build_stages(L, dev, lcu_qp=False):
     """-> {stage: [(name, units, launch(stream))]}, plus the tensors kept alive"""
     g = torch.Generator(device=dev); g.manual_seed(7)
     keep = []
@@ -108,9 +112,23 @@ def build_stages(L, dev):
     ir_tab = api.ref_picture_table([(ir_src[0].data_ptr(), ir_src[1].data_ptr(), ir_src[2].data_ptr(), W, W // 2)], W, H)
     ir_prm = api.inter_residual_params(27, 0, 0, 1)
     keep += [ir_src, ir_rec, ir_cus_d, ir_modes_d, ir_co, ir_tab, ir_prm]
-    stages["tu"].append(("intra_recon_frame", 1, lambda s: L.kvz_hip_intra_recon_frame(
-        ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
-        ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), None, None, ir_prm.ctypes.data, s)))
+    if lcu_qp:
+        # a QP per LCU: the flags go to an array (cleared once), the QP map is written from it after the intra stage
+        ir_qp = up(np.random.default_rng(35).integers(22, 43, api.lcu_count(W, H)).astype(np.int8))
+        ir_cbf = torch.zeros(ir_cus.shape, dtype=torch.uint8, device=dev)
+        ir_last = torch.empty(api.lcu_count(W, H), dtype=torch.int8, device=dev)
+        ir_qprm = np.zeros(1, dtype=api.CU_QP_PARAMS)
+        ir_qprm["start_qp"] = 27
+        keep += [ir_qp, ir_cbf, ir_last, ir_qprm]
+        stages["tu"].append(("intra_recon_frame_qp", 1, lambda s: L.kvz_hip_intra_recon_frame_qp(
+            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+            ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr(), None, ir_qp.data_ptr(), ir_prm.ctypes.data, s)))
+        stages["tu"].append(("cu_qp_frame", 1, lambda s: L.kvz_hip_cu_qp_frame(
+            ir_cus_d.data_ptr(), ir_cbf.data_ptr(), W, H, ir_qp.data_ptr(), ir_last.data_ptr(), ir_qprm.ctypes.data, s)))
+    else:
+        stages["tu"].append(("intra_recon_frame", 1, lambda s: L.kvz_hip_intra_recon_frame(
+            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+            ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), None, None, ir_prm.ctypes.data, s)))
 
     qp = QuantParams(); qp.qp = 27
     keep.append(qp)
@@ -147,7 +165,7 @@ def build_stages(L, dev):
     dbu = torch.from_numpy(np.tile(tu, reps)[:DH // 2, :W // 2].copy()).to(dev)
     dbv = torch.from_numpy(np.tile(tv, reps)[:DH // 2, :W // 2].copy()).to(dev)
     dbc = torch.from_numpy(np.tile(tcus, reps)[:DH // 4, :W // 4].copy().view(np.uint8)).to(dev)
-    dbp = deblock_params(qp=36)
+    dbp = deblock_params(qp=36, per_cu_qp=1 if lcu_qp else 0)          # per_cu_qp: the filter reads the qp field of the records
     keep += [dby, dbu, dbv, dbc, dbp]
     stages["sao"].insert(0, ("deblock_frame", 1, lambda s: L.kvz_hip_deblock_frame(
         dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, W, DH, dbc.data_ptr(), dbp.ctypes.data, s)))
@@ -221,6 +239,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--tune", default="", help="key=value[,key=value...] passed to kvz_hip_set_tuning")
+    ap.add_argument("--lcu-qp", action="store_true", help="a QP per LCU: intra_recon_frame_qp, cu_qp_frame, deblocking with per_cu_qp = 1")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     L = _lib.init(0)
@@ -230,7 +249,7 @@ def main():
     s = L.kvz_hip_stream_create()
     side = [L.kvz_hip_stream_create() for _ in range(7)]
     events = [L.kvz_hip_event_create() for _ in range(8)]
-    stages, keep = build_stages(L, dev)
+    stages, keep = build_stages(L, dev, args.lcu_qp)
     torch.cuda.synchronize()
     n_launch = sum(len(v) for v in stages.values())
 
@@ -251,7 +270,7 @@ def main():
             L.kvz_hip_event_destroy(e0); L.kvz_hip_event_destroy(e1)
             total += ms.value / 20
             print("%-34s %9d %10.1f" % (name, units, ms.value / 20 * 1e3))
-    print("%-34s %9s %10.1f   (%d calls; intra_recon_frame is %d kernel launches of its own)" % ("sum of the entries", "", total * 1e3, n_launch,
+    print("%-34s %9s %10.1f   (%d calls; the intra reconstruction is %d kernel launches of its own)" % ("sum of the entries", "", total * 1e3, n_launch,
                                                                                                1 + (W + 63) // 64 + 2 * ((H + 63) // 64 - 1)))
 
     results = {}
