@@ -1167,6 +1167,75 @@ KVZ_HIP_API int kvz_hip_sao_frame(const kvz_hip_pixel *rec_y, uint32_t stride_y,
                                   kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
+/* Tiles in the picture chain: intra, QP map, deblocking and SAO       */
+/*   reference: everything in-loop works on state->tile->frame, a      */
+/*   sub-picture with its own origin and size (intra.c:334-588,        */
+/*   encoderstate.c:550-609 / :729, filter.c:690-779, sao.c:278-337);  */
+/*   loop_filter_across_tiles_enabled_flag = 0                         */
+/*   (encoder_state-bitstream.c:501)                                   */
+/* ------------------------------------------------------------------ */
+#define KVZ_HIP_MAX_TILES_PER_DIM 48            /* global.h:217; counts are 1..47 */
+typedef struct {
+  int32_t cols, rows;                           /* 1..47 each */
+  int32_t col_bd[KVZ_HIP_MAX_TILES_PER_DIM];    /* tiles_col_bd (encoder.c:472-475), in LCUs: [0] = 0, strictly increasing,
+                                                   [cols] = ceil(width / 64); entries beyond [cols] are not read */
+  int32_t row_bd[KVZ_HIP_MAX_TILES_PER_DIM];    /* tiles_row_bd (encoder.c:478-481): [rows] = ceil(height / 64) */
+} kvz_hip_tile_grid;                            /* 392 bytes; HOST, copied at the call */
+/* The four stages of the chain that depend on tiles, each for a whole tiled picture in one call: the signature of the untiled
+ * entry plus the grid, placed before params where there is one, else before the stream.  The stages that do not depend on tiles
+ * take a tiled picture as they are: kvz_hip_inter_recon_frame (the reference clamps against the whole picture, inter.c:328-331),
+ * kvz_hip_inter_residual_frame(_qp) (per TU) and kvz_hip_sao_stats_frame (LCU interiors only).
+ * ONE RULE: the result inside each tile is what the untiled entry gives for a picture that consists of that tile alone -- its
+ *   planes the tile's rectangle of the planes, its CU map, modes and cbf bytes the tile's rectangle of the maps, its per-LCU
+ *   values the tile's LCUs.
+ * Planes, cus, intra_modes, cbf and costs stay picture-wide with their strides; the per-LCU arrays (coefficients, lcu_qp,
+ *   lcu_last_qp, sao_luma, sao_chroma) stay in PICTURE RASTER ORDER over the LCUs, as with every other entry and as
+ *   kvz_get_lcu_stats indexes them (encoderstate.c:1400-1406); the host's tile scan is its own business.  Alignment and stride
+ *   rules are the untiled entry's.
+ * grid == NULL is one tile, the whole picture: the outputs are byte for byte the untiled entry's.  A count outside 1..47,
+ *   bd[0] != 0, a boundary that does not increase or a last boundary that is not the picture's LCU count returns
+ *   KVZ_HIP_ERR_INVALID and nothing is written, as does every error of the untiled entry.
+ * Each entry is asynchronous on s, allocates nothing, does not synchronise with the host and owns no workspace; usable between
+ *   kvz_hip_graph_begin / _end.  The launch shapes depend on width, height, chroma and the grid only: a captured call replays
+ *   after the CONTENTS of every device array changed.
+ *
+ * kvz_hip_intra_recon_frame_tiles (kvz_intra_recon_cu): the arguments of kvz_hip_intra_recon_frame_qp; lcu_qp may be NULL, which
+ *   means params->qp everywhere.  Reference-pixel availability, the clipping of the above-right and below-left runs, has_left /
+ *   has_top and the 128 / substitution rules are taken against the TU's tile, and no TU reads a pixel outside its tile: the
+ *   tiles of a picture run side by side.  Wavefronts count from each tile's origin, t = (lcu_x - tile_x0) + 2 (lcu_y - tile_y0);
+ *   all tiles share launch t, and the number of dependent launches is the maximum over the tiles of w_t + 2 (h_t - 1).
+ * kvz_hip_cu_qp_frame_tiles (set_cu_qps): the rule of kvz_hip_cu_qp_frame with the chains chain_rows names; last = start_qp
+ *   at the start of every chain, lcu_last_qp[lcu] = last on entry to that LCU. */
+typedef struct {
+  int32_t start_qp;    /* as kvz_hip_cu_qp_params */
+  int32_t chain_rows;  /* 0: every tile is one chain, its LCUs in raster order inside the tile (a tile is a leaf state);
+                          1: every LCU row of every tile is a chain (WPP inside tiles); anything else: KVZ_HIP_ERR_INVALID */
+} kvz_hip_cu_qp_tiles_params; /* 8 bytes */
+/* kvz_hip_deblock_frame_tiles: the vertical edges at 64 col_bd[i] and the horizontal edges at 64 row_bd[j], 0 < i < cols,
+ *   0 < j < rows, are not filtered, in luma or in chroma; the right edge of a tile ends the horizontal edges as the right edge of
+ *   the picture does (filter.c:645-656).  Everything else is kvz_hip_deblock_frame.  An unfiltered boundary decouples its two
+ *   sides, so "all vertical edges, then all horizontal edges" over the picture remains the reference's order inside every tile.
+ * kvz_hip_sao_frame_tiles: an edge-offset pixel whose neighbour a or b lies outside its tile keeps its deblocked value; band
+ *   offset and copy are kvz_hip_sao_frame's. */
+KVZ_HIP_API int kvz_hip_intra_recon_frame_tiles(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                                const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                                kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                                const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
+                                                const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_cu_qp_frame_tiles(kvz_hip_cu_info *cus, const uint8_t *cbf, int width, int height, const int8_t *lcu_qp,
+                                          int8_t *lcu_last_qp, const kvz_hip_tile_grid *grid,
+                                          const kvz_hip_cu_qp_tiles_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_deblock_frame_tiles(kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v,
+                                            uint32_t stride_c, int width, int height, const kvz_hip_cu_info *cus,
+                                            const kvz_hip_tile_grid *grid, const kvz_hip_deblock_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_sao_frame_tiles(const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
+                                        const kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_pixel *dst_y, uint32_t dst_stride_y,
+                                        kvz_hip_pixel *dst_u, kvz_hip_pixel *dst_v, uint32_t dst_stride_c, int width, int height,
+                                        const kvz_hip_sao_info *sao_luma, const kvz_hip_sao_info *sao_chroma, int chroma,
+                                        const kvz_hip_tile_grid *grid, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */
 /* ------------------------------------------------------------------ */
 /* kvz_strategyselector_register (strategyselector.h:87, strategyselector.c:216-256) */

@@ -44,6 +44,17 @@ class TilePlane(C.Structure):
 
 
 MAX_RECTS = 16      # KVZ_HIP_MAX_RECTS
+MAX_TILES_PER_DIM = 48      # KVZ_HIP_MAX_TILES_PER_DIM
+
+
+class TileGrid(C.Structure):
+    """kvz_hip_tile_grid"""
+    _fields_ = [("cols", C.c_int32), ("rows", C.c_int32), ("col_bd", C.c_int32 * MAX_TILES_PER_DIM), ("row_bd", C.c_int32 * MAX_TILES_PER_DIM)]
+
+
+class CuQpTilesParams(C.Structure):
+    """kvz_hip_cu_qp_tiles_params"""
+    _fields_ = [("start_qp", C.c_int32), ("chain_rows", C.c_int32)]
 
 
 class KvzHipError(RuntimeError):
@@ -142,6 +153,10 @@ SIGNATURES = {
     "kvz_hip_cu_qp_frame": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
     "kvz_hip_sao_stats_frame": (_I, [_P, _P, _U, _P, _P, _U, _I, _P, _P, _P]),
     "kvz_hip_sao_frame": (_I, [_P, _U, _P, _P, _U, _P, _U, _P, _P, _U, _I, _I, _P, _P, _I, _P]),
+    "kvz_hip_intra_recon_frame_tiles": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "kvz_hip_cu_qp_frame_tiles": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "kvz_hip_deblock_frame_tiles": (_I, [_P, _U, _P, _P, _U, _I, _I, _P, _P, _P, _P]),
+    "kvz_hip_sao_frame_tiles": (_I, [_P, _U, _P, _P, _U, _P, _U, _P, _P, _U, _I, _I, _P, _P, _I, _P, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

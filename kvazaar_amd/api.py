@@ -531,11 +531,41 @@ def bipred_cost_batch(pic, ref0, ref1, cands):
     return out.to_numpy(np.uint32, (len(rec),))
 
 
+# ---- tiles of a picture, for the *_tiles entries of the picture chain ----
+TILE_GRID = np.dtype([("cols", "<i4"), ("rows", "<i4"), ("col_bd", "<i4", (48,)), ("row_bd", "<i4", (48,))])   # kvz_hip_tile_grid
+
+
+def tile_grid(width, height, col_bd, row_bd):
+    """one TILE_GRID record from the boundaries in LCUs, as encoder_control's tiles_col_bd / tiles_row_bd hold them: [0, ..., LCUs
+    per row] and [0, ..., LCU rows].  The library checks them against width and height; this only refuses what does not fit the record."""
+    col_bd, row_bd = [int(v) for v in col_bd], [int(v) for v in row_bd]
+    if not (2 <= len(col_bd) <= 48 and 2 <= len(row_bd) <= 48):
+        raise ValueError("1 to 47 tile columns and rows")
+    g = np.zeros(1, dtype=TILE_GRID)
+    g["cols"], g["rows"] = len(col_bd) - 1, len(row_bd) - 1
+    g["col_bd"][0, :len(col_bd)], g["row_bd"][0, :len(row_bd)] = col_bd, row_bd
+    return g
+
+
+def uniform_tile_grid(width, height, cols, rows):
+    """the reference's uniform spacing (encoder.c:437-458): tile i of c over n LCUs is (i + 1) n / c - i n / c LCUs wide"""
+    lx, ly = (width + 63) // 64, (height + 63) // 64
+    bd = lambda n, c: [0] + list(np.cumsum([(i + 1) * n // c - i * n // c for i in range(c)]))
+    return tile_grid(width, height, bd(lx, cols), bd(ly, rows))
+
+
+def _grid(tiles):
+    """the record as the *_tiles entries take it (HOST, copied at the call); the caller keeps the array until the call returned"""
+    g = np.ascontiguousarray(tiles)
+    assert g.dtype == TILE_GRID and g.size == 1
+    return g
+
+
 # ---- deblocking ----
-def deblock_frame(y, u, v, cus, prm):
+def deblock_frame(y, u, v, cus, prm, tiles=None):
     """y, u, v: uint8 planes or PlaneViews (u, v None with prm['chroma'] == 0; u and v share one stride); cus: kvz_hip_cu_info
     records [h/4, w/4] (20 bytes each); prm: one kvz_hip_deblock_params record (64 bytes).  Returns the filtered planes (the
-    whole buffer of a PlaneView)."""
+    whole buffer of a PlaneView).  tiles: a TILE_GRID record (tile_grid / uniform_tile_grid) -> kvz_hip_deblock_frame_tiles."""
     L = _lib.init()
     cus = np.ascontiguousarray(cus)
     prm = np.ascontiguousarray(prm)
@@ -544,8 +574,13 @@ def deblock_frame(y, u, v, cus, prm):
     du = _Staged(u) if u is not None else None
     dv = _Staged(v) if v is not None else None
     assert du is None or dv is None or du.stride == dv.stride
-    check(L.kvz_hip_deblock_frame(dy.ptr, dy.stride, du.ptr if du else None, dv.ptr if dv else None, du.stride if du else 0,
-                                  dy.w, dy.h, dc.ptr, prm.ctypes.data, None), "deblock_frame")
+    if tiles is None:
+        check(L.kvz_hip_deblock_frame(dy.ptr, dy.stride, du.ptr if du else None, dv.ptr if dv else None, du.stride if du else 0,
+                                      dy.w, dy.h, dc.ptr, prm.ctypes.data, None), "deblock_frame")
+    else:
+        g = _grid(tiles)
+        check(L.kvz_hip_deblock_frame_tiles(dy.ptr, dy.stride, du.ptr if du else None, dv.ptr if dv else None, du.stride if du else 0,
+                                            dy.w, dy.h, dc.ptr, g.ctypes.data, prm.ctypes.data, None), "deblock_frame_tiles")
     return (dy.download(), du.download() if du else None, dv.download() if dv else None)
 
 
@@ -652,18 +687,21 @@ def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhid
     return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp)
 
 
-def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None):
+def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
+                      tiles=None):
     """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
     intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
-    dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp."""
+    dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp.  tiles: a TILE_GRID record ->
+    kvz_hip_intra_recon_frame_tiles (with or without lcu_qp)."""
     cus = np.ascontiguousarray(cus)
     modes = np.ascontiguousarray(modes, dtype=np.uint8)
     assert modes.shape == cus.shape + (2,)
-    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp)
+    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles)
 
 
-def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None):
-    """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries"""
+def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None):
+    """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries; tiles given (intra only): the
+    _tiles entry"""
     L = _lib.init()
     chroma = int(chroma)
     height, width = src[0].shape
@@ -692,12 +730,18 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
         dq = DeviceBuffer.from_numpy(lq)
         tail = (dq.ptr,) + tail
     if modes is None:
+        assert tiles is None
         entry = L.kvz_hip_inter_residual_frame if lcu_qp is None else L.kvz_hip_inter_residual_frame_qp
         check(entry(*planes, *outs, *tail), "inter_residual frame")
     else:
         dm = DeviceBuffer.from_numpy(modes)
-        entry = L.kvz_hip_intra_recon_frame if lcu_qp is None else L.kvz_hip_intra_recon_frame_qp
-        check(entry(*planes, dm.ptr, *outs, *tail), "intra_recon frame")
+        if tiles is not None:
+            g = _grid(tiles)
+            check(L.kvz_hip_intra_recon_frame_tiles(*planes, dm.ptr, *outs, dq.ptr if lcu_qp is not None else None, g.ctypes.data, prm.ctypes.data, None),
+                  "intra_recon frame_tiles")
+        else:
+            entry = L.kvz_hip_intra_recon_frame if lcu_qp is None else L.kvz_hip_intra_recon_frame_qp
+            check(entry(*planes, dm.ptr, *outs, *tail), "intra_recon frame")
     pad = (None,) * (3 - n)
     return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
             "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
@@ -708,12 +752,28 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
 
 # ---- the QP map of a picture whose QP changes per LCU ----
 CU_QP_PARAMS = np.dtype([("start_qp", "<i4"), ("chain_lcus", "<i4")])                            # kvz_hip_cu_qp_params
+CU_QP_TILES_PARAMS = np.dtype([("start_qp", "<i4"), ("chain_rows", "<i4")])                      # kvz_hip_cu_qp_tiles_params
 
 
 def cu_qp_frame(cus, cbf, lcu_qp, start_qp, chain_lcus=0):
     """kvz_hip_cu_qp_frame.  cus: kvz_hip_cu_info records [height / 4, width / 4]; cbf: the cbf_out array of the residual stages,
     uint8 of the same shape; lcu_qp: int8 [LCUs] in raster order; start_qp: the picture's QP; chain_lcus: 0 = one chain, LCUs per
     row = a chain per LCU row.  Returns (cus with qp written, lcu_last_qp int8 [LCUs]: the QP predictor on entry to each LCU)."""
+    prm = np.zeros(1, dtype=CU_QP_PARAMS)
+    prm["start_qp"], prm["chain_lcus"] = start_qp, chain_lcus
+    return _cu_qp(cus, cbf, lcu_qp, prm, None)
+
+
+def cu_qp_frame_tiles(cus, cbf, lcu_qp, start_qp, tiles, chain_rows=0):
+    """kvz_hip_cu_qp_frame_tiles.  As cu_qp_frame; tiles: a TILE_GRID record (None: one tile); the chains are the tiles (chain_rows = 0)
+    or the LCU rows of the tiles (chain_rows = 1).  lcu_last_qp stays in picture raster order."""
+    prm = np.zeros(1, dtype=CU_QP_TILES_PARAMS)
+    prm["start_qp"], prm["chain_rows"] = start_qp, chain_rows
+    return _cu_qp(cus, cbf, lcu_qp, prm, (None if tiles is None else _grid(tiles),))
+
+
+def _cu_qp(cus, cbf, lcu_qp, prm, grid):
+    """the staging both QP-map entries share; grid: None for the untiled entry, else (TILE_GRID record or None,)"""
     L = _lib.init()
     cus = np.ascontiguousarray(cus)
     assert cus.dtype.itemsize == 20 and cus.ndim == 2
@@ -721,10 +781,12 @@ def cu_qp_frame(cus, cbf, lcu_qp, start_qp, chain_lcus=0):
     cb = np.ascontiguousarray(cbf, dtype=np.uint8).reshape(cus.shape)
     n = lcu_count(width, height)
     lq = np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(n)
-    prm = np.zeros(1, dtype=CU_QP_PARAMS)
-    prm["start_qp"], prm["chain_lcus"] = start_qp, chain_lcus
     dcu, dcb, dq, dl = DeviceBuffer.from_numpy(cus.view(np.uint8)), DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(lq), DeviceBuffer(n)
-    check(L.kvz_hip_cu_qp_frame(dcu.ptr, dcb.ptr, width, height, dq.ptr, dl.ptr, prm.ctypes.data, None), "cu_qp frame")
+    if grid is None:
+        check(L.kvz_hip_cu_qp_frame(dcu.ptr, dcb.ptr, width, height, dq.ptr, dl.ptr, prm.ctypes.data, None), "cu_qp frame")
+    else:
+        check(L.kvz_hip_cu_qp_frame_tiles(dcu.ptr, dcb.ptr, width, height, dq.ptr, dl.ptr, None if grid[0] is None else grid[0].ctypes.data,
+                                          prm.ctypes.data, None), "cu_qp frame_tiles")
     return dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape), dl.to_numpy(np.int8, (n,))
 
 
@@ -766,10 +828,11 @@ def sao_stats_frame(src, rec, chroma=1, with_cands=True):
     return stats, cands
 
 
-def sao_frame(rec, sao_luma, sao_chroma=None, chroma=1, dst=None):
+def sao_frame(rec, sao_luma, sao_chroma=None, chroma=1, dst=None, tiles=None):
     """kvz_hip_sao_frame.  rec: (y, u, v) uint8 planes or PlaneViews of the deblocked picture; sao_luma / sao_chroma: int32
     [LCUs, 14] or SAO_INFO records in raster order; dst: the initial destination planes (arrays or PlaneViews of the picture's
-    size; default zeros).  Returns the destination (y, u, v) after the call (the whole buffer of a PlaneView)."""
+    size; default zeros).  Returns the destination (y, u, v) after the call (the whole buffer of a PlaneView).  tiles: a TILE_GRID
+    record -> kvz_hip_sao_frame_tiles."""
     L = _lib.init()
     chroma = int(chroma)
     r = _stage_planes(rec, chroma)
@@ -782,9 +845,14 @@ def sao_frame(rec, sao_luma, sao_chroma=None, chroma=1, dst=None):
     infos = [np.ascontiguousarray(a).view(np.int32).reshape(n, 14) if a is not None and np.asarray(a).dtype == SAO_INFO
              else (np.ascontiguousarray(a, dtype=np.int32).reshape(n, 14) if a is not None else None) for a in (sao_luma, sao_chroma)]
     di = [DeviceBuffer.from_numpy(a) if a is not None else None for a in infos]
-    check(L.kvz_hip_sao_frame(r[0].ptr, r[0].stride, r[1].ptr if chroma else None, r[2].ptr if chroma else None, r[1].stride if chroma else 0,
-                              d[0].ptr, d[0].stride, d[1].ptr if chroma else None, d[2].ptr if chroma else None, d[1].stride if chroma else 0,
-                              w, h, di[0].ptr, di[1].ptr if di[1] else None, chroma, None), "sao_frame")
+    args = (r[0].ptr, r[0].stride, r[1].ptr if chroma else None, r[2].ptr if chroma else None, r[1].stride if chroma else 0,
+            d[0].ptr, d[0].stride, d[1].ptr if chroma else None, d[2].ptr if chroma else None, d[1].stride if chroma else 0,
+            w, h, di[0].ptr, di[1].ptr if di[1] else None, chroma)
+    if tiles is None:
+        check(L.kvz_hip_sao_frame(*args, None), "sao_frame")
+    else:
+        g = _grid(tiles)
+        check(L.kvz_hip_sao_frame_tiles(*args, g.ctypes.data, None), "sao_frame_tiles")
     out = [p.download() for p in d]
     return tuple(out + [None] * (3 - len(out)))
 

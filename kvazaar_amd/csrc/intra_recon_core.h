@@ -1,6 +1,6 @@
-// intra_recon_core.h -- the kernels and the host side of the two whole-picture intra entries (intra_recon.hip: one QP per call,
-// intra_recon_qp.hip: a QP per LCU).  Everything here has internal linkage: each of the two translation units gets its own copy and
-// instantiates exactly one of the two kernels.  The algorithm is described in intra_recon.hip.
+// intra_recon_core.h -- the kernels and the host side of the whole-picture intra entries (intra_recon.hip: one QP per call,
+// intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture).  Everything here has internal linkage: each of the
+// translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is described in intra_recon.hip.
 #pragma once
 
 #include "kvz_hip_internal.h"
@@ -8,6 +8,7 @@
 #include "quant_core.h"
 #include "lcu_layout.h"
 #include "intra_core.h"
+#include "tile_grid.h"
 
 using namespace kvzhip;
 
@@ -71,12 +72,16 @@ struct tu_pos {
   int mode, scan;
 };
 
+// the rectangle a TU takes its neighbours from, in luma pixels: the picture, or the TU's tile (state->tile->frame of the reference)
+struct tile_rect { int x0, y0, x1, y1; };
+
 struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { return p[(i / n) * ld + (i % n)]; } };
 
-// One leaf TU, N wide, by the whole wave.  Called under wave-uniform conditions only.
-template <int N>
-__device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS], u8 *s_ext,
-                                        u8 *s_pred, i16 *ta, i16 *tb, i16 *tq)
+// One leaf TU, N wide, by the whole wave.  Called under wave-uniform conditions only.  TILES: tr stands for the picture in everything
+// about the TU's neighbours; without it tr is not read, and the code is compiled from the expressions it always had.
+template <int N, bool TILES>
+__device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
+                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq)
 {
   constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5, LD = lds_tile_ld(N), W4 = N / 4;
   const int lane = threadIdx.x, row = lane & (N - 1);
@@ -88,18 +93,21 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
   __syncthreads();
   if (lane < 2 * N) {
     const int ux = (t.lx & 63) >> 2, uy = (t.ly & 63) >> 2;
-    const bool has_left = t.lx > 0, has_top = t.ly > 0;
+    bool has_left = t.lx > 0, has_top = t.ly > 0;
+    if constexpr (TILES) { has_left = t.lx > tr.x0; has_top = t.ly > tr.y0; }
     u8 left, top;
     if (has_left) {
       int avail = intra_coded_left(ux, uy) >> sh;
-      avail = min(avail, min(2 * N, (a.height - t.ly) >> sh));
+      if constexpr (TILES) avail = min(avail, min(2 * N, (tr.y1 - t.ly) >> sh));
+      else avail = min(avail, min(2 * N, (a.height - t.ly) >> sh));
       left = tile[tpx(t.tx - 1, t.ty + min(lane, avail - 1))];
     } else {
       left = has_top ? tile[tpx(t.tx, t.ty - 1)] : 128;
     }
     if (has_top) {
       int avail = intra_coded_above(ux, uy) >> sh;
-      avail = min(avail, min(2 * N, (a.width - t.lx) >> sh));
+      if constexpr (TILES) avail = min(avail, min(2 * N, (tr.x1 - t.lx) >> sh));
+      else avail = min(avail, min(2 * N, (a.width - t.lx) >> sh));
       top = tile[tpx(t.tx + min(lane, avail - 1), t.ty - 1)];
     } else {
       top = has_left ? tile[tpx(t.tx - 1, t.ty)] : 128;
@@ -287,13 +295,21 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
 // code the compiler emits for the first, and the one-QP kernel is to stay as it was measured.
 struct lcu_qp_source { const int8_t *lcu_qp; int slice_is_intra, signhide; };
 __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { return q; }
+// A tiled picture (kvz_hip_intra_recon_frame_tiles) is a second trailing argument after the QP source: the grid, and the QP of
+// every LCU where the source's array is NULL.  Again an instantiation of its own in a translation unit of its own
+// (intra_recon_tiles.hip); the two above compile to the code they were.
+struct tile_source { kvz_hip_tile_grid grid; int qp; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &) { return q; }
+__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t) { return t; }
 template <bool LCU_QP> struct lcu_sets {};                                   // what a workgroup derives from its LCU's QP: nothing with one QP per call,
 template <> struct lcu_sets<true> { quant_consts k[4]; };                    // else the sets of the four sizes, [log2 N - 2]
 
 // z-order index -> coordinate: the even bits of i
 __device__ __forceinline__ int compact4(int i) { i &= 0x55; i = (i | (i >> 1)) & 0x33; return (i | (i >> 2)) & 0x0f; }
 
-// wave t of the picture: grid (lcus_y, planes), LCU (t - 2 ly, ly).  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
+// wave t of the picture: grid (lcus_y, planes), LCU (t - 2 ly, ly).  Tiled: grid (lcus_y * cols, planes), a workgroup per LCU row and
+// tile column, LCU (x0 + t - 2 (ly - y0), ly) of the tile that begins at LCU (x0, y0): the waves of all tiles share the launches, and the
+// rectangle that stands for the picture in everything about neighbours is the tile.  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
 // the lanes beyond a TU's N rows repeat row lane % N, which is the same value to the same LDS address only while all of them are
 // one wave in lockstep; with a second wave the read-modify-write of ta / tq would race.
 constexpr int WG = 64;
@@ -301,7 +317,7 @@ static_assert(WG == 64, "one wave per workgroup: see intra_tu");
 template <typename... PER_LCU>
 __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int t, PER_LCU... per_lcu)
 {
-  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0;
+  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) == 2;
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -312,8 +328,22 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   __shared__ u8 s_intra[256];                                                // SCU (raster) belongs to an intra CU of this call
 
   const int lane = threadIdx.x, plane = blockIdx.y, sh = plane ? 1 : 0;
-  const int lcu_y = blockIdx.x, lcu_x = t - 2 * lcu_y;
-  if (lcu_x < 0 || lcu_x >= a.lcus_x) return;
+  int lcu_y = blockIdx.x, lcu_x = t - 2 * lcu_y;
+  tile_rect tr;                                                              // read with tiles only
+  if constexpr (TILES) {
+    // wave-uniform: scalar loads of the grid, scalar compares and selects
+    const kvz_hip_tile_grid &g = tiles_of(per_lcu...).grid;
+    const int cols = g.cols, col = (int)blockIdx.x % cols;
+    int cx0, cx1, ry0, ry1;
+    lcu_y = (int)blockIdx.x / cols;
+    tile_span_at(g.col_bd, col, cx0, cx1);
+    tile_span_of(g.row_bd, g.rows, lcu_y, ry0, ry1);
+    lcu_x = cx0 + t - 2 * (lcu_y - ry0);
+    if (lcu_x < cx0 || lcu_x >= cx1) return;
+    tr = { 64 * cx0, 64 * ry0, min(64 * cx1, a.width), min(64 * ry1, a.height) };
+  } else {
+    if (lcu_x < 0 || lcu_x >= a.lcus_x) return;
+  }
   const int X0 = 64 * lcu_x, Y0 = 64 * lcu_y;
 
   bool any = false;
@@ -329,8 +359,12 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   if (!__syncthreads_or(any)) return;
 
   // ---- the tile: rows -1 .. th - 1 as dwords (the plane's width and the tile's extent are multiples of 4), then the column left ----
-  const int T = 64 >> sh, pw = a.width >> sh, ph = a.height >> sh, x0 = X0 >> sh, y0 = Y0 >> sh;
-  const int tw = min(T, pw - x0), th = min(T, ph - y0), aw = y0 > 0 ? min(T + T / 2, pw - x0) : 0;
+  // nothing outside the rectangle is read: with tiles the LCUs beyond it are being written by other workgroups of this launch
+  const int T = 64 >> sh;
+  int pw = a.width >> sh, ph = a.height >> sh, qx = 0, qy = 0;
+  const int x0 = X0 >> sh, y0 = Y0 >> sh;
+  if constexpr (TILES) { pw = tr.x1 >> sh; ph = tr.y1 >> sh; qx = tr.x0 >> sh; qy = tr.y0 >> sh; }
+  const int tw = min(T, pw - x0), th = min(T, ph - y0), aw = y0 > qy ? min(T + T / 2, pw - x0) : 0;
   u8 *rec = a.rec[plane];
   const size_t stride = a.rec_stride[plane];
   constexpr int CW = (64 + 32) / 4;
@@ -342,15 +376,17 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
       *(u32 *)(tile + tpx(c4, r)) = v;
     }
   }
-  if (x0 > 0)
+  if (x0 > qx)
     for (int r = lane - 1; r < th; r += 64)
-      if (r >= 0 || y0 > 0) tile[tpx(-1, r)] = rec[(size_t)(y0 + r) * stride + x0 - 1];
+      if (r >= 0 || y0 > qy) tile[tpx(-1, r)] = rec[(size_t)(y0 + r) * stride + x0 - 1];
   __syncthreads();
 
   lcu_sets<LCU_QP> own;                                                      // the LCU's own sets, [log2 N - 2]
   if constexpr (LCU_QP) {
     const lcu_qp_source &q = only(per_lcu...);
-    const int qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]));
+    int qp;
+    if constexpr (TILES) qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(q.lcu_qp ? (int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x] : tiles_of(per_lcu...).qp)));
+    else qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, q.slice_is_intra, q.signhide);
   }
@@ -381,10 +417,10 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
     p.tx = (p.lx - X0) >> sh; p.ty = (p.ly - Y0) >> sh;
     const quant_consts *kk = a.k[plane ? 1 : 0];
     if constexpr (LCU_QP) kk = own.k;
-    if (n == 32) intra_tu<32>(a, p, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else if (n == 16) intra_tu<16>(a, p, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else if (n == 8) intra_tu<8>(a, p, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else intra_tu<4>(a, p, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    if (n == 32) intra_tu<32, TILES>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else if (n == 16) intra_tu<16, TILES>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else if (n == 8) intra_tu<8, TILES>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else intra_tu<4, TILES>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq);
   }
 
   // ---- the pixels of the intra CUs go back: a row of an SCU (4 luma, 2 chroma pixels) per item, 16 SCUs of a row side by side ----
@@ -399,7 +435,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   }
 }
 
-// both entries; per_lcu: nothing (one QP per call, params->qp) or one lcu_qp_source
+// the three entries; per_lcu: nothing (one QP per call, params->qp), one lcu_qp_source, or that and a tile_source
 template <typename... PER_LCU>
 int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                 kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes, kvz_hip_coeff *coeff_y,
@@ -439,9 +475,15 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
     KVZ_CHECK_LAUNCH("intra_recon_init_kernel");
   }
   // the launch sequence depends on width, height and chroma alone
-  const int waves = a.lcus_x + 2 * (lcus_y - 1);
+  int waves = a.lcus_x + 2 * (lcus_y - 1), groups = lcus_y;
+  if constexpr (sizeof...(PER_LCU) == 2) {
+    // and on the grid: the largest tile's count of waves, a workgroup per LCU row and tile column
+    const kvz_hip_tile_grid &g = tiles_of(per_lcu...).grid;
+    waves = tile_grid_waves(g);
+    groups = lcus_y * g.cols;
+  }
   for (int t = 0; t < waves; ++t) {
-    hipLaunchKernelGGL(intra_recon_wave_kernel<PER_LCU...>, dim3((unsigned)lcus_y, chroma ? 3u : 1u), dim3(WG), 0, st, a, t, per_lcu...);
+    hipLaunchKernelGGL(intra_recon_wave_kernel<PER_LCU...>, dim3((unsigned)groups, chroma ? 3u : 1u), dim3(WG), 0, st, a, t, per_lcu...);
     KVZ_CHECK_LAUNCH("intra_recon_wave_kernel");
   }
   return KVZ_HIP_OK;

@@ -1,0 +1,113 @@
+// tile_grid.h -- kvz_hip_tile_grid on the host and on the device, for the four *_tiles entries of the picture chain
+// (intra_recon_tiles.hip, cu_qp_tiles.hip, deblock_tiles.hip, sao_frame_tiles.hip).
+//
+// The grid travels to every kernel by value (392 bytes of kernel arguments).  The lookups below index it with constants only --
+// the loops are fully unrolled and select -- because a dynamically indexed kernel argument array is copied to scratch; with a
+// wave-uniform LCU position they are scalar loads, compares and selects.
+#pragma once
+
+#include "kvz_hip_internal.h"
+
+namespace {
+
+static_assert(sizeof(kvz_hip_tile_grid) == 392 && KVZ_HIP_MAX_TILES_PER_DIM == 48, "layout documented in kvz_hip.h");
+
+constexpr int TILE_MAX = KVZ_HIP_MAX_TILES_PER_DIM - 1;      // the largest count of tile columns or rows
+
+inline bool tile_bd_ok(int n, const int32_t *bd, int lcus)
+{
+  if (n < 1 || n > TILE_MAX || bd[0] != 0 || bd[n] != lcus) return false;
+  for (int i = 0; i < n; ++i)
+    if (bd[i + 1] <= bd[i]) return false;
+  return true;
+}
+
+// grid == NULL: one tile, the whole picture.  -> false for a malformed grid (tiles_col_bd / tiles_row_bd, encoder.c:472-481)
+inline bool tile_grid_make(const kvz_hip_tile_grid *grid, int width, int height, kvz_hip_tile_grid *out)
+{
+  const int lcus_x = (width + 63) >> 6, lcus_y = (height + 63) >> 6;
+  __builtin_memset(out, 0, sizeof *out);
+  if (!grid) {
+    out->cols = out->rows = 1;
+    out->col_bd[1] = lcus_x;
+    out->row_bd[1] = lcus_y;
+    return true;
+  }
+  if (!tile_bd_ok(grid->cols, grid->col_bd, lcus_x) || !tile_bd_ok(grid->rows, grid->row_bd, lcus_y)) return false;
+  // the entries beyond the counts are not the caller's to define: they travel as zeros
+  out->cols = grid->cols;
+  out->rows = grid->rows;
+  for (int i = 0; i <= grid->cols; ++i) out->col_bd[i] = grid->col_bd[i];
+  for (int i = 0; i <= grid->rows; ++i) out->row_bd[i] = grid->row_bd[i];
+  return true;
+}
+
+// the largest tile's wavefront count w + 2 (h - 1): the dependent launches of the intra stage
+inline int tile_grid_waves(const kvz_hip_tile_grid &g)
+{
+  int w = 0, h = 0;
+  for (int i = 0; i < g.cols; ++i) w = g.col_bd[i + 1] - g.col_bd[i] > w ? g.col_bd[i + 1] - g.col_bd[i] : w;
+  for (int i = 0; i < g.rows; ++i) h = g.row_bd[i + 1] - g.row_bd[i] > h ? g.row_bd[i + 1] - g.row_bd[i] : h;
+  return w + 2 * (h - 1);
+}
+
+// The lookups walk the boundaries in two parts: the first TILE_NEAR always, the rest only where the grid has more (a wave-uniform
+// branch on a kernel argument), so that the grids that occur -- a handful of tiles per direction -- cost a handful of compares.
+constexpr int TILE_NEAR = 8;
+
+template <int FROM, int TO>
+__device__ __forceinline__ void tile_span_part(const int32_t (&bd)[KVZ_HIP_MAX_TILES_PER_DIM], int n, int l, int &lo, int &hi)
+{
+#pragma unroll
+  for (int i = FROM; i <= TO; ++i) {
+    const int b = bd[i];
+    if (i <= n) {
+      if (b <= l) lo = b;
+      else hi = min(hi, b);
+    }
+  }
+}
+
+// the boundaries [lo, hi) of the tile column (row) that holds LCU column (row) l, in LCUs
+__device__ __forceinline__ void tile_span_of(const int32_t (&bd)[KVZ_HIP_MAX_TILES_PER_DIM], int n, int l, int &lo, int &hi)
+{
+  lo = 0;
+  hi = 0x7fffffff;
+  tile_span_part<1, TILE_NEAR>(bd, n, l, lo, hi);
+  if (n > TILE_NEAR) tile_span_part<TILE_NEAR + 1, TILE_MAX>(bd, n, l, lo, hi);
+}
+
+template <int FROM, int TO>
+__device__ __forceinline__ void tile_at_part(const int32_t (&bd)[KVZ_HIP_MAX_TILES_PER_DIM], int t, int &lo, int &hi)
+{
+#pragma unroll
+  for (int i = FROM; i <= TO; ++i)
+    if (i == t) { lo = bd[i]; hi = bd[i + 1]; }
+}
+
+// the boundaries of tile column (row) t itself
+__device__ __forceinline__ void tile_span_at(const int32_t (&bd)[KVZ_HIP_MAX_TILES_PER_DIM], int t, int &lo, int &hi)
+{
+  lo = hi = 0;
+  if (t < TILE_NEAR) tile_at_part<0, TILE_NEAR - 1>(bd, t, lo, hi);
+  else tile_at_part<TILE_NEAR, TILE_MAX - 1>(bd, t, lo, hi);
+}
+
+template <int FROM, int TO>
+__device__ __forceinline__ bool tile_starts_part(const int32_t (&bd)[KVZ_HIP_MAX_TILES_PER_DIM], int n, int l)
+{
+  bool hit = false;
+#pragma unroll
+  for (int i = FROM; i <= TO; ++i) hit = hit || (i <= n && bd[i] == l);
+  return hit;
+}
+
+// LCU column (row) l is where a tile column (row) other than the first begins, or where the last one ends
+__device__ __forceinline__ bool tile_starts_at(const int32_t (&bd)[KVZ_HIP_MAX_TILES_PER_DIM], int n, int l)
+{
+  bool hit = tile_starts_part<1, TILE_NEAR>(bd, n, l);
+  if (n > TILE_NEAR) hit = hit || tile_starts_part<TILE_NEAR + 1, TILE_MAX>(bd, n, l);
+  return hit;
+}
+
+}  // namespace

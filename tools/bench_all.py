@@ -236,10 +236,33 @@ def main():
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp" for o in args.only.split(",")):
         inter_residual_rows(L, st, dev, max(args.rounds, 5))
-    if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p" for o in args.only.split(",")):
+    if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p sao_frame_1080p_tiles4x2" for o in args.only.split(",")):
         sao_frame_rows(L, st, dev, max(args.rounds, 5))
-    if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all intra_recon_frame_1080p_mixed_lcu_qp cu_qp_frame_1080p" for o in args.only.split(",")):
+    if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all intra_recon_frame_1080p_mixed_lcu_qp cu_qp_frame_1080p "
+                            "intra_recon_frame_1080p_mixed_tiles4x2 intra_recon_frame_1080p_all_tiles4x2 cu_qp_frame_1080p_tiles4x2" for o in args.only.split(",")):
         intra_recon_rows(L, st, dev, max(args.rounds, 5))
+    if not args.only or any(o in "deblock_frame_1080p_tiles4x2" for o in args.only.split(",")):
+        deblock_tiles_rows(L, st, max(args.rounds, 5), (dby, dbu, dbv, dbc, dbp, DW, DH))
+
+
+def deblock_tiles_rows(L, st, rounds, picture, iters=20):
+    """kvz_hip_deblock_frame_tiles with 4 x 2 uniform tiles on the picture of the deblock_frame_1080p row, interleaved round by round with
+    the untiled entry; medians and min..max over the rounds (two launches each)."""
+    import numpy as np
+    from kvazaar_amd import api
+    y, u, v, cus, prm, W, H = picture
+    grid = api.uniform_tile_grid(W, H, 4, 2)
+    fns = {"deblock_frame_1080p": lambda: L.kvz_hip_deblock_frame(y.data_ptr(), W, u.data_ptr(), v.data_ptr(), W // 2, W, H, cus.data_ptr(), prm.ctypes.data, st),
+           "deblock_frame_1080p_tiles4x2": lambda: L.kvz_hip_deblock_frame_tiles(y.data_ptr(), W, u.data_ptr(), v.data_ptr(), W // 2, W, H, cus.data_ptr(),
+                                                                                 grid.ctypes.data, prm.ctypes.data, st)}
+    t = {k: [] for k in fns}
+    for _ in range(rounds):
+        for k, fn in fns.items():
+            t[k].append(timed(L, st, lambda fn=fn, k=k: _lib.check(fn(), k), iters=iters, warm=3))
+    print("%-30s %10s %12s %8s %16s" % ("kernel", "launches", "frames/s", "ms", "min..max ms"))
+    for k in fns:
+        ms = float(np.median(t[k]))
+        print("%-30s %10d %12.1f %8.4f %7.4f..%7.4f" % (k, 2, 1e3 / ms, ms, min(t[k]), max(t[k])))
 
 
 def intra_recon_rows(L, st, dev, rounds, iters=3):
@@ -248,13 +271,20 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
     and tr_depth as tests/intra_recon_cases.py sets them.  The stage is a chain of dependent launches (one per wavefront of LCUs) and
     of dependent TUs inside an LCU, so the figure is a latency, not a throughput: ms per picture, medians (and min..max) over the
     rounds.  On the mixed picture the same call with a QP per LCU (kvz_hip_intra_recon_frame_qp, QPs 22..42 drawn per LCU) and the QP
-    map from its flags (kvz_hip_cu_qp_frame) are timed in the same rounds, interleaved with the one-QP row."""
+    map from its flags (kvz_hip_cu_qp_frame) are timed in the same rounds, interleaved with the one-QP row.  Both pictures also go
+    through kvz_hip_intra_recon_frame_tiles with 4 x 2 uniform tiles (rows *_tiles4x2; the mixed picture's QP map through
+    kvz_hip_cu_qp_frame_tiles as well), interleaved with their untiled rows; `launches` is the number of dependent wavefront launches."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import intra_recon_cases as XC
     from kvazaar_amd import api
     W, H = 1920, 1080
-    print("%-38s %8s %10s %12s %10s %18s" % ("kernel", "intra %", "TUs", "frames/s", "ms", "min..max ms"))
+    print("%-38s %8s %10s %9s %12s %10s %18s" % ("kernel", "intra %", "TUs", "launches", "frames/s", "ms", "min..max ms"))
+    grid = api.uniform_tile_grid(W, H, 4, 2)
+    waves = lambda bx, by: max(np.diff(bx)) + 2 * (max(np.diff(by)) - 1)
+    n_launch = {False: waves([0, (W + 63) // 64], [0, (H + 63) // 64]), True: waves(grid["col_bd"][0, :5], grid["row_bd"][0, :3])}
+    tprm = np.zeros(1, dtype=api.CU_QP_TILES_PARAMS)
+    tprm["start_qp"] = 32
     for name, share in (("intra_recon_frame_1080p_mixed", 0.1), ("intra_recon_frame_1080p_all", 1.0)):
         cus, _, modes = XC.make_map(W, H, 51, intra_share=share, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
         src, rec = XC.make_planes(cus, 52)
@@ -283,7 +313,18 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
 
         def qp_map():                                    # cbf_d: the flags of the intra CUs as the call before left them, 0 elsewhere
             return L.kvz_hip_cu_qp_frame(cus_d.data_ptr(), cbf_d.data_ptr(), W, H, lcu_qp_d.data_ptr(), last_d.data_ptr(), qprm.ctypes.data, st)
-        rows = [(name, frame, iters)] + ([(name + "_lcu_qp", frame_qp, iters), ("cu_qp_frame_1080p", qp_map, 20)] if share < 1.0 else [])
+
+        def frame_tiles():                               # one QP per call, as `frame`
+            return L.kvz_hip_intra_recon_frame_tiles(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
+                                                     cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
+                                                     cbf_d.data_ptr(), cost_d.data_ptr(), None, grid.ctypes.data, prm.ctypes.data, st)
+
+        def qp_map_tiles():
+            return L.kvz_hip_cu_qp_frame_tiles(cus_d.data_ptr(), cbf_d.data_ptr(), W, H, lcu_qp_d.data_ptr(), last_d.data_ptr(), grid.ctypes.data,
+                                               tprm.ctypes.data, st)
+        rows = [(name, frame, iters), (name + "_tiles4x2", frame_tiles, iters)]
+        if share < 1.0:
+            rows += [(name + "_lcu_qp", frame_qp, iters), ("cu_qp_frame_1080p", qp_map, 20), ("cu_qp_frame_1080p_tiles4x2", qp_map_tiles, 20)]
         cbf_d.zero_()
         torch.cuda.synchronize()
         t = {r[0]: [] for r in rows}
@@ -293,8 +334,9 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
         m, _, _ = XC.intra_mask(cus, W, H)
         for (rname, fn, it) in rows:
             ms = float(np.median(t[rname]))
-            print("%-38s %8.1f %10d %12.1f %10.3f %18s" % (rname, 100 * m.mean(), len(XC.walk_tus(cus, modes, W, H)), 1e3 / ms, ms,
-                                                           "%.3f..%.3f" % (min(t[rname]), max(t[rname]))))
+            launches = 3 if rname.startswith("cu_qp") else n_launch[rname.endswith("_tiles4x2")]
+            print("%-38s %8.1f %10d %9d %12.1f %10.3f %18s" % (rname, 100 * m.mean(), len(XC.walk_tus(cus, modes, W, H)), launches, 1e3 / ms, ms,
+                                                               "%.3f..%.3f" % (min(t[rname]), max(t[rname]))))
 
 
 def inter_recon_rows(L, st, dev, rounds, frames=64):
@@ -530,6 +572,11 @@ def sao_frame_rows(L, st, dev, rounds, iters=20):
     def new_frame():
         return L.kvz_hip_sao_frame(rec[0].data_ptr(), W, rec[1].data_ptr(), rec[2].data_ptr(), W // 2, dst[0].data_ptr(), W, dst[1].data_ptr(),
                                    dst[2].data_ptr(), W // 2, W, H, luma_d.data_ptr(), chro_d.data_ptr(), 1, st)
+    grid = api.uniform_tile_grid(W, H, 4, 2)
+
+    def new_frame_tiles():
+        return L.kvz_hip_sao_frame_tiles(rec[0].data_ptr(), W, rec[1].data_ptr(), rec[2].data_ptr(), W // 2, dst[0].data_ptr(), W, dst[1].data_ptr(),
+                                         dst[2].data_ptr(), W // 2, W, H, luma_d.data_ptr(), chro_d.data_ptr(), 1, grid.ctypes.data, st)
     # ---- the block-list way ----
     blit, groups, keep = [], [], []
     for color in range(3):
@@ -594,8 +641,8 @@ def sao_frame_rows(L, st, dev, rounds, iters=20):
     _lib.check(old_frame(), "block-list reconstruction")
     _lib.check(L.kvz_hip_stream_sync(st), "sync")
     assert all(torch.equal(a, b) for a, b in zip(want, dst)), "sao_frame differs from the block-list reconstruction"
-    t = {k: [] for k in ("new_stats", "old_stats", "new_frame", "old_frame")}
-    fns = {"new_stats": new_stats, "old_stats": old_stats, "new_frame": new_frame, "old_frame": old_frame}
+    t = {k: [] for k in ("new_stats", "old_stats", "new_frame", "old_frame", "new_frame_tiles")}
+    fns = {"new_stats": new_stats, "old_stats": old_stats, "new_frame": new_frame, "old_frame": old_frame, "new_frame_tiles": new_frame_tiles}
     for _ in range(rounds):
         for k, fn in fns.items():
             t[k].append(timed(L, st, lambda fn=fn, k=k: _lib.check(fn(), k), iters=iters, warm=3))
@@ -606,6 +653,9 @@ def sao_frame_rows(L, st, dev, rounds, iters=20):
         ms, ms_o = float(np.median(t[new])), float(np.median(t[old]))
         print("%-28s %10d %12.1f %10.1f %8.4f %7.4f..%7.4f %8.2f" % (name, n_new, 1e3 / ms, nbytes / ms / 1e6, ms, min(t[new]), max(t[new]), ms_o / ms))
         print("%-28s %10d %12.1f %10.1f %8.4f %7.4f..%7.4f %8s" % (name + "(blocks)", n_old, 1e3 / ms_o, nbytes / ms_o / 1e6, ms_o, min(t[old]), max(t[old]), "-"))
+    ms = float(np.median(t["new_frame_tiles"]))                  # 4 x 2 uniform tiles, in the same rounds as the untiled row
+    print("%-28s %10d %12.1f %10.1f %8.4f %7.4f..%7.4f %8s" % ("sao_frame_1080p_tiles4x2", 1, 1e3 / ms, nbytes / ms / 1e6, ms, min(t["new_frame_tiles"]),
+                                                             max(t["new_frame_tiles"]), "-"))
 
 
 if __name__ == "__main__":

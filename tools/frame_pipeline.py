@@ -13,11 +13,13 @@ once), so launch overhead, partial waves and tails count the way they do in an e
 tools/bench_all.py, whose batches are sized to hide them.  It is a measurement of the kernels on a
 frame-sized workload, not of an encoder: the mode decision around them is not here.
 
-  python tools/frame_pipeline.py [--frames 200] [--lcu-qp]
+  python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR]
 
 --lcu-qp: the picture chain of a frame whose QP changes per LCU (rate control, --roi): intra reconstruction through
 kvz_hip_intra_recon_frame_qp with a QP array, then kvz_hip_cu_qp_frame (the QP map and the per-LCU predictor), and deblocking
 with per_cu_qp = 1.
+--tiles CxR: the picture is cut into C x R uniform tiles (the reference's spacing): the stages of the picture chain that depend on
+tiles go through their *_tiles entries -- intra reconstruction, the QP map (with --lcu-qp), deblocking and the SAO reconstruction.
 """
 import argparse
 import ctypes as C
@@ -36,7 +38,7 @@ from kvazaar_amd._lib import QuantParams  # noqa: E402
 W, H = 1920, 1080
 
 
-def build_stages(L, dev, lcu_qp=False):
+def build_stages(L, dev, lcu_qp=False, tiles=None):
     """-> {stage: [(name, units, launch(stream))]}, plus the tensors kept alive"""
     g = torch.Generator(device=dev); g.manual_seed(7)
     keep = []
@@ -112,6 +114,8 @@ def build_stages(L, dev, lcu_qp=False):
     ir_tab = api.ref_picture_table([(ir_src[0].data_ptr(), ir_src[1].data_ptr(), ir_src[2].data_ptr(), W, W // 2)], W, H)
     ir_prm = api.inter_residual_params(27, 0, 0, 1)
     keep += [ir_src, ir_rec, ir_cus_d, ir_modes_d, ir_co, ir_tab, ir_prm]
+    grid = api.uniform_tile_grid(W, H, tiles[0], tiles[1]) if tiles else None      # 1080 and the 1088 coded rows are the same 17 LCU rows
+    keep.append(grid)
     if lcu_qp:
         # a QP per LCU: the flags go to an array (cleared once), the QP map is written from it after the intra stage
         ir_qp = up(np.random.default_rng(35).integers(22, 43, api.lcu_count(W, H)).astype(np.int8))
@@ -120,6 +124,18 @@ def build_stages(L, dev, lcu_qp=False):
         ir_qprm = np.zeros(1, dtype=api.CU_QP_PARAMS)
         ir_qprm["start_qp"] = 27
         keep += [ir_qp, ir_cbf, ir_last, ir_qprm]
+    if tiles:
+        stages["tu"].append(("intra_recon_frame_tiles", 1, lambda s: L.kvz_hip_intra_recon_frame_tiles(
+            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+            ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
+            ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data, ir_prm.ctypes.data, s)))
+        if lcu_qp:
+            ir_tprm = np.zeros(1, dtype=api.CU_QP_TILES_PARAMS)
+            ir_tprm["start_qp"] = 27
+            keep.append(ir_tprm)
+            stages["tu"].append(("cu_qp_frame_tiles", 1, lambda s: L.kvz_hip_cu_qp_frame_tiles(
+                ir_cus_d.data_ptr(), ir_cbf.data_ptr(), W, H, ir_qp.data_ptr(), ir_last.data_ptr(), grid.ctypes.data, ir_tprm.ctypes.data, s)))
+    elif lcu_qp:
         stages["tu"].append(("intra_recon_frame_qp", 1, lambda s: L.kvz_hip_intra_recon_frame_qp(
             ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
             ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr(), None, ir_qp.data_ptr(), ir_prm.ctypes.data, s)))
@@ -167,8 +183,12 @@ def build_stages(L, dev, lcu_qp=False):
     dbc = torch.from_numpy(np.tile(tcus, reps)[:DH // 4, :W // 4].copy().view(np.uint8)).to(dev)
     dbp = deblock_params(qp=36, per_cu_qp=1 if lcu_qp else 0)          # per_cu_qp: the filter reads the qp field of the records
     keep += [dby, dbu, dbv, dbc, dbp]
-    stages["sao"].insert(0, ("deblock_frame", 1, lambda s: L.kvz_hip_deblock_frame(
-        dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, W, DH, dbc.data_ptr(), dbp.ctypes.data, s)))
+    if tiles:
+        stages["sao"].insert(0, ("deblock_frame_tiles", 1, lambda s: L.kvz_hip_deblock_frame_tiles(
+            dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, W, DH, dbc.data_ptr(), grid.ctypes.data, dbp.ctypes.data, s)))
+    else:
+        stages["sao"].insert(0, ("deblock_frame", 1, lambda s: L.kvz_hip_deblock_frame(
+            dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, W, DH, dbc.data_ptr(), dbp.ctypes.data, s)))
     # SAO of the deblocked picture, the two whole-picture calls: statistics + candidates of every LCU and plane, then the
     # reconstruction into the next frame's reference (records: every LCU an edge or band record, as after a decision)
     from patterns import sao_records
@@ -184,9 +204,14 @@ def build_stages(L, dev, lcu_qp=False):
     keep += [so_src, so_tab, so_stats, so_cands, so_luma, so_chroma, so_dst]
     stages["sao"].insert(1, ("sao_stats_frame", 3 * n_lcu, lambda s: L.kvz_hip_sao_stats_frame(
         so_tab.ctypes.data, dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, 1, so_stats.data_ptr(), so_cands.data_ptr(), s)))
-    stages["sao"].insert(2, ("sao_frame", 1, lambda s: L.kvz_hip_sao_frame(
-        dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, so_dst[0].data_ptr(), W, so_dst[1].data_ptr(), so_dst[2].data_ptr(), W // 2,
-        W, DH, so_luma.data_ptr(), so_chroma.data_ptr(), 1, s)))
+    if tiles:
+        stages["sao"].insert(2, ("sao_frame_tiles", 1, lambda s: L.kvz_hip_sao_frame_tiles(
+            dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, so_dst[0].data_ptr(), W, so_dst[1].data_ptr(), so_dst[2].data_ptr(), W // 2,
+            W, DH, so_luma.data_ptr(), so_chroma.data_ptr(), 1, grid.ctypes.data, s)))
+    else:
+        stages["sao"].insert(2, ("sao_frame", 1, lambda s: L.kvz_hip_sao_frame(
+            dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, so_dst[0].data_ptr(), W, so_dst[1].data_ptr(), so_dst[2].data_ptr(), W // 2,
+            W, DH, so_luma.data_ptr(), so_chroma.data_ptr(), 1, s)))
     return stages, keep
 
 
@@ -240,7 +265,10 @@ def main():
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--tune", default="", help="key=value[,key=value...] passed to kvz_hip_set_tuning")
     ap.add_argument("--lcu-qp", action="store_true", help="a QP per LCU: intra_recon_frame_qp, cu_qp_frame, deblocking with per_cu_qp = 1")
+    ap.add_argument("--tiles", default="", metavar="CxR", help="C x R uniform tiles: the *_tiles entries of intra, QP map, deblocking and SAO")
     args = ap.parse_args()
+    tiles = tuple(int(v) for v in args.tiles.lower().split("x")) if args.tiles else None
+    assert tiles is None or len(tiles) == 2
     dev = torch.device("cuda", 0)
     L = _lib.init(0)
     for kv in filter(None, args.tune.split(",")):
@@ -249,7 +277,7 @@ def main():
     s = L.kvz_hip_stream_create()
     side = [L.kvz_hip_stream_create() for _ in range(7)]
     events = [L.kvz_hip_event_create() for _ in range(8)]
-    stages, keep = build_stages(L, dev, args.lcu_qp)
+    stages, keep = build_stages(L, dev, args.lcu_qp, tiles)
     torch.cuda.synchronize()
     n_launch = sum(len(v) for v in stages.values())
 
@@ -270,8 +298,13 @@ def main():
             L.kvz_hip_event_destroy(e0); L.kvz_hip_event_destroy(e1)
             total += ms.value / 20
             print("%-34s %9d %10.1f" % (name, units, ms.value / 20 * 1e3))
+    waves = (W + 63) // 64 + 2 * ((H + 63) // 64 - 1)
+    if tiles:
+        from kvazaar_amd import api
+        g = api.uniform_tile_grid(W, H, tiles[0], tiles[1])
+        waves = int(max(np.diff(g["col_bd"][0, :tiles[0] + 1])) + 2 * (max(np.diff(g["row_bd"][0, :tiles[1] + 1])) - 1))
     print("%-34s %9s %10.1f   (%d calls; the intra reconstruction is %d kernel launches of its own)" % ("sum of the entries", "", total * 1e3, n_launch,
-                                                                                               1 + (W + 63) // 64 + 2 * ((H + 63) // 64 - 1)))
+                                                                                               1 + waves))
 
     results = {}
     results["eager"] = run(L, s, args.frames, lambda: enqueue_serial(stages, s))
