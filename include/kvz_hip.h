@@ -911,7 +911,7 @@ typedef struct {
   int32_t qp;               /* state->qp: one QP per call */
   int32_t slice_is_intra;   /* state->frame->slicetype == KVZ_SLICE_I */
   int32_t signhide;         /* encoder->cfg.signhide_enable */
-  int32_t scaling_list;     /* must be 0: flat lists only */
+  int32_t scaling_list;     /* 0: flat lists; non-zero with the _sl entries only, which take the tables (below) */
   int32_t chroma;           /* 0: 4:0:0 (U / V pointers unused), 1: 4:2:0 */
   int32_t reserved;
 } kvz_hip_inter_residual_params;   /* 24 bytes; the first four fields are those of kvz_hip_quant_params */
@@ -937,8 +937,8 @@ typedef struct {
  *   TUs are half as wide; with 4x4 luma TUs the chroma of the 8x8 area is one 4x4 TU per plane (transform.c:293-313).
  * Per TU: kvz_quantize_residual, rdoq off (quant-generic.c:180-273), cu_is_intra = 0, diagonal scan (kvz_get_scan_order of
  *   an inter CU), no transform skip; bit-exact with the generic strategy at bit depth 8.  OUT OF SCOPE: lossless coding,
- *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID) and per-CU QP (the qp field of
- *   the records is not read; a QP per LCU: kvz_hip_inter_residual_frame_qp below).  Intra CUs need their neighbours' reconstruction and are not handled, as in
+ *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID; kvz_hip_inter_residual_frame_sl
+ *   below takes them) and per-CU QP (the qp field of the records is not read; a QP per LCU: kvz_hip_inter_residual_frame_qp below).  Intra CUs need their neighbours' reconstruction and are not handled, as in
  *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.
  * Outputs:
  *   rec planes: the reconstruction inside the inter CUs (a TU without coefficients keeps its prediction).
@@ -1234,6 +1234,60 @@ KVZ_HIP_API int kvz_hip_sao_frame_tiles(const kvz_hip_pixel *rec_y, uint32_t str
                                         kvz_hip_pixel *dst_u, kvz_hip_pixel *dst_v, uint32_t dst_stride_c, int width, int height,
                                         const kvz_hip_sao_info *sao_luma, const kvz_hip_sao_info *sao_chroma, int chroma,
                                         const kvz_hip_tile_grid *grid, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Scaling lists in the picture chain: residual coding and intra recon */
+/*   reference: scaling_list_t (scalinglist.h:34-41) as                */
+/*   kvz_scalinglist_process leaves it (scalinglist.c:277-411); its    */
+/*   use in kvz_quant (quant-generic.c:40-67, :76-77) and kvz_dequant  */
+/*   (quant-generic.c:283-320); --scaling-list, --cqmfile              */
+/* ------------------------------------------------------------------ */
+/* The processed lists of scaling_list_t (scalinglist.h:34-41) as two dense DEVICE arrays of int32, 16-byte aligned:
+ * table (size_id, list, rem) -- size_id = log2 N - 2 in 0..3, list 0..5 (0-2 intra Y/U/V, 3-5 inter Y/U/V), rem = qp_scaled % 6 --
+ * is the N*N row-major values at  36 * {0, 16, 80, 336}[size_id] + (6 * list + rem) * N * N. */
+#define KVZ_HIP_SL_TABLE_LEN 48960            /* 36 * (16 + 64 + 256 + 1024) values per array, 195840 bytes */
+typedef struct { const int32_t *quant, *dequant; } kvz_hip_scaling_tables;   /* 16 bytes; HOST struct, copied at the call */
+
+/* Host only: needs no device and no kvz_hip_init.  Copies the tables a Kvazaar host holds after kvz_scalinglist_process
+ * (encoder->scaling_list.quant_coeff / .de_quant_coeff, [size_id][list][rem]) into two HOST arrays of KVZ_HIP_SL_TABLE_LEN values
+ * in the layout above; the host uploads them with kvz_hip_memcpy_h2d.
+ * size_id 3: lists 0, 1 and 3 are read and the tables of lists 2, 4 and 5 are filled with zeros -- the reference allocates two 32x32
+ *   lists, aliases [3][3] to [3][1] (scalinglist.c:30, :78-95) and never sets [3][2], [3][4], [3][5], whose pointers are not
+ *   dereferenced here.  No 32x32 chroma TU exists, so no kernel reads the zero tables.
+ * A NULL argument or a NULL source pointer elsewhere returns KVZ_HIP_ERR_INVALID. */
+KVZ_HIP_API int kvz_hip_scaling_tables_pack(const int32_t *const quant_coeff[4][6][6], const int32_t *const de_quant_coeff[4][6][6],
+                                            int32_t *quant_out, int32_t *dequant_out);
+
+/* kvz_hip_inter_residual_frame_qp and kvz_hip_intra_recon_frame_tiles with one more argument, placed before params, for pictures
+ * coded with scaling lists: these two stages are the ones of the chain that quantise.  The host's three lines: pack, upload, pass.
+ * tables == NULL requires params->scaling_list == 0; the call then IS the _qp / _tiles entry, byte for byte (it calls it, and that
+ *   entry names itself in kvz_hip_last_error).  tables != NULL requires params->scaling_list != 0 and both pointers non-NULL and
+ *   16-byte aligned.  Any mismatch returns KVZ_HIP_ERR_INVALID and nothing is written.  The entries above keep refusing
+ *   scaling_list != 0.  lcu_qp == NULL means params->qp everywhere (a negative one is refused); grid == NULL means one tile.
+ * Per TU N wide of plane 0 Y / 1 U / 2 V: qp = the QP of the TU's LCU, clamped into 0..51; qps = kvz_get_scaled_qp(plane, qp);
+ *   rem = qps % 6; size_id = log2 N - 2; base = 0 in the intra entry and 3 in the inter entry -- it follows the CU's type, not the
+ *   slice's.  Quantisation uses list base + (plane ? 1 : 0): the reference quantises V with type 2, U's list (quant-generic.c:223,
+ *   :46-47), with the 64-bit product of quant-generic.c:62 (a list entry below 16 gives factors up to 26214 << 4, and
+ *   |coef| * factor passes 2^32); the sign-hiding pass reads the same table (:76-77).  Dequantisation uses list base + plane (:244,
+ *   :293-295) and takes both branches of :296-311: with shift = log2 N + 3, round and shift right by shift - qps / 6 while
+ *   shift > qps / 6, else clip, shift left by qps / 6 - shift, clip.  q_bits and add are those of flat lists.
+ * In every other respect -- planes and their alignment rules, the CU and transform-tree rules, the coefficient layout, cbf_y /
+ *   cbf_out / costs, tiles, error returns, launches, capture -- they are the entries they extend.  A captured call may be replayed
+ *   after the CONTENTS of the two arrays changed (the pointers are part of the capture).
+ * OUT OF SCOPE: RDOQ and its error_scale, transform skip and lossless coding, parsing --cqmfile, signalling the lists. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                                kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
+                                                uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
+                                                const kvz_hip_scaling_tables *tables,
+                                                const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                             kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                             const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                             kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                             const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
+                                             const kvz_hip_scaling_tables *tables,
+                                             const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */

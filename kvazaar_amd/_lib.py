@@ -57,6 +57,14 @@ class CuQpTilesParams(C.Structure):
     _fields_ = [("start_qp", C.c_int32), ("chain_rows", C.c_int32)]
 
 
+SL_TABLE_LEN = 48960      # KVZ_HIP_SL_TABLE_LEN
+
+
+class ScalingTables(C.Structure):
+    """kvz_hip_scaling_tables"""
+    _fields_ = [("quant", C.c_void_p), ("dequant", C.c_void_p)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -157,6 +165,9 @@ SIGNATURES = {
     "kvz_hip_cu_qp_frame_tiles": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "kvz_hip_deblock_frame_tiles": (_I, [_P, _U, _P, _P, _U, _I, _I, _P, _P, _P, _P]),
     "kvz_hip_sao_frame_tiles": (_I, [_P, _U, _P, _P, _U, _P, _U, _P, _P, _U, _I, _I, _P, _P, _I, _P, _P]),
+    "kvz_hip_scaling_tables_pack": (_I, [_P, _P, _P, _P]),
+    "kvz_hip_inter_residual_frame_sl": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), _P, _P]),
+    "kvz_hip_intra_recon_frame_sl": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), _P, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -677,31 +677,70 @@ def coeff_shapes(width, height):
     return (n, 4096), (n, 1024)
 
 
-def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None):
+SL_TABLE_LEN = _lib.SL_TABLE_LEN                                   # KVZ_HIP_SL_TABLE_LEN: values per packed array
+
+
+def sl_table_offset(size_id, list_id, rem):
+    """where table (size_id = log2 N - 2, list 0..5, rem = qp_scaled % 6) begins in a packed array (kvz_hip_scaling_tables)"""
+    assert 0 <= size_id < 4 and 0 <= list_id < 6 and 0 <= rem < 6
+    return 36 * (0, 16, 80, 336)[size_id] + (6 * list_id + rem) * (16 << (2 * size_id))
+
+
+def pack_scaling_tables(quant, dequant):
+    """kvz_hip_scaling_tables_pack.  quant, dequant: [size_id][list][rem] -> N*N int32 values (nested sequences or dicts keyed
+    (size_id, list, rem)), as scaling_list_t holds them after kvz_scalinglist_process; of the 32x32 lists only 0, 1 and 3 are read
+    (the others may be missing or None).  -> (quant, dequant): two int32 arrays of SL_TABLE_LEN values.  Needs no device."""
+    L = _lib.load()
+    keep, ptrs = [], []
+    for src in (quant, dequant):
+        p = (C.c_void_p * 6 * 6 * 4)()
+        for size_id in range(4):
+            for list_id in range(6):
+                for rem in range(6):
+                    try:
+                        t = src[(size_id, list_id, rem)] if isinstance(src, dict) else src[size_id][list_id][rem]
+                    except (KeyError, IndexError):
+                        t = None
+                    if t is None:
+                        continue
+                    a = np.ascontiguousarray(t, dtype=np.int32).reshape(-1)
+                    assert a.size == 16 << (2 * size_id)
+                    keep.append(a)
+                    p[size_id][list_id][rem] = a.ctypes.data
+        ptrs.append(p)
+    out = np.zeros(SL_TABLE_LEN, np.int32), np.zeros(SL_TABLE_LEN, np.int32)
+    check(L.kvz_hip_scaling_tables_pack(C.addressof(ptrs[0]), C.addressof(ptrs[1]), out[0].ctypes.data, out[1].ctypes.data), "scaling_tables_pack")
+    return out
+
+
+def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
+                         scaling=None):
     """kvz_hip_inter_residual_frame.  src: (y, u, v) uint8 planes of the source picture (its luma shape is the picture size;
     u, v None for 4:0:0); pred: (y, u, v) planes holding the prediction, at least as large (a wider array gives a stride);
     cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
     (default zeros).  Returns a dict: rec (y, u, v), coeff (y, u, v) as [LCUs, 4096 / 1024] int16, cus (with cbf_y set), cbf_out
     uint8 [height / 4, width / 4], costs INTER_RESIDUAL_COST [height / 4, width / 4].
-    lcu_qp: int8 [LCUs] in raster order -> kvz_hip_inter_residual_frame_qp: every TU takes the QP of its LCU and qp is ignored."""
-    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp)
+    lcu_qp: int8 [LCUs] in raster order -> kvz_hip_inter_residual_frame_qp: every TU takes the QP of its LCU and qp is ignored.
+    scaling: the pair of packed arrays of pack_scaling_tables -> kvz_hip_inter_residual_frame_sl (with or without lcu_qp)."""
+    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, scaling=scaling)
 
 
 def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                      tiles=None):
+                      tiles=None, scaling=None):
     """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
     intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
     dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp.  tiles: a TILE_GRID record ->
-    kvz_hip_intra_recon_frame_tiles (with or without lcu_qp)."""
+    kvz_hip_intra_recon_frame_tiles (with or without lcu_qp).  scaling: the pair of packed arrays of pack_scaling_tables ->
+    kvz_hip_intra_recon_frame_sl (with or without lcu_qp and tiles)."""
     cus = np.ascontiguousarray(cus)
     modes = np.ascontiguousarray(modes, dtype=np.uint8)
     assert modes.shape == cus.shape + (2,)
-    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles)
+    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling)
 
 
-def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None):
+def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None, scaling=None):
     """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries; tiles given (intra only): the
-    _tiles entry"""
+    _tiles entry; scaling given: the _sl entries, the packed arrays uploaded for the call"""
     L = _lib.init()
     chroma = int(chroma)
     height, width = src[0].shape
@@ -720,7 +759,12 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
     cb = np.zeros(cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(cus.shape)
     cs = np.zeros(cus.shape, INTER_RESIDUAL_COST) if costs is None else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(cus.shape)
     dcb, dcs, dcu = DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(cs.view(np.uint8)), DeviceBuffer.from_numpy(cus.view(np.uint8))
-    prm = inter_residual_params(qp, slice_is_intra, signhide, chroma)
+    prm = inter_residual_params(qp, slice_is_intra, signhide, chroma, 0 if scaling is None else 1)
+    sl = None
+    if scaling is not None:
+        tq, td = (np.ascontiguousarray(t, dtype=np.int32).reshape(SL_TABLE_LEN) for t in scaling)
+        dtq, dtd = DeviceBuffer.from_numpy(tq), DeviceBuffer.from_numpy(td)
+        sl = _lib.ScalingTables(dtq.ptr, dtd.ptr)
     planes = (table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
               r[1].shape[1] if chroma else 0, dcu.ptr)
     outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr)
@@ -729,15 +773,23 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
         lq = np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(lcu_count(width, height))
         dq = DeviceBuffer.from_numpy(lq)
         tail = (dq.ptr,) + tail
+    dqp = dq.ptr if lcu_qp is not None else None
     if modes is None:
         assert tiles is None
-        entry = L.kvz_hip_inter_residual_frame if lcu_qp is None else L.kvz_hip_inter_residual_frame_qp
-        check(entry(*planes, *outs, *tail), "inter_residual frame")
+        if sl is not None:
+            check(L.kvz_hip_inter_residual_frame_sl(*planes, *outs, dqp, C.byref(sl), prm.ctypes.data, None), "inter_residual frame_sl")
+        else:
+            entry = L.kvz_hip_inter_residual_frame if lcu_qp is None else L.kvz_hip_inter_residual_frame_qp
+            check(entry(*planes, *outs, *tail), "inter_residual frame")
     else:
         dm = DeviceBuffer.from_numpy(modes)
-        if tiles is not None:
+        if sl is not None:
+            g = _grid(tiles) if tiles is not None else None
+            check(L.kvz_hip_intra_recon_frame_sl(*planes, dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None, C.byref(sl), prm.ctypes.data,
+                                                 None), "intra_recon frame_sl")
+        elif tiles is not None:
             g = _grid(tiles)
-            check(L.kvz_hip_intra_recon_frame_tiles(*planes, dm.ptr, *outs, dq.ptr if lcu_qp is not None else None, g.ctypes.data, prm.ctypes.data, None),
+            check(L.kvz_hip_intra_recon_frame_tiles(*planes, dm.ptr, *outs, dqp, g.ctypes.data, prm.ctypes.data, None),
                   "intra_recon frame_tiles")
         else:
             entry = L.kvz_hip_intra_recon_frame if lcu_qp is None else L.kvz_hip_intra_recon_frame_qp

@@ -1,0 +1,344 @@
+// inter_residual_core.h -- the kernels and the host side of the whole-picture inter residual entries (inter_residual.hip: one QP per
+// call and a QP per LCU; inter_residual_sl.hip: scaling lists).  Everything here has internal linkage: each translation unit gets
+// its own copy and instantiates its own kernels.  The algorithm is described in inter_residual.hip.
+#pragma once
+
+#include "kvz_hip_internal.h"
+#include "transform_core.h"
+#include "quant_core.h"
+#include "lcu_layout.h"
+
+using namespace kvzhip;
+
+namespace {
+
+static_assert(sizeof(kvz_hip_inter_residual_params) == 24 && sizeof(kvz_hip_inter_residual_cost) == 24 && sizeof(kvz_hip_cu_info) == 20,
+              "layouts documented in kvz_hip.h");
+
+struct resid_args {
+  const u8 *src_y, *src_u, *src_v;
+  u8 *rec_y, *rec_u, *rec_v;
+  u32 src_stride_y, src_stride_c, rec_stride_y, rec_stride_c;
+  i16 *coeff_y, *coeff_u, *coeff_v;
+  u32 *cus;                      // records as five dwords; cbf_y is byte 4
+  u8 *cbf_out;                   // or nullptr
+  u32 *cost;                     // six dwords per SCU, or nullptr
+  int cus_stride, lcus_x;
+  int width, height;
+};
+
+// the inter CU that holds the luma position (x, y), from the record of that position alone: false for another type, a
+// depth beyond 3 or a CU that would leave the picture (the rule of kvz_hip_inter_recon_frame)
+__device__ __forceinline__ bool inter_cu_at(const resid_args &a, int x, int y, int &cu_x, int &cu_y, int &leaf)
+{
+  const u32 head = a.cus[((size_t)(y >> 2) * a.cus_stride + (x >> 2)) * 5];
+  const int depth = (head >> 8) & 255, trd = (int)(head >> 24);
+  if ((head & 255u) != 2u || depth > 3) return false;                         // CU_INTER (cu.h:38-43)
+  const int size = 64 >> depth;
+  cu_x = x & ~(size - 1);
+  cu_y = y & ~(size - 1);
+  // transform.c:448: split while depth == 0 or tr_depth > depth; 4x4 is the smallest TU
+  leaf = 64 >> min(4, max(max(depth, trd), 1));
+  return cu_x + size <= a.width && cu_y + size <= a.height;
+}
+
+// Outputs that TUs accumulate into start from zero inside the inter CUs (and keep their contents elsewhere).
+__global__ __launch_bounds__(256) void inter_residual_init_kernel(resid_args a, int n_scu)
+{
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_scu) return;
+  const int sy = i / a.cus_stride, sx = i - sy * a.cus_stride;
+  int cu_x, cu_y, leaf;
+  if (!inter_cu_at(a, 4 * sx, 4 * sy, cu_x, cu_y, leaf)) return;
+  if (a.cbf_out) a.cbf_out[i] = 0;
+  if (a.cost && cu_x == 4 * sx && cu_y == 4 * sy) {
+#pragma unroll
+    for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
+  }
+}
+
+// A QP per LCU (kvz_hip_inter_residual_frame_qp): the array and what else the constants depend on.  Every TU derives its own set
+// from the QP of the LCU it lies in, with the function the host uses (flat_consts, quant_core.h) -- a workgroup holds 256 / N
+// neighbouring slots of one row, up to four LCUs for N = 4, so the constants are per TU group, not per workgroup.  The kernel takes
+// it as an optional trailing argument: without it (one QP per call) the instantiation is the kernel as it was, argument for argument.
+struct lcu_qp_source { const int8_t *lcu_qp; int slice_is_intra, signhide; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { return q; }
+// Scaling lists (kvz_hip_inter_residual_frame_sl) are a second trailing argument after the QP source: the two packed arrays, and the
+// QP of every LCU where the source's array is NULL.  A TU's tables depend on its size, its plane and qp % 6 of its own LCU, so the
+// pointers are per TU group like the rest of the constants (sl_consts, quant_core.h).  The instantiation has a translation unit of
+// its own (inter_residual_sl.hip): the two above compile to the code they were.
+struct sl_source { const int32_t *quant, *dequant; int qp; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &) { return q; }
+__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t) { return t; }
+
+// Slots: [0, n_y) the N-aligned positions of Y, nx_y per row; then n_c of U and n_c of V, nx_c per row (n_c = 0 for
+// 4:0:0 and for N = 32).  A chroma slot (tx, ty) lies at the luma position (2 N tx, 2 N ty).
+template <int N, typename... PER_LCU>
+__global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, quant_consts ky, quant_consts kc,
+                                                                int nx_y, int n_y, int nx_c, int n_c, PER_LCU... per_lcu)
+{
+  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, SL = sizeof...(PER_LCU) == 2;
+  constexpr int TPB = 256 / N, W4 = N / 4;
+  constexpr int LD = lds_tile_ld(N);
+  __shared__ __attribute__((aligned(16))) i16 sa[TPB * N * LD];     // residual / coefficients
+  __shared__ __attribute__((aligned(16))) i16 sb[TPB * N * LD];     // transform scratch
+  __shared__ __attribute__((aligned(16))) i16 sq[TPB * N * LD];     // quantized coefficients
+  __shared__ int s_has[TPB];
+
+  const int tid = threadIdx.x, tu = tid / N, row = tid % N;
+  const int slot = blockIdx.x * TPB + tu;
+  int plane = 0, lx = 0, ly = 0, cu_x = 0, cu_y = 0, leaf = 0;
+  bool valid = slot < n_y + 2 * n_c;
+  if (slot < n_y) {
+    const int ty = slot / nx_y;
+    lx = N * (slot - ty * nx_y);
+    ly = N * ty;
+  } else if (valid) {
+    int s = slot - n_y;
+    plane = 1;
+    if (s >= n_c) { s -= n_c; plane = 2; }
+    const int ty = s / nx_c;
+    lx = 2 * N * (s - ty * nx_c);
+    ly = 2 * N * ty;
+  }
+  valid = valid && lx < a.width && ly < a.height && inter_cu_at(a, lx, ly, cu_x, cu_y, leaf);
+  // chroma TUs are half as wide; with 4x4 luma TUs the chroma of the 8x8 area is one 4x4 TU (transform.c:293-313)
+  valid = valid && (plane == 0 ? leaf == N : (N == 4 ? leaf <= 8 : leaf == 2 * N));
+  if (!__syncthreads_or(valid)) return;
+
+  quant_consts k = plane ? kc : ky;
+  k.qtable = nullptr; k.dqtable = nullptr; k.dq_mode = 0;                  // flat lists only
+  if constexpr (LCU_QP) {
+    constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
+    // ky and kc are not used.  A slot that is no TU runs the barriers with the constants of QP 0 and reads nothing
+    const lcu_qp_source &q = only(per_lcu...);
+    if constexpr (SL) {
+      // a slot that is no TU reads the tables of QP 0 of its size and plane: inside the arrays
+      const sl_source &t = lists_of(per_lcu...);
+      const int qp = valid ? clip_lcu_qp(q.lcu_qp ? (int)q.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)] : t.qp) : 0;
+      k = sl_consts(qp, LOG2, plane, 0, q.slice_is_intra, q.signhide, t.quant, t.dequant);
+    } else {
+      const int qp = valid ? clip_lcu_qp(q.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)]) : 0;
+      k = flat_consts(qp, LOG2, plane, q.slice_is_intra, q.signhide);
+    }
+  }
+  const int sh = plane ? 1 : 0, px = lx >> sh, py = ly >> sh;
+  const u8 *src_row = (plane == 0 ? a.src_y : (plane == 1 ? a.src_u : a.src_v)) + (size_t)(py + row) * (plane ? a.src_stride_c : a.src_stride_y) + px;
+  u8 *rec_row = (plane == 0 ? a.rec_y : (plane == 1 ? a.rec_u : a.rec_v)) + (size_t)(py + row) * (plane ? a.rec_stride_c : a.rec_stride_y) + px;
+  i16 *ta = sa + tu * N * LD, *tb = sb + tu * N * LD, *tq = sq + tu * N * LD;
+
+  u32 sw[W4], pw[W4];
+#pragma unroll
+  for (int j = 0; j < W4; ++j) sw[j] = pw[j] = 0u;
+  if (valid) {
+    load_row<N>(src_row, sw);
+    load_row<N>(rec_row, pw);
+  }
+  u32 zssd = 0;
+#pragma unroll
+  for (int x = 0; x < N; ++x) {
+    const int d = byte_of(sw, x) - byte_of(pw, x);
+    ta[row * LD + x] = (i16)d;
+    zssd += (u32)(d * d);
+  }
+  if (row == 0) s_has[tu] = 0;
+  __syncthreads();
+  transform_2d_lds<N, 0, LD>(ta, tb, row);
+  __syncthreads();
+  int any = 0;
+  if constexpr (SL) {
+    // the thread's row of the table is contiguous: 16-byte loads (the arrays and every table in them are 16-byte aligned)
+#pragma unroll
+    for (int j = 0; j < W4; ++j) {
+      const int4 f4 = *(const int4 *)(k.qtable + row * N + 4 * j);
+      const int f[4] = { f4.x, f4.y, f4.z, f4.w };
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int v = quant_listed(ta[row * LD + 4 * j + i], f[i], k);
+        tq[row * LD + 4 * j + i] = (i16)v;
+        any |= v;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int x = 0; x < N; ++x) {
+      const int v = quant_one(ta[row * LD + x], k.flat_qc, k);
+      tq[row * LD + x] = (i16)v;
+      any |= v;
+    }
+  }
+  if (k.signhide) {
+    __syncthreads();
+    if (row == 0) {
+      struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { return p[(i / n) * ld + (i % n)]; } };
+      lds_view cv = { ta, LD, N }, qv = { tq, LD, N };
+      sign_hide_block(cv, qv, N, 0, k);                                       // diagonal: kvz_get_scan_order of an inter CU
+    }
+    __syncthreads();
+    any = 0;
+#pragma unroll
+    for (int x = 0; x < N; ++x) any |= tq[row * LD + x];
+  }
+  if (any) atomicOr(&s_has[tu], 1);
+  __syncthreads();
+  const int has = s_has[tu];
+  u32 sab = 0;
+  if constexpr (SL) {
+#pragma unroll
+    for (int j = 0; j < W4; ++j) {
+      const int4 d4 = *(const int4 *)(k.dqtable + row * N + 4 * j);
+      const int d[4] = { d4.x, d4.y, d4.z, d4.w };
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int q = tq[row * LD + 4 * j + i];
+        sab += (u32)(q < 0 ? -q : q);
+        ta[row * LD + 4 * j + i] = (i16)dequant_listed(q, d[i], k);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int x = 0; x < N; ++x) {
+      const int q = tq[row * LD + x];
+      sab += (u32)(q < 0 ? -q : q);
+      ta[row * LD + x] = (i16)dequant_one(q, row * N + x, k);
+    }
+  }
+  __syncthreads();
+  transform_2d_lds<N, 1, LD>(ta, tb, row);
+  __syncthreads();
+  u32 ssd = zssd;                                    // a TU without coefficients keeps its prediction (quant-generic.c:262-271)
+  if (has) {
+    u32 ow[W4];
+    ssd = 0;
+#pragma unroll
+    for (int j = 0; j < W4; ++j) {
+      u32 o = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int x = 4 * j + i;
+        const i16 val = (i16)((int)ta[row * LD + x] + byte_of(pw, x));             // quant-generic.c:255
+        const int c = val < 0 ? 0 : (val > 255 ? 255 : val);
+        const int d = byte_of(sw, x) - c;
+        ssd += (u32)(d * d);
+        o |= (u32)c << (8 * i);
+      }
+      ow[j] = o;
+    }
+    if (valid) store_row<N>(rec_row, ow);
+  }
+  if (valid) {
+    const int bx = (lx & 63) >> (2 + sh), by = (ly & 63) >> (2 + sh);
+    const size_t lcu = (size_t)(ly >> 6) * a.lcus_x + (lx >> 6);
+    i16 *dst = (plane == 0 ? a.coeff_y : (plane == 1 ? a.coeff_u : a.coeff_v)) + lcu * (plane ? 1024 : 4096) + 16 * zorder_blk(bx, by) + row * N;
+    if (N == 4) {
+      *(uint2 *)dst = make_uint2(*(const u32 *)(tq + row * LD), *(const u32 *)(tq + row * LD + 2));
+    } else {
+#pragma unroll
+      for (int j = 0; j < N / 8; ++j) *(uint4 *)(dst + 8 * j) = lds_tile_load8<N, LD>(tq, row * N + 8 * j);
+    }
+    // flags of the SCUs the TU covers: cbf_y as lcu_set_coeff leaves it (search.c:173-190), bit `plane` of cbf_out
+    const int sx0 = lx >> 2, sy0 = ly >> 2;
+    if (plane == 0) {
+      if ((row & 3) == 0) {
+        for (int i = 0; i < W4; ++i) {
+          const size_t scu = (size_t)(sy0 + (row >> 2)) * a.cus_stride + sx0 + i;
+          ((u8 *)a.cus)[scu * 20 + 4] = (u8)has;
+          if (a.cbf_out && has) or_byte(a.cbf_out, scu, 1u);
+        }
+      }
+    } else if (row < N / 2 && a.cbf_out && has) {
+      for (int i = 0; i < N / 2; ++i) or_byte(a.cbf_out, (size_t)(sy0 + row) * a.cus_stride + sx0 + i, 1u << plane);
+    }
+  }
+  if (a.cost) {
+    // the inputs of the CU's cost (search.c:580-642): integer sums, so the order of the additions does not matter
+    ssd = group_sum<N>(ssd);
+    zssd = group_sum<N>(zssd);
+    sab = group_sum<N>(sab);
+    if (valid && row == 0) {
+      u32 *c = a.cost + ((size_t)(cu_y >> 2) * a.cus_stride + (cu_x >> 2)) * 6 + sh;
+      atomicAdd(c, ssd);
+      atomicAdd(c + 2, zssd);
+      atomicAdd(c + 4, sab);
+    }
+  }
+}
+
+template <int N, typename... PER_LCU>
+void launch_size(const resid_args &a, const quant_consts &ky, const quant_consts &kc, int chroma, hipStream_t st, PER_LCU... q)
+{
+  const int nx_y = (a.width + N - 1) / N, n_y = nx_y * ((a.height + N - 1) / N);
+  const int cw = a.width >> 1, chh = a.height >> 1;
+  const int nx_c = (cw + N - 1) / N, n_c = (chroma && N < 32) ? nx_c * ((chh + N - 1) / N) : 0;
+  constexpr int TPB = 256 / N;
+  const int slots = n_y + 2 * n_c;
+  hipLaunchKernelGGL((inter_residual_tu_kernel<N, PER_LCU...>), dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(256), 0, st, a, ky, kc, nx_y, n_y, nx_c, n_c, q...);
+}
+
+template <typename... PER_LCU>
+void launch_width(int n, const resid_args &a, const quant_consts &ky, const quant_consts &kc, int chroma, hipStream_t st, PER_LCU... q)
+{
+  if (n == 32) launch_size<32>(a, ky, kc, chroma, st, q...);
+  else if (n == 16) launch_size<16>(a, ky, kc, chroma, st, q...);
+  else if (n == 8) launch_size<8>(a, ky, kc, chroma, st, q...);
+  else launch_size<4>(a, ky, kc, chroma, st, q...);
+}
+
+// the three entries: lcu_qp == nullptr is one QP per call (params->qp).  SL: the entry with scaling lists, tables required and checked;
+// it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only
+template <bool SL>
+int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                   kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                   kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
+                   const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
+{
+  if (!src || !params || !rec_y || !cus || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
+    return kvzhip::invalid_arg(entry);
+  const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
+  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
+      (params->scaling_list != 0) != SL)
+    return kvzhip::invalid_arg(entry);
+  if (SL && (!tables || !tables->quant || !tables->dequant || (((uintptr_t)tables->quant | (uintptr_t)tables->dequant) & 15)))
+    return kvzhip::invalid_arg(entry);
+  if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
+                 src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
+    return kvzhip::invalid_arg(entry);
+  const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
+  quant_consts ky = {}, kc = {};                                              // not read with a QP array
+  // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants
+  if (!lcu_qp && (!make_consts(&qp, 4, 0, 0, &ky) || !make_consts(&qp, 4, 2, 2, &kc))) return kvzhip::invalid_arg(entry);
+  resid_args a;
+  a.src_y = src->y; a.src_u = chroma ? src->u : nullptr; a.src_v = chroma ? src->v : nullptr;
+  a.rec_y = rec_y; a.rec_u = chroma ? rec_u : nullptr; a.rec_v = chroma ? rec_v : nullptr;
+  a.src_stride_y = src->stride_y; a.src_stride_c = src->stride_c; a.rec_stride_y = stride_y; a.rec_stride_c = stride_c;
+  a.coeff_y = coeff_y; a.coeff_u = chroma ? coeff_u : nullptr; a.coeff_v = chroma ? coeff_v : nullptr;
+  a.cus = (u32 *)cus; a.cbf_out = cbf_out; a.cost = (u32 *)costs;
+  a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
+  a.width = width; a.height = height;
+  hipStream_t st = ctx_stream(s);
+  if (cbf_out || costs) {
+    const int n_scu = (width >> 2) * (height >> 2);
+    hipLaunchKernelGGL(inter_residual_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
+    KVZ_CHECK_LAUNCH("inter_residual_init_kernel");
+  }
+  // the shift of the transform depends on the size: q_bits, add and the dequantisation shift per launch
+  const int sizes[4] = { 32, 16, 8, 4 };
+  for (int i = 0; i < 4; ++i) {
+    const int n = sizes[i];
+    if constexpr (SL) {
+      const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+      const sl_source lists = { tables->quant, tables->dequant, params->qp };
+      launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+    } else if (lcu_qp) {
+      const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+      launch_width(n, a, ky, kc, chroma, st, per_lcu);
+    } else {
+      if (!make_consts(&qp, n, 0, 0, &ky) || !make_consts(&qp, n, 2, 2, &kc)) return kvzhip::invalid_arg(entry);
+      launch_width(n, a, ky, kc, chroma, st);
+    }
+    KVZ_CHECK_LAUNCH("inter_residual_tu_kernel");
+  }
+  return KVZ_HIP_OK;
+}
+
+}  // namespace

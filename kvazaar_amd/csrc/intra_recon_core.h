@@ -1,6 +1,7 @@
 // intra_recon_core.h -- the kernels and the host side of the whole-picture intra entries (intra_recon.hip: one QP per call,
-// intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture).  Everything here has internal linkage: each of the
-// translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is described in intra_recon.hip.
+// intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture, intra_recon_sl.hip: scaling lists).  Everything here has
+// internal linkage: each of the translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is
+// described in intra_recon.hip.
 #pragma once
 
 #include "kvz_hip_internal.h"
@@ -78,8 +79,9 @@ struct tile_rect { int x0, y0, x1, y1; };
 struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { return p[(i / n) * ld + (i % n)]; } };
 
 // One leaf TU, N wide, by the whole wave.  Called under wave-uniform conditions only.  TILES: tr stands for the picture in everything
-// about the TU's neighbours; without it tr is not read, and the code is compiled from the expressions it always had.
-template <int N, bool TILES>
+// about the TU's neighbours; without it tr is not read, and the code is compiled from the expressions it always had.  SL: k carries the
+// TU's tables (sl_consts, quant_core.h); a lane reads its row of each, which is contiguous, with 16-byte loads.
+template <int N, bool TILES, bool SL = false>
 __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
                                         u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq)
 {
@@ -180,11 +182,25 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
   }
   __syncthreads();
   int any = 0;
+  if constexpr (SL) {
 #pragma unroll
-  for (int x = 0; x < N; ++x) {
-    const int v = quant_one(ta[row * LD + x], k.flat_qc, k);
-    tq[row * LD + x] = (i16)v;
-    any |= v;
+    for (int j = 0; j < W4; ++j) {
+      const int4 f4 = *(const int4 *)(k.qtable + row * N + 4 * j);
+      const int f[4] = { f4.x, f4.y, f4.z, f4.w };
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int v = quant_listed(ta[row * LD + 4 * j + i], f[i], k);
+        tq[row * LD + 4 * j + i] = (i16)v;
+        any |= v;
+      }
+    }
+  } else {
+#pragma unroll
+    for (int x = 0; x < N; ++x) {
+      const int v = quant_one(ta[row * LD + x], k.flat_qc, k);
+      tq[row * LD + x] = (i16)v;
+      any |= v;
+    }
   }
   if (k.signhide) {
     // a lane per coefficient group, as sign_hide_kernel (quant.hip): the block's ac_sum is a sum over the lanes, the "last"
@@ -200,7 +216,8 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
     for (int n = 0; n < 16; ++n) {
       pos16[n] = scan_pos(t.scan, LOG2, ((cg_ok ? lane : 0) << 4) + n);
       nz = nz || qv[pos16[n]] != 0;
-      ac += (u32)quant_level(cv[pos16[n]], k.flat_qc, k);
+      if constexpr (SL) ac += (u32)quant_level(cv[pos16[n]], k.qtable[pos16[n]], k);
+      else ac += (u32)quant_level(cv[pos16[n]], k.flat_qc, k);
     }
     ac = group_sum<64>(cg_ok ? ac : 0u);
     const unsigned long long bal = __ballot(nz && cg_ok);
@@ -213,11 +230,25 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
   }
   const int has = __syncthreads_or(any) ? 1 : 0;
   u32 sab = 0;
+  if constexpr (SL) {
 #pragma unroll
-  for (int x = 0; x < N; ++x) {
-    const int q = tq[row * LD + x];
-    sab += (u32)(q < 0 ? -q : q);
-    ta[row * LD + x] = (i16)dequant_one(q, row * N + x, k);
+    for (int j = 0; j < W4; ++j) {
+      const int4 d4 = *(const int4 *)(k.dqtable + row * N + 4 * j);
+      const int d[4] = { d4.x, d4.y, d4.z, d4.w };
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int q = tq[row * LD + 4 * j + i];
+        sab += (u32)(q < 0 ? -q : q);
+        ta[row * LD + 4 * j + i] = (i16)dequant_listed(q, d[i], k);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int x = 0; x < N; ++x) {
+      const int q = tq[row * LD + x];
+      sab += (u32)(q < 0 ? -q : q);
+      ta[row * LD + x] = (i16)dequant_one(q, row * N + x, k);
+    }
   }
   __syncthreads();
   if constexpr (N == 4) {
@@ -301,6 +332,13 @@ __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { r
 struct tile_source { kvz_hip_tile_grid grid; int qp; };
 __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &) { return q; }
 __host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t) { return t; }
+// Scaling lists (kvz_hip_intra_recon_frame_sl) are a third trailing argument after the grid: the two packed arrays.  The workgroup
+// derives the sets of the four sizes of its LCU and plane with their table pointers (sl_consts, quant_core.h) where the others derive
+// the flat sets.  Once more an instantiation of its own in a translation unit of its own (intra_recon_sl.hip).
+struct sl_source { const int32_t *quant, *dequant; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &) { return q; }
+__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &) { return t; }
+__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l) { return l; }
 template <bool LCU_QP> struct lcu_sets {};                                   // what a workgroup derives from its LCU's QP: nothing with one QP per call,
 template <> struct lcu_sets<true> { quant_consts k[4]; };                    // else the sets of the four sizes, [log2 N - 2]
 
@@ -317,7 +355,7 @@ static_assert(WG == 64, "one wave per workgroup: see intra_tu");
 template <typename... PER_LCU>
 __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int t, PER_LCU... per_lcu)
 {
-  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) == 2;
+  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2, SL = sizeof...(PER_LCU) == 3;
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -388,7 +426,11 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
     if constexpr (TILES) qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(q.lcu_qp ? (int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x] : tiles_of(per_lcu...).qp)));
     else qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]));
 #pragma unroll
-    for (int i = 0; i < 4; ++i) own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, q.slice_is_intra, q.signhide);
+    for (int i = 0; i < 4; ++i) {
+      // (a chroma plane has no 32x32 TU: that set is derived and not used)
+      if constexpr (SL) own.k[i] = sl_consts(qp, 2 + i, plane, 1, q.slice_is_intra, q.signhide, lists_of(per_lcu...).quant, lists_of(per_lcu...).dequant);
+      else own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, q.slice_is_intra, q.signhide);
+    }
   }
 
   // ---- the walk: 256 SCUs in z-order; a leaf TU is done at its top-left SCU ----
@@ -417,10 +459,10 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
     p.tx = (p.lx - X0) >> sh; p.ty = (p.ly - Y0) >> sh;
     const quant_consts *kk = a.k[plane ? 1 : 0];
     if constexpr (LCU_QP) kk = own.k;
-    if (n == 32) intra_tu<32, TILES>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else if (n == 16) intra_tu<16, TILES>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else if (n == 8) intra_tu<8, TILES>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else intra_tu<4, TILES>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    if (n == 32) intra_tu<32, TILES, SL>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else if (n == 16) intra_tu<16, TILES, SL>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else if (n == 8) intra_tu<8, TILES, SL>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else intra_tu<4, TILES, SL>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq);
   }
 
   // ---- the pixels of the intra CUs go back: a row of an SCU (4 luma, 2 chroma pixels) per item, 16 SCUs of a row side by side ----
@@ -435,7 +477,8 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   }
 }
 
-// the three entries; per_lcu: nothing (one QP per call, params->qp), one lcu_qp_source, or that and a tile_source
+// the four entries; per_lcu: nothing (one QP per call, params->qp), one lcu_qp_source, that and a tile_source, or those and an
+// sl_source (the only one that takes, and requires, params->scaling_list != 0)
 template <typename... PER_LCU>
 int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                 kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes, kvz_hip_coeff *coeff_y,
@@ -447,7 +490,7 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
   if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      params->scaling_list != 0)
+      (params->scaling_list != 0) != (sizeof...(PER_LCU) == 3))
     return kvzhip::invalid_arg(entry);
   if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
                  src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
@@ -476,7 +519,7 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
   }
   // the launch sequence depends on width, height and chroma alone
   int waves = a.lcus_x + 2 * (lcus_y - 1), groups = lcus_y;
-  if constexpr (sizeof...(PER_LCU) == 2) {
+  if constexpr (sizeof...(PER_LCU) >= 2) {
     // and on the grid: the largest tile's count of waves, a workgroup per LCU row and tile column
     const kvz_hip_tile_grid &g = tiles_of(per_lcu...).grid;
     waves = tile_grid_waves(g);

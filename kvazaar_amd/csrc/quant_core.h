@@ -1,6 +1,7 @@
 // quant_core.h -- the quantisation arithmetic shared by quant.hip (batched entries), inter_residual.hip and intra_recon_core.h
 // (whole-picture entries): the flattened encoder state and the one function that derives it for flat lists, on the host and on the
-// device (flat_consts), quant / dequant of one coefficient and the sign-bit-hiding pass.
+// device (flat_consts), the one that layers scaling lists over it (sl_consts), quant / dequant of one coefficient and the
+// sign-bit-hiding pass.
 // Reference: src/strategies/generic/quant-generic.c (cited per function), transform.c:129-143 for the scaled QP.
 #pragma once
 
@@ -52,6 +53,29 @@ __host__ __device__ inline quant_consts flat_consts(int qp, int log2_tr, int chr
 // the LCU QP the per-LCU entries use: any value is brought into 0..51 (the reference's CLIP_TO_QP), so that no value leaves a table
 __host__ __device__ inline int clip_lcu_qp(int qp) { return qp < 0 ? 0 : (qp > 51 ? 51 : qp); }
 
+// The packed scaling lists of kvz_hip_scaling_tables (kvz_hip.h): where table (size_id, list, rem) begins in either array
+__host__ __device__ constexpr int sl_table_offset(int size_id, int list, int rem)
+{
+  // 36 tables of every smaller size come first: 16 + 64 + .. = (16 * 4^size_id - 16) / 3 values each
+  return 12 * ((16 << (2 * size_id)) - 16) + ((6 * list + rem) << (2 * size_id + 4));
+}
+// The constants of one TU under scaling lists, on the host and on the device: flat_consts with the table pointers, dq_mode and
+// dq_shift / dq_add on top -- the arithmetic of make_consts below, for the whole-picture entries, which pick a TU's tables on the
+// device from its size, its plane (0 Y, 1 U, 2 V), its CU's type and the QP of its LCU.  The reference quantises V with U's list
+// (type 2, quant-generic.c:223 with :46-47) and dequantises each plane with its own (:244, :293-295); both branches of :296-311.
+__host__ __device__ inline quant_consts sl_consts(int qp, int log2_tr, int plane, int cu_is_intra, int slice_is_intra, int signhide,
+                                                  const int32_t *quant, const int32_t *dequant)
+{
+  quant_consts c = flat_consts(qp, log2_tr, plane != 0, slice_is_intra, signhide);
+  const int qps = scaled_qp(plane ? 2 : 0, qp), base = cu_is_intra ? 0 : 3, shift = log2_tr + 3;
+  c.qtable = quant + sl_table_offset(log2_tr - 2, base + (plane ? 1 : 0), qps % 6);
+  c.dqtable = dequant + sl_table_offset(log2_tr - 2, base + plane, qps % 6);
+  if (shift > qps / 6) { c.dq_mode = 1; c.dq_shift = shift - qps / 6; c.dq_add = 1 << (c.dq_shift - 1); }
+  else { c.dq_mode = 2; c.dq_shift = qps / 6 - shift; c.dq_add = 0; }
+  c.dq_scale = 0;
+  return c;
+}
+
 // quant-generic.c:40-50 and :283-320: flat_consts, with the scaling-list tables on top where they are given
 static bool make_consts(const kvz_hip_quant_params *p, int width, int type_q, int type_dq, quant_consts *c)
 {
@@ -99,6 +123,21 @@ __device__ __forceinline__ int dequant_one(int q, int n, const quant_consts &k)
   if (k.dq_mode == 1) return clip16((q * d + k.dq_add) >> k.dq_shift);
   int v = clip16(q * d);
   return clip16((int)((unsigned)v << k.dq_shift));
+}
+// the same with the table entry d already loaded (the whole-picture kernels read their row of the table as 16-byte vectors);
+// dq_mode is 1 or 2
+__device__ __forceinline__ int dequant_listed(int q, int d, const quant_consts &k)
+{
+  if (k.dq_mode == 1) return clip16((q * d + k.dq_add) >> k.dq_shift);
+  const int v = clip16(q * d);
+  return clip16((int)((unsigned)v << k.dq_shift));
+}
+// quant_one with a table entry: always the reference's 64-bit product (quant-generic.c:62)
+__device__ __forceinline__ int quant_listed(int c, int qc, const quant_consts &k)
+{
+  const int a = c < 0 ? -c : c;
+  const int level = (int)(((long long)a * qc + k.add) >> k.q_bits);
+  return clip16(c < 0 ? -level : level);
 }
 
 // ---- sign bit hiding (quant-generic.c:69-162) on one block; coef/q_coef may be

@@ -13,13 +13,18 @@ once), so launch overhead, partial waves and tails count the way they do in an e
 tools/bench_all.py, whose batches are sized to hide them.  It is a measurement of the kernels on a
 frame-sized workload, not of an encoder: the mode decision around them is not here.
 
-  python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR]
+  python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR] [--scaling-list [default|none]]
 
 --lcu-qp: the picture chain of a frame whose QP changes per LCU (rate control, --roi): intra reconstruction through
 kvz_hip_intra_recon_frame_qp with a QP array, then kvz_hip_cu_qp_frame (the QP map and the per-LCU predictor), and deblocking
 with per_cu_qp = 1.
 --tiles CxR: the picture is cut into C x R uniform tiles (the reference's spacing): the stages of the picture chain that depend on
 tiles go through their *_tiles entries -- intra reconstruction, the QP map (with --lcu-qp), deblocking and the SAO reconstruction.
+--scaling-list: the two stages that quantise go through their *_sl entries with the reference's default lists (the packed tables of
+tests/golden/scaling_list.npz): the residual coding of the inter CUs (kvz_hip_inter_residual_frame_sl, after the motion compensation,
+on its planes and its map) and the intra reconstruction (kvz_hip_intra_recon_frame_sl).  `none` passes tables == NULL: the same
+entries, which then launch the kernels of the entries without lists -- the baseline of what the table reads cost.  Combines with
+--lcu-qp and --tiles.
 """
 import argparse
 import ctypes as C
@@ -38,7 +43,7 @@ from kvazaar_amd._lib import QuantParams  # noqa: E402
 W, H = 1920, 1080
 
 
-def build_stages(L, dev, lcu_qp=False, tiles=None):
+def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None):
     """-> {stage: [(name, units, launch(stream))]}, plus the tensors kept alive"""
     g = torch.Generator(device=dev); g.manual_seed(7)
     keep = []
@@ -124,7 +129,40 @@ def build_stages(L, dev, lcu_qp=False, tiles=None):
         ir_qprm = np.zeros(1, dtype=api.CU_QP_PARAMS)
         ir_qprm["start_qp"] = 27
         keep += [ir_qp, ir_cbf, ir_last, ir_qprm]
-    if tiles:
+    if lists:
+        # the packed tables on the device; `none`: no tables, and params->scaling_list stays 0
+        sl = None
+        if lists == "default":
+            z = np.load(os.path.join(ROOT, "tests", "golden", "scaling_list.npz"), allow_pickle=False)
+            sl_q, sl_d = up(z["default_quant"]), up(z["default_dequant"])
+            sl = _lib.ScalingTables(sl_q.data_ptr(), sl_d.data_ptr())
+            ir_prm = api.inter_residual_params(27, 0, 0, 1, scaling_list=1)
+            keep += [sl_q, sl_d, sl, ir_prm]
+        sl_ref = C.byref(sl) if sl is not None else None
+        # residual coding of the inter CUs, on the planes the motion compensation has just written (tr_depth 0 in this map: the
+        # TUs are as large as their CUs, 32 at the most)
+        rc_co = [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+        rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
+        rc_src_tab = api.ref_picture_table([(rc_src[0].data_ptr(), rc_src[1].data_ptr(), rc_src[2].data_ptr(), W, W // 2)], W, H)
+        keep += [rc_co, rc_src, rc_src_tab]
+        stages["tu"].append(("inter_residual_frame_sl", 1, lambda s: L.kvz_hip_inter_residual_frame_sl(
+            rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
+            rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
+            ir_prm.ctypes.data, s)))
+        stages["tu"].append(("intra_recon_frame_sl", 1, lambda s: L.kvz_hip_intra_recon_frame_sl(
+            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+            ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
+            ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data if tiles else None, sl_ref, ir_prm.ctypes.data, s)))
+        if lcu_qp and tiles:
+            ir_tprm = np.zeros(1, dtype=api.CU_QP_TILES_PARAMS)
+            ir_tprm["start_qp"] = 27
+            keep.append(ir_tprm)
+            stages["tu"].append(("cu_qp_frame_tiles", 1, lambda s: L.kvz_hip_cu_qp_frame_tiles(
+                ir_cus_d.data_ptr(), ir_cbf.data_ptr(), W, H, ir_qp.data_ptr(), ir_last.data_ptr(), grid.ctypes.data, ir_tprm.ctypes.data, s)))
+        elif lcu_qp:
+            stages["tu"].append(("cu_qp_frame", 1, lambda s: L.kvz_hip_cu_qp_frame(
+                ir_cus_d.data_ptr(), ir_cbf.data_ptr(), W, H, ir_qp.data_ptr(), ir_last.data_ptr(), ir_qprm.ctypes.data, s)))
+    elif tiles:
         stages["tu"].append(("intra_recon_frame_tiles", 1, lambda s: L.kvz_hip_intra_recon_frame_tiles(
             ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
             ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
@@ -266,6 +304,8 @@ def main():
     ap.add_argument("--tune", default="", help="key=value[,key=value...] passed to kvz_hip_set_tuning")
     ap.add_argument("--lcu-qp", action="store_true", help="a QP per LCU: intra_recon_frame_qp, cu_qp_frame, deblocking with per_cu_qp = 1")
     ap.add_argument("--tiles", default="", metavar="CxR", help="C x R uniform tiles: the *_tiles entries of intra, QP map, deblocking and SAO")
+    ap.add_argument("--scaling-list", nargs="?", const="default", default=None, choices=("default", "none"),
+                    help="the *_sl entries of the inter residual coding and the intra reconstruction; `none`: with tables == NULL (the baseline)")
     args = ap.parse_args()
     tiles = tuple(int(v) for v in args.tiles.lower().split("x")) if args.tiles else None
     assert tiles is None or len(tiles) == 2
@@ -277,7 +317,7 @@ def main():
     s = L.kvz_hip_stream_create()
     side = [L.kvz_hip_stream_create() for _ in range(7)]
     events = [L.kvz_hip_event_create() for _ in range(8)]
-    stages, keep = build_stages(L, dev, args.lcu_qp, tiles)
+    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list)
     torch.cuda.synchronize()
     n_launch = sum(len(v) for v in stages.values())
 
