@@ -1290,6 +1290,68 @@ KVZ_HIP_API int kvz_hip_intra_recon_frame_sl(const kvz_hip_ref_picture *src, kvz
                                              const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
+/* Transform skip in the picture chain: residual coding, intra recon   */
+/*   reference: kvz_quantize_residual_trskip (transform.c:229-276) as  */
+/*   quantize_tr_residual calls it (transform.c:348-387);              */
+/*   kvz_transformskip / kvz_itransformskip (transform.c:151-181);     */
+/*   kvz_get_coeff_cost below fast_residual_cost_limit                 */
+/*   (rdo.c:44-45, :208-222); --transform-skip, --fast-residual-cost   */
+/* ------------------------------------------------------------------ */
+typedef struct {
+  int32_t bit_cost;             /* (int)(state->lambda + 0.5), transform.c:244; used where lcu_bit_cost == NULL; >= 0 */
+  int32_t reserved;
+  const int32_t *lcu_bit_cost;  /* DEVICE, optional: one value per LCU in picture raster order (lambda follows the LCU under
+                                   rate control, rate_control.c:278-340); negative values count as 0 */
+} kvz_hip_trskip;               /* 16 bytes; HOST struct, copied at the call */
+
+/* kvz_hip_inter_residual_frame_sl and kvz_hip_intra_recon_frame_sl with two more arguments, placed before params, for pictures coded
+ * with --transform-skip (cfg.trskip_enable).
+ * ts == NULL: the call IS the _sl entry, byte for byte (it calls it, and that entry names itself in kvz_hip_last_error);
+ *   tr_skip_out is not touched.  ts != NULL: every combination of lcu_qp, grid and tables that the _sl entry accepts is accepted.
+ * tr_skip_out: DEVICE, one byte per 4x4 SCU in the raster of cus, any alignment; required with ts != NULL.
+ * Which TUs: the 4x4 luma leaf TUs of the CUs the entry handles -- those for which can_use_trskip holds (transform.c:348-350).
+ *   Chroma TUs and larger luma TUs are coded exactly as by the _sl entry.
+ * Per such TU, kvz_quantize_residual runs twice on the same source and prediction, with the same scan order, sign hiding, QP
+ *   constants and scaling tables, use_trskip = 0 then 1.  The transformed trial uses the DST in the intra entry and the DCT in the
+ *   inter entry.  The skipped trial is kvz_transformskip / kvz_itransformskip: coefficient = residual << 5, residual =
+ *   (coefficient + 16) >> 5 (bit depth 8).  Scaling lists apply to the skipped coefficients too: quant-generic.c does not look at
+ *   use_trskip when it quantises.
+ * Cost of a trial, in uint32_t arithmetic that wraps as C's does:
+ *     cost = kvz_pixels_calc_ssd(source, trial rec) + coeff_cost * (uint32_t)bit_cost
+ *     coeff_cost = (uint32_t)(sum * (qp * 0.044407704 + 0.557323653) + 0.5)                      (doubles, rdo.c:44-45, :219-220)
+ *   sum = kvz_coeff_abs_sum of the trial's 16 coefficients; qp = state->qp of the TU's LCU, the luma QP and not the scaled one: the
+ *   clamped lcu_qp value, or params->qp.  Every multiply and add rounds on its own, as on the host (no fused multiply-add).
+ *   bit_cost = lcu_bit_cost[LCU] where the array is given (a negative value counts as 0), else ts->bit_cost.
+ * Decision: the transformed trial wins ties (noskip.cost <= skip.cost, transform.c:260).  The winner's reconstruction, coefficients
+ *   and has_coeffs become the TU's and feed cus[].cbf_y, cbf_out and costs exactly as the one trial of the _sl entry does: ssd_y and
+ *   coeff_abs_y are the winner's, zero_ssd_y is against the prediction and does not change.  A winner without coefficients keeps
+ *   the prediction and writes zeros.  In the intra entry a later TU reads the winner's pixels, as it reads any reconstruction.
+ * tr_skip_out[scu] = 1 or 0 for every SCU covered by such a TU: what cur_pu->tr_skip holds at transform.c:387.  The bytes of all
+ *   other SCUs are left untouched; the host clears the array once, as it does cbf_out.
+ * Equals the reference where cfg.trskip_enable is set and state->qp < cfg.fast_residual_cost_limit (--fast-residual-cost N) holds
+ *   for every LCU.  At or above the limit the reference prices coefficients with CABAC on the live context state
+ *   (get_coeff_cabac_cost), which is OUT OF SCOPE, as are lossless coding, RDOQ and the transform-skip term of the intra rough
+ *   search (search_intra.c:105-167).
+ * Errors: ts != NULL with tr_skip_out == NULL, with bit_cost < 0 while lcu_bit_cost == NULL, or with lcu_bit_cost not 4-byte
+ *   aligned returns KVZ_HIP_ERR_INVALID and nothing is written; so does every error of the _sl entry.
+ * Launches and capture: asynchronous, no allocation, no synchronisation with the host, usable between kvz_hip_graph_begin / _end.
+ *   The launch shapes are those of the _sl entry: the same launch count, the same intra wavefront count.  A captured call may be
+ *   replayed after the CONTENTS of lcu_bit_cost changed.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame_ts(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                                kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
+                                                uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
+                                                const kvz_hip_scaling_tables *tables, const kvz_hip_trskip *ts, uint8_t *tr_skip_out,
+                                                const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frame_ts(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                             kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                             const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                             kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                             const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
+                                             const kvz_hip_scaling_tables *tables, const kvz_hip_trskip *ts, uint8_t *tr_skip_out,
+                                             const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */
 /* ------------------------------------------------------------------ */
 /* kvz_strategyselector_register (strategyselector.h:87, strategyselector.c:216-256) */

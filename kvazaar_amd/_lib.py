@@ -65,6 +65,11 @@ class ScalingTables(C.Structure):
     _fields_ = [("quant", C.c_void_p), ("dequant", C.c_void_p)]
 
 
+class TrSkip(C.Structure):
+    """kvz_hip_trskip"""
+    _fields_ = [("bit_cost", C.c_int32), ("reserved", C.c_int32), ("lcu_bit_cost", C.c_void_p)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -168,6 +173,9 @@ SIGNATURES = {
     "kvz_hip_scaling_tables_pack": (_I, [_P, _P, _P, _P]),
     "kvz_hip_inter_residual_frame_sl": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), _P, _P]),
     "kvz_hip_intra_recon_frame_sl": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), _P, _P]),
+    "kvz_hip_inter_residual_frame_ts": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P, _P, _P]),
+    "kvz_hip_intra_recon_frame_ts": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P,
+                                          _P, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -713,34 +713,43 @@ def pack_scaling_tables(quant, dequant):
     return out
 
 
+TRSKIP = np.dtype([("bit_cost", "<i4"), ("reserved", "<i4"), ("lcu_bit_cost", "<u8")])           # kvz_hip_trskip
+
+
 def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                         scaling=None):
+                         trskip=None, tr_skip=None, scaling=None):
     """kvz_hip_inter_residual_frame.  src: (y, u, v) uint8 planes of the source picture (its luma shape is the picture size;
     u, v None for 4:0:0); pred: (y, u, v) planes holding the prediction, at least as large (a wider array gives a stride);
     cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
     (default zeros).  Returns a dict: rec (y, u, v), coeff (y, u, v) as [LCUs, 4096 / 1024] int16, cus (with cbf_y set), cbf_out
     uint8 [height / 4, width / 4], costs INTER_RESIDUAL_COST [height / 4, width / 4].
     lcu_qp: int8 [LCUs] in raster order -> kvz_hip_inter_residual_frame_qp: every TU takes the QP of its LCU and qp is ignored.
-    scaling: the pair of packed arrays of pack_scaling_tables -> kvz_hip_inter_residual_frame_sl (with or without lcu_qp)."""
-    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, scaling=scaling)
+    scaling: the pair of packed arrays of pack_scaling_tables -> kvz_hip_inter_residual_frame_sl (with or without lcu_qp).
+    trskip: the bit cost of transform skip, (int)(lambda + 0.5) as one int or as an int32 array [LCUs] in raster order ->
+    kvz_hip_inter_residual_frame_ts (with or without lcu_qp and scaling); the dict gains tr_skip, uint8 [height / 4, width / 4].
+    tr_skip: optional initial contents of that array (default zeros)."""
+    return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, scaling=scaling,
+                           trskip=trskip, tr_skip=tr_skip)
 
 
 def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                      tiles=None, scaling=None):
+                      tiles=None, trskip=None, tr_skip=None, scaling=None):
     """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
     intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
     dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp.  tiles: a TILE_GRID record ->
     kvz_hip_intra_recon_frame_tiles (with or without lcu_qp).  scaling: the pair of packed arrays of pack_scaling_tables ->
-    kvz_hip_intra_recon_frame_sl (with or without lcu_qp and tiles)."""
+    kvz_hip_intra_recon_frame_sl (with or without lcu_qp and tiles).  trskip, tr_skip: as in inter_residual_frame ->
+    kvz_hip_intra_recon_frame_ts (with or without lcu_qp, tiles and scaling)."""
     cus = np.ascontiguousarray(cus)
     modes = np.ascontiguousarray(modes, dtype=np.uint8)
     assert modes.shape == cus.shape + (2,)
-    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling)
+    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling, trskip, tr_skip)
 
 
-def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None, scaling=None):
+def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None, scaling=None,
+                    trskip=None, tr_skip=None):
     """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries; tiles given (intra only): the
-    _tiles entry; scaling given: the _sl entries, the packed arrays uploaded for the call"""
+    _tiles entry; scaling given: the _sl entries, the packed arrays uploaded for the call; trskip given: the _ts entries"""
     L = _lib.init()
     chroma = int(chroma)
     height, width = src[0].shape
@@ -774,7 +783,27 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
         dq = DeviceBuffer.from_numpy(lq)
         tail = (dq.ptr,) + tail
     dqp = dq.ptr if lcu_qp is not None else None
-    if modes is None:
+    dts = None
+    if trskip is not None:
+        ts = _lib.TrSkip(0, 0, None)
+        if np.ndim(trskip) == 0:
+            ts.bit_cost = int(trskip)
+        else:
+            dbc = DeviceBuffer.from_numpy(np.ascontiguousarray(trskip, dtype=np.int32).reshape(lcu_count(width, height)))
+            ts.lcu_bit_cost = dbc.ptr
+        tsk = np.zeros(cus.shape, np.uint8) if tr_skip is None else np.ascontiguousarray(tr_skip, dtype=np.uint8).reshape(cus.shape)
+        dts = DeviceBuffer.from_numpy(tsk)
+        g = _grid(tiles) if tiles is not None else None
+        if modes is None:
+            assert tiles is None
+            check(L.kvz_hip_inter_residual_frame_ts(*planes, *outs, dqp, C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr,
+                                                    prm.ctypes.data, None), "inter_residual frame_ts")
+        else:
+            dm = DeviceBuffer.from_numpy(modes)
+            check(L.kvz_hip_intra_recon_frame_ts(*planes, dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None,
+                                                 C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr, prm.ctypes.data, None),
+                  "intra_recon frame_ts")
+    elif modes is None:
         assert tiles is None
         if sl is not None:
             check(L.kvz_hip_inter_residual_frame_sl(*planes, *outs, dqp, C.byref(sl), prm.ctypes.data, None), "inter_residual frame_sl")
@@ -795,11 +824,14 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
             entry = L.kvz_hip_intra_recon_frame if lcu_qp is None else L.kvz_hip_intra_recon_frame_qp
             check(entry(*planes, dm.ptr, *outs, *tail), "intra_recon frame")
     pad = (None,) * (3 - n)
-    return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
-            "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
-            "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
-            "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
-            "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+    out = {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
+           "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
+           "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
+           "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
+           "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+    if dts is not None:
+        out["tr_skip"] = dts.to_numpy(np.uint8, cus.shape)
+    return out
 
 
 # ---- the QP map of a picture whose QP changes per LCU ----

@@ -1,5 +1,5 @@
 // inter_residual_core.h -- the kernels and the host side of the whole-picture inter residual entries (inter_residual.hip: one QP per
-// call and a QP per LCU; inter_residual_sl.hip: scaling lists).  Everything here has internal linkage: each translation unit gets
+// call and a QP per LCU; inter_residual_sl.hip: scaling lists; inter_residual_ts.hip: transform skip).  Everything here has internal linkage: each translation unit gets
 // its own copy and instantiates its own kernels.  The algorithm is described in inter_residual.hip.
 #pragma once
 
@@ -70,6 +70,19 @@ __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { r
 struct sl_source { const int32_t *quant, *dequant; int qp; };
 __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &) { return q; }
 __device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t) { return t; }
+// Transform skip (kvz_hip_inter_residual_frame_ts) is the last trailing argument, after the QP source or after the lists, and only the
+// N = 4 launch takes it: a luma slot runs kvz_quantize_residual twice, transformed and skipped, prices both and keeps the cheaper one
+// (kvz_quantize_residual_trskip, transform.c:229-276).  qp: the QP of every LCU where the QP source's array is NULL and there are no
+// lists.  The two instantiations live in inter_residual_ts.hip; those above compile to the code they were.
+struct ts_source { const int32_t *lcu_bit_cost; u8 *tr_skip_out; int bit_cost, qp; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const ts_source &) { return q; }
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &, const ts_source &) { return q; }
+__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t, const ts_source &) { return t; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const ts_source &t) { return t; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const sl_source &, const ts_source &t) { return t; }
+template <typename T, typename U> struct same_type { static constexpr bool value = false; };
+template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
+template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
 
 // Slots: [0, n_y) the N-aligned positions of Y, nx_y per row; then n_c of U and n_c of V, nx_c per row (n_c = 0 for
 // 4:0:0 and for N = 32).  A chroma slot (tx, ty) lies at the luma position (2 N tx, 2 N ty).
@@ -77,7 +90,8 @@ template <int N, typename... PER_LCU>
 __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, quant_consts ky, quant_consts kc,
                                                                 int nx_y, int n_y, int nx_c, int n_c, PER_LCU... per_lcu)
 {
-  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, SL = sizeof...(PER_LCU) == 2;
+  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, SL = pack_has<sl_source, PER_LCU...>, TS = pack_has<ts_source, PER_LCU...>;
+  static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
   constexpr int TPB = 256 / N, W4 = N / 4;
   constexpr int LD = lds_tile_ld(N);
   __shared__ __attribute__((aligned(16))) i16 sa[TPB * N * LD];     // residual / coefficients
@@ -108,6 +122,7 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
 
   quant_consts k = plane ? kc : ky;
   k.qtable = nullptr; k.dqtable = nullptr; k.dq_mode = 0;                  // flat lists only
+  [[maybe_unused]] int tu_qp = 0;                                          // TS: state->qp of the TU's LCU
   if constexpr (LCU_QP) {
     constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
     // ky and kc are not used.  A slot that is no TU runs the barriers with the constants of QP 0 and reads nothing
@@ -117,6 +132,13 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
       const sl_source &t = lists_of(per_lcu...);
       const int qp = valid ? clip_lcu_qp(q.lcu_qp ? (int)q.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)] : t.qp) : 0;
       k = sl_consts(qp, LOG2, plane, 0, q.slice_is_intra, q.signhide, t.quant, t.dequant);
+      if constexpr (TS) tu_qp = qp;
+    } else if constexpr (TS) {
+      // without an array it is the QP of the one-QP entry, which is not clamped
+      const int at = valid ? (int)((size_t)(ly >> 6) * a.lcus_x + (lx >> 6)) : 0;
+      const int qp = q.lcu_qp ? (valid ? clip_lcu_qp(q.lcu_qp[at]) : 0) : skip_of(per_lcu...).qp;
+      k = flat_consts(qp, LOG2, plane, q.slice_is_intra, q.signhide);
+      tu_qp = qp;
     } else {
       const int qp = valid ? clip_lcu_qp(q.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)]) : 0;
       k = flat_consts(qp, LOG2, plane, q.slice_is_intra, q.signhide);
@@ -181,7 +203,7 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
   }
   if (any) atomicOr(&s_has[tu], 1);
   __syncthreads();
-  const int has = s_has[tu];
+  int has = s_has[tu];
   u32 sab = 0;
   if constexpr (SL) {
 #pragma unroll
@@ -207,6 +229,7 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
   transform_2d_lds<N, 1, LD>(ta, tb, row);
   __syncthreads();
   u32 ssd = zssd;                                    // a TU without coefficients keeps its prediction (quant-generic.c:262-271)
+  [[maybe_unused]] u32 keep[W4];                     // TS: the pixels of the trial that stands
   if (has) {
     u32 ow[W4];
     ssd = 0;
@@ -224,7 +247,99 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
       }
       ow[j] = o;
     }
-    if (valid) store_row<N>(rec_row, ow);
+    if constexpr (TS) {
+#pragma unroll
+      for (int j = 0; j < W4; ++j) keep[j] = ow[j];
+    } else {
+      if (valid) store_row<N>(rec_row, ow);
+    }
+  }
+  if constexpr (TS) {
+    // ---- the second trial, use_trskip = 1 (transform.c:253-258), in the same threads on the same registers: kvz_transformskip is a
+    // shift, so nothing crosses rows but the sign-hiding pass and the sums.  A thread reads and writes its own row of ta / tq since
+    // the last barrier; the first trial's row of levels waits in registers.  Chroma slots run it too (the barriers are the
+    // workgroup's) and never take it.
+    const ts_source &ts = skip_of(per_lcu...);
+    const uint2 q1 = make_uint2(*(const u32 *)(tq + row * LD), *(const u32 *)(tq + row * LD + 2));
+    int any2 = 0;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) ta[row * LD + x] = (i16)((byte_of(sw, x) - byte_of(pw, x)) * 32);   // << 5: 15 - 8 - log2 4 (transform.c:151-161)
+    if constexpr (SL) {
+      const int4 f4 = *(const int4 *)(k.qtable + row * 4);
+      const int f[4] = { f4.x, f4.y, f4.z, f4.w };
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int v = quant_listed(ta[row * LD + x], f[x], k);
+        tq[row * LD + x] = (i16)v;
+        any2 |= v;
+      }
+    } else {
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int v = quant_one(ta[row * LD + x], k.flat_qc, k);
+        tq[row * LD + x] = (i16)v;
+        any2 |= v;
+      }
+    }
+    if (k.signhide) {
+      __syncthreads();
+      if (row == 0) {
+        struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { return p[(i / n) * ld + (i % n)]; } };
+        lds_view cv = { ta, LD, 4 }, qv = { tq, LD, 4 };
+        sign_hide_block(cv, qv, 4, 0, k);
+      }
+      __syncthreads();
+      any2 = 0;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) any2 |= tq[row * LD + x];
+    }
+    const int has2 = group_sum<4>(any2 ? 1u : 0u) ? 1 : 0;                 // the TU's four threads are one quad
+    u32 sab2 = 0, ssd2 = zssd, o2 = 0;
+    int res[4];
+    {
+      int d[4] = { 0, 0, 0, 0 };
+      if constexpr (SL) {
+        const int4 d4 = *(const int4 *)(k.dqtable + row * 4);
+        d[0] = d4.x; d[1] = d4.y; d[2] = d4.z; d[3] = d4.w;
+      }
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const int q = tq[row * LD + x];
+        sab2 += (u32)(q < 0 ? -q : q);
+        int c;
+        if constexpr (SL) c = dequant_listed(q, d[x], k);
+        else c = dequant_one(q, row * 4 + x, k);
+        res[x] = (c + 16) >> 5;                                            // kvz_itransformskip (transform.c:169-181)
+      }
+    }
+    if (has2) {
+      ssd2 = 0;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) {
+        const i16 val = (i16)(res[x] + byte_of(pw, x));
+        const int c = val < 0 ? 0 : (val > 255 ? 255 : val);
+        const int d = byte_of(sw, x) - c;
+        ssd2 += (u32)(d * d);
+        o2 |= (u32)c << (8 * x);
+      }
+    }
+    // transform.c:244-266: uint32 costs, the transformed trial wins ties
+    u32 bit_cost = 0;
+    if (valid) {
+      const int v = ts.lcu_bit_cost ? ts.lcu_bit_cost[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)] : ts.bit_cost;
+      bit_cost = (u32)max(v, 0);
+    }
+    const u32 cost1 = group_sum<4>(ssd) + trskip_coeff_cost(group_sum<4>(sab), tu_qp) * bit_cost;
+    const u32 cost2 = group_sum<4>(ssd2) + trskip_coeff_cost(group_sum<4>(sab2), tu_qp) * bit_cost;
+    const bool skip = plane == 0 && cost1 > cost2;
+    if (skip) {
+      has = has2; ssd = ssd2; sab = sab2; keep[0] = o2;
+    } else {
+      *(u32 *)(tq + row * LD) = q1.x;
+      *(u32 *)(tq + row * LD + 2) = q1.y;
+    }
+    if (valid && has) store_row<N>(rec_row, keep);
+    if (valid && plane == 0 && row == 0) ts.tr_skip_out[(size_t)(ly >> 2) * a.cus_stride + (lx >> 2)] = skip ? 1 : 0;
   }
   if (valid) {
     const int bx = (lx & 63) >> (2 + sh), by = (ly & 63) >> (2 + sh);
@@ -285,12 +400,14 @@ void launch_width(int n, const resid_args &a, const quant_consts &ky, const quan
 }
 
 // the three entries: lcu_qp == nullptr is one QP per call (params->qp).  SL: the entry with scaling lists, tables required and checked;
-// it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only
-template <bool SL>
+// it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only.  TS: the 4x4 launch
+// takes *skip (checked by the caller); the launches of the other sizes are those of the entry without it
+template <bool SL, bool TS = false>
 int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                    kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
                    kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
-                   const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
+                   const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s,
+                   const ts_source *skip = nullptr)
 {
   if (!src || !params || !rec_y || !cus || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
     return kvzhip::invalid_arg(entry);
@@ -328,7 +445,17 @@ int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pi
     if constexpr (SL) {
       const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
       const sl_source lists = { tables->quant, tables->dequant, params->qp };
-      launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+      if constexpr (TS) {
+        if (n == 4) launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip);
+        else launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+      } else {
+        launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+      }
+    } else if (TS && n == 4) {
+      if constexpr (TS) {
+        const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+        launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip);
+      }
     } else if (lcu_qp) {
       const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
       launch_width(n, a, ky, kc, chroma, st, per_lcu);

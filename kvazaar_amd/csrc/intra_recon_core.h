@@ -1,5 +1,6 @@
 // intra_recon_core.h -- the kernels and the host side of the whole-picture intra entries (intra_recon.hip: one QP per call,
-// intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture, intra_recon_sl.hip: scaling lists).  Everything here has
+// intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture, intra_recon_sl.hip: scaling lists, intra_recon_ts.hip:
+// transform skip).  Everything here has
 // internal linkage: each of the translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is
 // described in intra_recon.hip.
 #pragma once
@@ -78,16 +79,26 @@ struct tile_rect { int x0, y0, x1, y1; };
 
 struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { return p[(i / n) * ld + (i % n)]; } };
 
+// what a 4x4 luma TU needs for the two trials of transform skip: state->qp and the bit cost of its LCU, and where the choice goes
+struct ts_lcu { int qp; u32 bit_cost; u8 *out; };
+
 // One leaf TU, N wide, by the whole wave.  Called under wave-uniform conditions only.  TILES: tr stands for the picture in everything
 // about the TU's neighbours; without it tr is not read, and the code is compiled from the expressions it always had.  SL: k carries the
 // TU's tables (sl_consts, quant_core.h); a lane reads its row of each, which is contiguous, with 16-byte loads.
-template <int N, bool TILES, bool SL = false>
+// TS (N = 4): a luma TU is coded twice side by side, transformed on lanes 0-3 and transform-skipped on lanes 4-7, which repeat rows
+// 0-3 on a second set of LDS rows (kvz_quantize_residual_trskip, transform.c:229-276).  Both trials share the prediction and run every
+// step in the same instructions; the skipped one replaces the transforms' results by the shifts of kvz_transformskip /
+// kvz_itransformskip.  They meet once, after the reconstruction: each quad sums its SSD and |coeff|, prices its trial, reads the
+// other quad's cost through a lane exchange, and the lanes of the trial that stands write the tile, the coefficients and the flags.
+// The lanes beyond 8 repeat lane % 8.  A chroma TU of the same kernel is coded as without TS.
+template <int N, bool TILES, bool SL = false, bool TS = false>
 __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
-                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq)
+                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq, const ts_lcu ts = {})
 {
+  static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
   constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5, LD = lds_tile_ld(N), W4 = N / 4;
   const int lane = threadIdx.x, row = lane & (N - 1);
-  const bool own = lane < N;                                     // the lanes that touch global memory
+  bool own = lane < N;                                           // the lanes that touch global memory
   const int sh = t.sh, flags = t.plane == 0 ? (KVZ_HIP_INTRA_LUMA | KVZ_HIP_INTRA_FILTER_BOUNDARY) : 0;
 
   // ---- kvz_intra_build_reference (intra.c:334-588) from the tile, as intra_build_reference_kernel takes it from the plane ----
@@ -166,6 +177,13 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
   load_row<N>(a.src[t.plane] + (size_t)(py0 + row) * a.src_stride[t.plane] + px0, sw);      // lanes beyond N: the row of lane % N again
 #pragma unroll
   for (int j = 0; j < W4; ++j) pw[j] = *(const u32 *)(s_pred + row * N + 4 * j);
+  [[maybe_unused]] bool dual = false;                                           // TS: a luma TU, two trials (wave-uniform)
+  [[maybe_unused]] int trial = 0;                                               // TS: 0 transformed, 1 skipped
+  if constexpr (TS) {
+    dual = t.plane == 0;
+    trial = dual ? (lane >> 2) & 1 : 0;
+    ta += trial * 4 * LD; tb += trial * 4 * LD; tq += trial * 4 * LD;          // each trial on LDS rows of its own
+  }
   u32 zssd = 0;
 #pragma unroll
   for (int x = 0; x < N; ++x) {
@@ -181,6 +199,14 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
     transform_2d_lds<N, 0, LD>(ta, tb, row);
   }
   __syncthreads();
+  if constexpr (TS) {
+    // kvz_transformskip (transform.c:151-161): << 15 - 8 - log2 4.  The skipped trial ran the transform above with the other one, on
+    // its own rows, and drops the result
+    if (trial) {
+#pragma unroll
+      for (int x = 0; x < 4; ++x) ta[row * LD + x] = (i16)((byte_of(sw, x) - byte_of(pw, x)) * 32);
+    }
+  }
   int any = 0;
   if constexpr (SL) {
 #pragma unroll
@@ -207,28 +233,49 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
     // group a ballot of the lanes that hold a level
     __syncthreads();
     constexpr int NCG = W4 * W4;
-    const bool cg_ok = lane < NCG;
     const lds_view cv = { ta, LD, N }, qv = { tq, LD, N };
     int pos16[16];
     bool nz = false;
     u32 ac = 0;
+    if constexpr (TS) {
+      // one coefficient group per trial, on the trial's first lane: its ac_sum is the lane's own, and it is the last group if it
+      // holds a level
 #pragma unroll
-    for (int n = 0; n < 16; ++n) {
-      pos16[n] = scan_pos(t.scan, LOG2, ((cg_ok ? lane : 0) << 4) + n);
-      nz = nz || qv[pos16[n]] != 0;
-      if constexpr (SL) ac += (u32)quant_level(cv[pos16[n]], k.qtable[pos16[n]], k);
-      else ac += (u32)quant_level(cv[pos16[n]], k.flat_qc, k);
+      for (int n = 0; n < 16; ++n) {
+        pos16[n] = scan_pos(t.scan, 2, n);
+        nz = nz || qv[pos16[n]] != 0;
+        if constexpr (SL) ac += (u32)quant_level(cv[pos16[n]], k.qtable[pos16[n]], k);
+        else ac += (u32)quant_level(cv[pos16[n]], k.flat_qc, k);
+      }
+      if (lane == 4 * trial && ac >= 2) sign_hide_cg(cv, qv, pos16, nz, k);
+    } else {
+      const bool cg_ok = lane < NCG;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) {
+        pos16[n] = scan_pos(t.scan, LOG2, ((cg_ok ? lane : 0) << 4) + n);
+        nz = nz || qv[pos16[n]] != 0;
+        if constexpr (SL) ac += (u32)quant_level(cv[pos16[n]], k.qtable[pos16[n]], k);
+        else ac += (u32)quant_level(cv[pos16[n]], k.flat_qc, k);
+      }
+      ac = group_sum<64>(cg_ok ? ac : 0u);
+      const unsigned long long bal = __ballot(nz && cg_ok);
+      const bool is_last = nz && (bal & ~((2ull << lane) - 1ull)) == 0ull;
+      if (cg_ok && ac >= 2) sign_hide_cg(cv, qv, pos16, is_last, k);
     }
-    ac = group_sum<64>(cg_ok ? ac : 0u);
-    const unsigned long long bal = __ballot(nz && cg_ok);
-    const bool is_last = nz && (bal & ~((2ull << lane) - 1ull)) == 0ull;
-    if (cg_ok && ac >= 2) sign_hide_cg(cv, qv, pos16, is_last, k);
     __syncthreads();
     any = 0;
 #pragma unroll
     for (int x = 0; x < N; ++x) any |= tq[row * LD + x];
   }
-  const int has = __syncthreads_or(any) ? 1 : 0;
+  int has;
+  if constexpr (TS) {
+    // has_coeffs of the lane's own trial: lanes 0-3 and 4-7 hold the rows of the two trials (of the one trial for a chroma TU)
+    const unsigned long long bal = __ballot(any != 0);
+    __syncthreads();
+    has = ((bal >> (4 * trial)) & 15ull) ? 1 : 0;
+  } else {
+    has = __syncthreads_or(any) ? 1 : 0;
+  }
   u32 sab = 0;
   if constexpr (SL) {
 #pragma unroll
@@ -250,6 +297,11 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
       ta[row * LD + x] = (i16)dequant_one(q, row * N + x, k);
     }
   }
+  [[maybe_unused]] int skipped[4];                                              // TS: kvz_itransformskip (transform.c:169-181) of the lane's row
+  if constexpr (TS) {
+#pragma unroll
+    for (int x = 0; x < 4; ++x) skipped[x] = ((int)ta[row * LD + x] + 16) >> 5;
+  }
   __syncthreads();
   if constexpr (N == 4) {
     if (t.plane == 0) transform_2d_lds<4, 3, LD>(ta, tb, row);
@@ -261,6 +313,7 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
   // the reconstruction goes into the tile; a TU without coefficients keeps its prediction (quant-generic.c:262-271)
   u32 ssd = zssd;
   if (has) ssd = 0;
+  [[maybe_unused]] u32 kept = 0;                                                // TS: the lane's row of its trial's reconstruction
 #pragma unroll
   for (int j = 0; j < W4; ++j) {
     u32 o = pw[j];
@@ -269,14 +322,28 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int x = 4 * j + i;
-        const i16 val = (i16)((int)ta[row * LD + x] + byte_of(pw, x));             // quant-generic.c:255
+        int res = (int)ta[row * LD + x];
+        if constexpr (TS) res = trial ? skipped[x] : res;
+        const i16 val = (i16)(res + byte_of(pw, x));                               // quant-generic.c:255
         const int c = val < 0 ? 0 : (val > 255 ? 255 : val);
         const int d = byte_of(sw, x) - c;
         ssd += (u32)(d * d);
         o |= (u32)c << (8 * i);
       }
     }
-    *(u32 *)(tile + tpx(t.tx + 4 * j, t.ty + row)) = o;                         // tx is a multiple of 4: an aligned dword
+    if constexpr (TS) kept = o;
+    else *(u32 *)(tile + tpx(t.tx + 4 * j, t.ty + row)) = o;                    // tx is a multiple of 4: an aligned dword
+  }
+  if constexpr (TS) {
+    // transform.c:244-266: uint32 costs, the transformed trial wins ties.  The lanes of the trial that stands go on as the TU's lanes
+    bool stands = true;
+    if (dual) {
+      const u32 cost = group_sum<4>(ssd) + trskip_coeff_cost(group_sum<4>(sab), ts.qp) * ts.bit_cost;
+      const u32 other = (u32)__shfl_xor((int)cost, 4, 64);
+      stands = trial ? cost < other : cost <= other;
+    }
+    if (stands) *(u32 *)(tile + tpx(t.tx, t.ty + row)) = kept;
+    own = lane < (dual ? 8 : 4) && stands;
   }
   if (own) {
     const int bx = (t.lx & 63) >> (2 + sh), by = (t.ly & 63) >> (2 + sh);
@@ -297,6 +364,7 @@ __device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, c
           const size_t scu = (size_t)(sy0 + (row >> 2)) * a.cus_stride + sx0 + i;
           ((u8 *)a.cus)[scu * 20 + 4] = (u8)has;
           if (a.cbf_out && has) or_byte(a.cbf_out, scu, 1u);
+          if constexpr (TS) ts.out[scu] = (u8)trial;                                 // cur_pu->tr_skip (transform.c:387)
         }
       }
     } else if (row < N / 2 && a.cbf_out && has) {
@@ -339,6 +407,20 @@ struct sl_source { const int32_t *quant, *dequant; };
 __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &) { return q; }
 __host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &) { return t; }
 __device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l) { return l; }
+// Transform skip (kvz_hip_intra_recon_frame_ts) is the last trailing argument, after the grid or after the lists: the bit cost, one
+// value or one per LCU, and the array of choices.  The workgroup reads its LCU's value once, next to the QP.  Two instantiations, flat
+// lists and tables, in a translation unit of their own (intra_recon_ts.hip).
+struct ts_source { const int32_t *lcu_bit_cost; u8 *tr_skip_out; int bit_cost; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const ts_source &) { return q; }
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &, const ts_source &) { return q; }
+__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const ts_source &) { return t; }
+__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &, const ts_source &) { return t; }
+__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l, const ts_source &) { return l; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const ts_source &t) { return t; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &t) { return t; }
+template <typename T, typename U> struct same_type { static constexpr bool value = false; };
+template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
+template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
 template <bool LCU_QP> struct lcu_sets {};                                   // what a workgroup derives from its LCU's QP: nothing with one QP per call,
 template <> struct lcu_sets<true> { quant_consts k[4]; };                    // else the sets of the four sizes, [log2 N - 2]
 
@@ -355,7 +437,8 @@ static_assert(WG == 64, "one wave per workgroup: see intra_tu");
 template <typename... PER_LCU>
 __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int t, PER_LCU... per_lcu)
 {
-  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2, SL = sizeof...(PER_LCU) == 3;
+  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2, SL = pack_has<sl_source, PER_LCU...>,
+                 TS = pack_has<ts_source, PER_LCU...>;
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -420,6 +503,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   __syncthreads();
 
   lcu_sets<LCU_QP> own;                                                      // the LCU's own sets, [log2 N - 2]
+  [[maybe_unused]] ts_lcu skip = {};
   if constexpr (LCU_QP) {
     const lcu_qp_source &q = only(per_lcu...);
     int qp;
@@ -430,6 +514,11 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
       // (a chroma plane has no 32x32 TU: that set is derived and not used)
       if constexpr (SL) own.k[i] = sl_consts(qp, 2 + i, plane, 1, q.slice_is_intra, q.signhide, lists_of(per_lcu...).quant, lists_of(per_lcu...).dequant);
       else own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, q.slice_is_intra, q.signhide);
+    }
+    if constexpr (TS) {
+      const ts_source &ts = skip_of(per_lcu...);
+      const int v = (int)__builtin_amdgcn_readfirstlane((u32)(ts.lcu_bit_cost ? ts.lcu_bit_cost[(size_t)lcu_y * a.lcus_x + lcu_x] : ts.bit_cost));
+      skip = { qp, (u32)max(v, 0), ts.tr_skip_out };
     }
   }
 
@@ -462,7 +551,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
     if (n == 32) intra_tu<32, TILES, SL>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 16) intra_tu<16, TILES, SL>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 8) intra_tu<8, TILES, SL>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
-    else intra_tu<4, TILES, SL>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else intra_tu<4, TILES, SL, TS>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq, skip);
   }
 
   // ---- the pixels of the intra CUs go back: a row of an SCU (4 luma, 2 chroma pixels) per item, 16 SCUs of a row side by side ----
@@ -490,7 +579,7 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
   if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      (params->scaling_list != 0) != (sizeof...(PER_LCU) == 3))
+      (params->scaling_list != 0) != pack_has<sl_source, PER_LCU...>)
     return kvzhip::invalid_arg(entry);
   if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
                  src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))

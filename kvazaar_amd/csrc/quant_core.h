@@ -140,6 +140,14 @@ __device__ __forceinline__ int quant_listed(int c, int qc, const quant_consts &k
   return clip16(c < 0 ? -level : level);
 }
 
+// kvz_get_coeff_cost below fast_residual_cost_limit (rdo.c:44-45, :219-220): (uint32_t)(sum * (qp * 0.044407704 + 0.557323653) + 0.5)
+// in doubles.  The host rounds each multiply and each add; the intrinsics keep the compiler from contracting them into fused operations,
+// which round once.
+__device__ __forceinline__ u32 trskip_coeff_cost(u32 sum, int qp)
+{
+  return (u32)__dadd_rn(__dmul_rn((double)sum, __dadd_rn(__dmul_rn((double)qp, 0.044407704), 0.557323653)), 0.5);
+}
+
 // ---- sign bit hiding (quant-generic.c:69-162) on one block; coef/q_coef may be
 // global or LDS pointers.  Sequential per block, exactly the reference's control
 // flow (including `abssum` being a signed sum and `cur_change` persisting across

@@ -234,12 +234,13 @@ def main():
         L.kvz_hip_set_tuning(tune_key.encode(), -1)
     if not args.only or any(o in "inter_recon_frame_p inter_recon_frame_b" for o in args.only.split(",")):
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
-    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp" for o in args.only.split(",")):
+    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp inter_residual_frame_1080p_ts" for o in args.only.split(",")):
         inter_residual_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p sao_frame_1080p_tiles4x2" for o in args.only.split(",")):
         sao_frame_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all intra_recon_frame_1080p_mixed_lcu_qp cu_qp_frame_1080p "
-                            "intra_recon_frame_1080p_mixed_tiles4x2 intra_recon_frame_1080p_all_tiles4x2 cu_qp_frame_1080p_tiles4x2" for o in args.only.split(",")):
+                            "intra_recon_frame_1080p_mixed_tiles4x2 intra_recon_frame_1080p_all_tiles4x2 cu_qp_frame_1080p_tiles4x2 "
+                            "intra_recon_frame_1080p_mixed_ts intra_recon_frame_1080p_all_ts intra_recon_frame_1080p_mixed_ts_null intra_recon_frame_1080p_all_ts_null" for o in args.only.split(",")):
         intra_recon_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "deblock_frame_1080p_tiles4x2" for o in args.only.split(",")):
         deblock_tiles_rows(L, st, max(args.rounds, 5), (dby, dbu, dbv, dbc, dbp, DW, DH))
@@ -273,7 +274,10 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
     rounds.  On the mixed picture the same call with a QP per LCU (kvz_hip_intra_recon_frame_qp, QPs 22..42 drawn per LCU) and the QP
     map from its flags (kvz_hip_cu_qp_frame) are timed in the same rounds, interleaved with the one-QP row.  Both pictures also go
     through kvz_hip_intra_recon_frame_tiles with 4 x 2 uniform tiles (rows *_tiles4x2; the mixed picture's QP map through
-    kvz_hip_cu_qp_frame_tiles as well), interleaved with their untiled rows; `launches` is the number of dependent wavefront launches."""
+    kvz_hip_cu_qp_frame_tiles as well), interleaved with their untiled rows; `launches` is the number of dependent wavefront launches.
+    Rows *_ts: the untiled call through kvz_hip_intra_recon_frame_ts with one bit cost (transform skip: every 4x4 luma TU coded twice),
+    in the same rounds; *_ts_null: the same entry with ts == NULL, which runs the kernel of the _tiles entry on one tile -- the
+    instantiation the _ts kernel extends, and so its baseline (the one-QP kernel of the plain row is another instantiation)."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import intra_recon_cases as XC
@@ -322,7 +326,20 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
         def qp_map_tiles():
             return L.kvz_hip_cu_qp_frame_tiles(cus_d.data_ptr(), cbf_d.data_ptr(), W, H, lcu_qp_d.data_ptr(), last_d.data_ptr(), grid.ctypes.data,
                                                tprm.ctypes.data, st)
-        rows = [(name, frame, iters), (name + "_tiles4x2", frame_tiles, iters)]
+        skip_d = torch.zeros(cus.shape, dtype=torch.uint8, device=dev)
+        ts = _lib.TrSkip(58, 0, None)                   # (int)(lambda + 0.5) at QP 32
+
+        def frame_ts():                                  # one QP per call, no tiles, flat lists, as `frame`
+            return L.kvz_hip_intra_recon_frame_ts(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
+                                                  cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
+                                                  cbf_d.data_ptr(), cost_d.data_ptr(), None, None, None, C.byref(ts), skip_d.data_ptr(),
+                                                  prm.ctypes.data, st)
+
+        def frame_ts_null():                             # ts == NULL: the _sl entry, i.e. the _tiles kernel on one tile -- the kernel the _ts one extends
+            return L.kvz_hip_intra_recon_frame_ts(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
+                                                  cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
+                                                  cbf_d.data_ptr(), cost_d.data_ptr(), None, None, None, None, None, prm.ctypes.data, st)
+        rows = [(name, frame, iters), (name + "_ts", frame_ts, iters), (name + "_ts_null", frame_ts_null, iters), (name + "_tiles4x2", frame_tiles, iters)]
         if share < 1.0:
             rows += [(name + "_lcu_qp", frame_qp, iters), ("cu_qp_frame_1080p", qp_map, 20), ("cu_qp_frame_1080p_tiles4x2", qp_map_tiles, 20)]
         cbf_d.zero_()
@@ -429,7 +446,8 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
     without the gather a caller would add -- a lower bound of what the picture cost before the entry existed.  Interleaved round by
     round in one process, medians.  The entry works in place, so every timed call gets a fresh copy of the prediction (copied outside
     the timed region).  At 1080p the same picture with a QP per LCU (kvz_hip_inter_residual_frame_qp, QPs 22..42 drawn per LCU) is timed
-    in the same rounds, interleaved.  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
+    in the same rounds, interleaved, and so is kvz_hip_inter_residual_frame_ts with one bit cost (transform skip: the 4x4 launch codes
+    every luma TU twice).  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
     Algorithmic bytes: 5 per sample = 7.5 per luma pixel, + 20 per 16 luma pixels of map."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -468,6 +486,15 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
             return L.kvz_hip_inter_residual_frame_qp(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
                                                      co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
                                                      lcu_qp_d.data_ptr(), prm.ctypes.data, st)
+        skip_d = torch.zeros(cus.shape, dtype=torch.uint8, device=dev)
+        ts = _lib.TrSkip(58, 0, None)                   # (int)(lambda + 0.5) at QP 32
+
+        def frame_ts():
+            r = recs[turn[0] % len(recs)]
+            turn[0] += 1
+            return L.kvz_hip_inter_residual_frame_ts(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
+                                                     co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
+                                                     None, None, C.byref(ts), skip_d.data_ptr(), prm.ctypes.data, st)
         # the same TUs, contiguous, per (plane, size)
         groups = {}
         for t in RC.walk_tus(cus, W, H):
@@ -497,13 +524,15 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
                     d.copy_(m)
             torch.cuda.synchronize()
             turn[0] = 0
-        t = {"frame": [], "contig": [], "lcu_qp": []}
+        t = {"frame": [], "contig": [], "lcu_qp": [], "ts": []}
         for _ in range(rounds):
             refresh()
             t["frame"].append(timed(L, st, lambda: _lib.check(frame(), name), iters=iters - 1, warm=1))
             if W == 1920:
                 refresh()
                 t["lcu_qp"].append(timed(L, st, lambda: _lib.check(frame_qp(), name + "_lcu_qp"), iters=iters - 1, warm=1))
+                refresh()
+                t["ts"].append(timed(L, st, lambda: _lib.check(frame_ts(), name + "_ts"), iters=iters - 1, warm=1))
             t["contig"].append(timed(L, st, lambda: _lib.check(batches(), name + " contiguous"), iters=iters - 1, warm=1))
         ms, ms_c = float(np.median(t["frame"])), float(np.median(t["contig"]))
         n_tus = sum(c[2] for c in contig)
@@ -515,6 +544,9 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
             ms_q = float(np.median(t["lcu_qp"]))
             print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "_lcu_qp", n_tus, 1e3 / ms_q, nbytes / ms_q / 1e6, ms_q, "-"))
             print("#   %s_lcu_qp over the %d rounds: min..max %.4f..%.4f ms" % (name, rounds, min(t["lcu_qp"]), max(t["lcu_qp"])))
+            ms_t = float(np.median(t["ts"]))
+            print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "_ts", n_tus, 1e3 / ms_t, nbytes / ms_t / 1e6, ms_t, "-"))
+            print("#   %s_ts over the %d rounds: min..max %.4f..%.4f ms" % (name, rounds, min(t["ts"]), max(t["ts"])))
         print("#   fraction of the 8 TB/s HBM roofline: frame %.3f, contiguous sum %.3f; %d launches against %d" %
               (nbytes / ms / 1e6 / 8000, 7.5 * W * H / ms_c / 1e6 / 8000, 5, len(contig)))
         if W != 1920:

@@ -13,7 +13,7 @@ once), so launch overhead, partial waves and tails count the way they do in an e
 tools/bench_all.py, whose batches are sized to hide them.  It is a measurement of the kernels on a
 frame-sized workload, not of an encoder: the mode decision around them is not here.
 
-  python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR] [--scaling-list [default|none]]
+  python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR] [--scaling-list [default|none]] [--transform-skip]
 
 --lcu-qp: the picture chain of a frame whose QP changes per LCU (rate control, --roi): intra reconstruction through
 kvz_hip_intra_recon_frame_qp with a QP array, then kvz_hip_cu_qp_frame (the QP map and the per-LCU predictor), and deblocking
@@ -25,6 +25,9 @@ tests/golden/scaling_list.npz): the residual coding of the inter CUs (kvz_hip_in
 on its planes and its map) and the intra reconstruction (kvz_hip_intra_recon_frame_sl).  `none` passes tables == NULL: the same
 entries, which then launch the kernels of the entries without lists -- the baseline of what the table reads cost.  Combines with
 --lcu-qp and --tiles.
+--transform-skip: both residual calls go through their *_ts entries with one bit cost, (int)(lambda + 0.5) at the frame's QP: every 4x4
+luma TU is coded transformed and transform-skipped and the cheaper trial is kept.  Combines with --lcu-qp, --tiles and --scaling-list
+(without --scaling-list the tables are NULL, as with `none`).
 """
 import argparse
 import ctypes as C
@@ -43,7 +46,7 @@ from kvazaar_amd._lib import QuantParams  # noqa: E402
 W, H = 1920, 1080
 
 
-def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None):
+def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False):
     """-> {stage: [(name, units, launch(stream))]}, plus the tensors kept alive"""
     g = torch.Generator(device=dev); g.manual_seed(7)
     keep = []
@@ -129,7 +132,7 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None):
         ir_qprm = np.zeros(1, dtype=api.CU_QP_PARAMS)
         ir_qprm["start_qp"] = 27
         keep += [ir_qp, ir_cbf, ir_last, ir_qprm]
-    if lists:
+    if lists or trskip:
         # the packed tables on the device; `none`: no tables, and params->scaling_list stays 0
         sl = None
         if lists == "default":
@@ -145,14 +148,29 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None):
         rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
         rc_src_tab = api.ref_picture_table([(rc_src[0].data_ptr(), rc_src[1].data_ptr(), rc_src[2].data_ptr(), W, W // 2)], W, H)
         keep += [rc_co, rc_src, rc_src_tab]
-        stages["tu"].append(("inter_residual_frame_sl", 1, lambda s: L.kvz_hip_inter_residual_frame_sl(
-            rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
-            rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
-            ir_prm.ctypes.data, s)))
-        stages["tu"].append(("intra_recon_frame_sl", 1, lambda s: L.kvz_hip_intra_recon_frame_sl(
-            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
-            ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
-            ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data if tiles else None, sl_ref, ir_prm.ctypes.data, s)))
+        if trskip:
+            # one bit cost, (int)(lambda + 0.5) at QP 27; the choices of the two stages go to an array each (cleared once)
+            ts = _lib.TrSkip(18, 0, None)
+            rc_skip, ir_skip = (torch.zeros(ir_cus.shape, dtype=torch.uint8, device=dev) for _ in range(2))
+            keep += [ts, rc_skip, ir_skip]
+            stages["tu"].append(("inter_residual_frame_ts", 1, lambda s: L.kvz_hip_inter_residual_frame_ts(
+                rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
+                rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
+                C.byref(ts), rc_skip.data_ptr(), ir_prm.ctypes.data, s)))
+            stages["tu"].append(("intra_recon_frame_ts", 1, lambda s: L.kvz_hip_intra_recon_frame_ts(
+                ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+                ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
+                ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data if tiles else None, sl_ref, C.byref(ts), ir_skip.data_ptr(),
+                ir_prm.ctypes.data, s)))
+        else:
+            stages["tu"].append(("inter_residual_frame_sl", 1, lambda s: L.kvz_hip_inter_residual_frame_sl(
+                rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
+                rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
+                ir_prm.ctypes.data, s)))
+            stages["tu"].append(("intra_recon_frame_sl", 1, lambda s: L.kvz_hip_intra_recon_frame_sl(
+                ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+                ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
+                ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data if tiles else None, sl_ref, ir_prm.ctypes.data, s)))
         if lcu_qp and tiles:
             ir_tprm = np.zeros(1, dtype=api.CU_QP_TILES_PARAMS)
             ir_tprm["start_qp"] = 27
@@ -306,6 +324,8 @@ def main():
     ap.add_argument("--tiles", default="", metavar="CxR", help="C x R uniform tiles: the *_tiles entries of intra, QP map, deblocking and SAO")
     ap.add_argument("--scaling-list", nargs="?", const="default", default=None, choices=("default", "none"),
                     help="the *_sl entries of the inter residual coding and the intra reconstruction; `none`: with tables == NULL (the baseline)")
+    ap.add_argument("--transform-skip", action="store_true",
+                    help="the *_ts entries of the inter residual coding and the intra reconstruction, with one bit cost")
     args = ap.parse_args()
     tiles = tuple(int(v) for v in args.tiles.lower().split("x")) if args.tiles else None
     assert tiles is None or len(tiles) == 2
@@ -317,7 +337,7 @@ def main():
     s = L.kvz_hip_stream_create()
     side = [L.kvz_hip_stream_create() for _ in range(7)]
     events = [L.kvz_hip_event_create() for _ in range(8)]
-    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list)
+    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list, args.transform_skip)
     torch.cuda.synchronize()
     n_launch = sum(len(v) for v in stages.values())
 
