@@ -936,7 +936,8 @@ typedef struct {
  *   wide -- with tr_depth READ FROM THE MAP (from the record at the TU's own top-left SCU), not derived from part_size.  Chroma
  *   TUs are half as wide; with 4x4 luma TUs the chroma of the 8x8 area is one 4x4 TU per plane (transform.c:293-313).
  * Per TU: kvz_quantize_residual, rdoq off (quant-generic.c:180-273), cu_is_intra = 0, diagonal scan (kvz_get_scan_order of
- *   an inter CU), no transform skip; bit-exact with the generic strategy at bit depth 8.  OUT OF SCOPE: lossless coding,
+ *   an inter CU), no transform skip; bit-exact with the generic strategy at bit depth 8.  A picture coded with --lossless goes
+ *   through kvz_hip_inter_residual_frame_lossless (below) instead.  OUT OF SCOPE:
  *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID; kvz_hip_inter_residual_frame_sl
  *   below takes them) and per-CU QP (the qp field of the records is not read; a QP per LCU: kvz_hip_inter_residual_frame_qp below).  Intra CUs need their neighbours' reconstruction and are not handled, as in
  *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.
@@ -991,7 +992,8 @@ KVZ_HIP_API int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz
  *   them, taken from the rec plane of that colour (availability follows position alone); kvz_intra_predict with filter_boundary
  *   for luma; kvz_quantize_residual, rdoq off, cu_is_intra = 1 (DST for 4x4 luma), under the scan of kvz_get_scan_order
  *   (encoderstate.c:1384-1398: luma TUs 8 or 4 wide and chroma TUs 4 wide scan vertically for modes 6..14 and horizontally for
- *   22..30), which matters through sign hiding.  No transform skip, no lossless mode.
+ *   22..30), which matters through sign hiding.  No transform skip; a picture coded with --lossless goes through
+ *   kvz_hip_intra_recon_frame_lossless (below) instead.
  * Outputs:
  *   rec planes: the reconstruction inside the intra CUs (a TU without coefficients keeps its prediction); their contents on
  *     entry are never used.
@@ -1081,7 +1083,8 @@ typedef struct {
  *   entry keeps its per-LCU intermediate in lcu_last_qp, so it owns no buffer.)
  * Asynchronous on s; no allocation, no host synchronisation, no atomics; three launches whose shapes depend on width, height and
  * chain_lcus only.  Usable between kvz_hip_graph_begin / _end, and a captured call may be replayed after the contents of the
- * arrays changed.  OUT OF SCOPE: tiles (a chain is a raster run of the picture) and max_qp_delta_depth > 0.
+ * arrays changed.  OUT OF SCOPE: tiles (a chain is a raster run of the picture) and max_qp_delta_depth > 0 (which the reference never
+ * sets: encoder.c:381-383 makes it 0 or -1).
  * A NULL pointer, a misaligned cus, a size that is not a multiple of 8 or below 8, start_qp outside 0..51, a negative chain_lcus or
  * one that is neither 0 nor a multiple of ceil(width / 64) returns KVZ_HIP_ERR_INVALID and nothing is written. */
 KVZ_HIP_API int kvz_hip_cu_qp_frame(kvz_hip_cu_info *cus, const uint8_t *cbf, int width, int height, const int8_t *lcu_qp,
@@ -1274,7 +1277,8 @@ KVZ_HIP_API int kvz_hip_scaling_tables_pack(const int32_t *const quant_coeff[4][
  * In every other respect -- planes and their alignment rules, the CU and transform-tree rules, the coefficient layout, cbf_y /
  *   cbf_out / costs, tiles, error returns, launches, capture -- they are the entries they extend.  A captured call may be replayed
  *   after the CONTENTS of the two arrays changed (the pointers are part of the capture).
- * OUT OF SCOPE: RDOQ and its error_scale, transform skip and lossless coding, parsing --cqmfile, signalling the lists. */
+ * OUT OF SCOPE: RDOQ and its error_scale, transform skip, parsing --cqmfile, signalling the lists.  Lossless coding has entries of
+ * its own, kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below): nothing is quantised there. */
 KVZ_HIP_API int kvz_hip_inter_residual_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
                                                 kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
                                                 kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
@@ -1330,8 +1334,9 @@ typedef struct {
  *   other SCUs are left untouched; the host clears the array once, as it does cbf_out.
  * Equals the reference where cfg.trskip_enable is set and state->qp < cfg.fast_residual_cost_limit (--fast-residual-cost N) holds
  *   for every LCU.  At or above the limit the reference prices coefficients with CABAC on the live context state
- *   (get_coeff_cabac_cost), which is OUT OF SCOPE, as are lossless coding, RDOQ and the transform-skip term of the intra rough
- *   search (search_intra.c:105-167).
+ *   (get_coeff_cabac_cost), which is OUT OF SCOPE, as are RDOQ and the transform-skip term of the intra rough
+ *   search (search_intra.c:105-167).  Lossless coding switches transform skip off (encoder.c:623-628) and has entries of its own:
+ *   kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below).
  * Errors: ts != NULL with tr_skip_out == NULL, with bit_cost < 0 while lcu_bit_cost == NULL, or with lcu_bit_cost not 4-byte
  *   aligned returns KVZ_HIP_ERR_INVALID and nothing is written; so does every error of the _sl entry.
  * Launches and capture: asynchronous, no allocation, no synchronisation with the host, usable between kvz_hip_graph_begin / _end.
@@ -1350,6 +1355,71 @@ KVZ_HIP_API int kvz_hip_intra_recon_frame_ts(const kvz_hip_ref_picture *src, kvz
                                              const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
                                              const kvz_hip_scaling_tables *tables, const kvz_hip_trskip *ts, uint8_t *tr_skip_out,
                                              const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Lossless coding in the picture chain: residual and intra stages     */
+/*   reference: the `if (cfg->lossless)` branch of                     */
+/*   quantize_tr_residual (transform.c:354-369) over bypass_transquant */
+/*   (transform.c:73-100) and rdpcm (transform.c:109-123);             */
+/*   intra_recon_tb_leaf (intra.c:590-638); --lossless,                */
+/*   --implicit-rdpcm                                                  */
+/* ------------------------------------------------------------------ */
+typedef struct {
+  int32_t chroma;          /* 0: 4:0:0 (U / V pointers unused), 1: 4:2:0 */
+  int32_t implicit_rdpcm;  /* encoder->cfg.implicit_rdpcm */
+  int32_t reserved[2];     /* must be 0 */
+} kvz_hip_lossless;        /* 16 bytes; HOST struct, copied at the call */
+
+/* kvz_hip_inter_residual_frame and kvz_hip_intra_recon_frame_tiles for a picture coded with --lossless (cfg.lossless): the same
+ * arguments without params, lcu_qp, tables and transform skip -- there is no QP, no scaling table and no transform skip, because
+ * nothing is transformed or quantised, and encoder.c:623-628 switches sign hiding, transform skip, deblocking and SAO off under
+ * --lossless: the chain of a lossless picture is prediction -> these two entries.
+ * The lossy entries set the rules and they hold here unchanged: argument meanings, the plane, alignment and stride rules (PLANES:
+ *   any base alignment, any strides >= the widths; cus 4-byte aligned, the coefficient arrays 16-byte aligned), which CUs an entry
+ *   owns (CU_INTER / CU_INTRA records with depth 0..3 whose CU lies inside the picture), the transform tree (tr_depth read from the
+ *   map; chroma TUs half as wide, one 4x4 chroma TU per plane per 8x8 area under 4x4 luma TUs), the LCU coefficient layout, cus[].cbf_y,
+ *   cbf_out and costs, and "everything that belongs to other records is left untouched".  No access leaves the planes or arrays,
+ *   whatever the map holds.
+ * kvz_hip_inter_residual_frame_lossless, per TU (bypass_transquant): coeff[x + y * w] = source - prediction, the w * w values at the
+ *   TU's z-order slot in row-major order; rec = source; has_coeffs = any value non-zero.  rec_* hold the PREDICTION on entry, as for
+ *   the lossy entry.  There is no RDPCM for inter CUs, whatever implicit_rdpcm says (transform.c:362: cur_pu->type == CU_INTRA).
+ * kvz_hip_intra_recon_frame_lossless, per TU (intra_recon_tb_leaf, then the same bypass): the reference pixels as
+ *   kvz_hip_intra_build_reference_batch defines them -- with a grid, by the tile rule of kvz_hip_intra_recon_frame_tiles -- TAKEN
+ *   FROM THE SOURCE PLANE of that colour.  The rec planes on entry are never read, not even outside the intra CUs.  The reason: in
+ *   the reference a lossless picture's reconstruction is its source (encoder_set_source_picture, encoderstate.c:1125-1127:
+ *   rec = kvz_image_copy_ref(frame); bypass_transquant writes rec = ref for every TU), so every reference pixel an intra TU reads
+ *   equals the source pixel at that place, whatever was coded before it, and availability follows position alone.  The stage has no
+ *   dependency between TUs and no wavefront.  kvz_intra_predict runs with filter_boundary = luma && !implicit_rdpcm (intra.c:621);
+ *   coeff = source - prediction, rec = source.  With implicit_rdpcm a TU whose mode is 10 gets horizontal DPCM, c[y][x] -= c[y][x - 1]
+ *   for x >= 1, and a TU whose mode is 26 the vertical one, c[y][x] -= c[y - 1][x] for y >= 1 (transform.c:109-123; the reference walks
+ *   from the bottom right, so every subtraction sees the unmodified neighbour).  "Mode" is the luma byte of intra_modes for a luma TU
+ *   and the chroma byte for a chroma TU (transform.c:315-316): a chroma TU in mode 10 or 26 gets DPCM too.  The reference takes
+ *   has_coeffs before the DPCM; DPCM is invertible, so that equals "any STORED value non-zero".  A TU whose mode is above 34 is skipped:
+ *   nothing is written for it, its cbf_out bit is 0 and it adds nothing to the costs.
+ * costs, both entries: ssd_* = 0 (the reconstruction is the source); zero_ssd_* = the SSD of the source against the prediction;
+ *   coeff_abs_* = the sum of |coeff| as stored, i.e. after DPCM.  search.c:580 does not apply the zero-coefficient alternative
+ *   (cu_zero_coeff_cost) under lossless: zero_ssd_* is there for the caller's own use.  Integer sums: the result does not depend on
+ *   scheduling.
+ * cbf_out: the bytes of the owned CUs' SCUs are SET, as by the lossy entries, but with one plain byte store each: the workgroup that
+ *   owns an LCU owns all three planes of it, so no dword around the array is touched and cbf_out may have any alignment.
+ * tiles (intra entry): may be NULL = one tile, the whole picture, byte for byte.  The inter entry does not depend on tiles.
+ * Launches: each entry is ONE kernel launch, Y, U and V together, whatever the picture size, the grid and the map hold: a workgroup
+ *   per LCU.  Asynchronous on s, no host synchronisation, no allocation, no workspace; usable between kvz_hip_graph_begin / _end, and a
+ *   captured call may be replayed after the CONTENTS of cus, intra_modes, the source and the planes changed.
+ * Errors: a NULL ll, a non-zero reserved field, a missing required pointer (intra_modes included, and U / V with chroma = 1), a
+ *   misaligned cus or coefficient array, a size that is not a multiple of 8, a stride below the width or an invalid tile grid returns
+ *   KVZ_HIP_ERR_INVALID and nothing is written.
+ * OUT OF SCOPE: the search side of implicit_rdpcm (search_intra.c:419), PCM, bit depths above 8.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame_lossless(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                      kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c,
+                                                      kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                                      kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                                      const kvz_hip_lossless *ll, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frame_lossless(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                   kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                                   const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                                   kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                                   const kvz_hip_tile_grid *tiles, const kvz_hip_lossless *ll, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */

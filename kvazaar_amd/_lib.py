@@ -70,6 +70,11 @@ class TrSkip(C.Structure):
     _fields_ = [("bit_cost", C.c_int32), ("reserved", C.c_int32), ("lcu_bit_cost", C.c_void_p)]
 
 
+class Lossless(C.Structure):
+    """kvz_hip_lossless"""
+    _fields_ = [("chroma", C.c_int32), ("implicit_rdpcm", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -176,6 +181,8 @@ SIGNATURES = {
     "kvz_hip_inter_residual_frame_ts": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P, _P, _P]),
     "kvz_hip_intra_recon_frame_ts": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P,
                                           _P, _P]),
+    "kvz_hip_inter_residual_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
+    "kvz_hip_intra_recon_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -834,6 +834,61 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
     return out
 
 
+# ---- lossless coding: the two residual stages of a picture coded with --lossless ----
+def inter_residual_frame_lossless(src, pred, cus, chroma=1, implicit_rdpcm=0, coeff=None, cbf_out=None, costs=None):
+    """kvz_hip_inter_residual_frame_lossless.  Arguments and the returned dict as inter_residual_frame, without a QP: coeff = source -
+    prediction, rec = source.  implicit_rdpcm is carried in the struct and does not apply to inter CUs."""
+    return _lossless_frame(None, src, pred, cus, chroma, implicit_rdpcm, None, coeff, cbf_out, costs)
+
+
+def intra_recon_frame_lossless(src, rec, cus, modes, chroma=1, implicit_rdpcm=0, tiles=None, coeff=None, cbf_out=None, costs=None):
+    """kvz_hip_intra_recon_frame_lossless.  As intra_recon_frame without a QP; the reference pixels come from the source planes and rec
+    is only written.  implicit_rdpcm: DPCM for TUs in modes 10 and 26, and no boundary filter.  tiles: a TILE_GRID record or None."""
+    cus = np.ascontiguousarray(cus)
+    modes = np.ascontiguousarray(modes, dtype=np.uint8)
+    assert modes.shape == cus.shape + (2,)
+    return _lossless_frame(modes, src, rec, cus, chroma, implicit_rdpcm, tiles, coeff, cbf_out, costs)
+
+
+def _lossless_frame(modes, src, pred, cus, chroma, implicit_rdpcm, tiles, coeff, cbf_out, costs):
+    """the staging of the two lossless entries; modes None: the inter stage"""
+    L = _lib.init()
+    chroma = int(chroma)
+    height, width = src[0].shape
+    cus = np.ascontiguousarray(cus)
+    assert cus.dtype.itemsize == 20 and cus.shape == (height // 4, width // 4)
+    n = 3 if chroma else 1
+    s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
+    r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
+    ds, dr = [DeviceBuffer.from_numpy(p) for p in s], [DeviceBuffer.from_numpy(p) for p in r]
+    table = ref_picture_table([(ds[0].ptr, ds[1].ptr if chroma else 0, ds[2].ptr if chroma else 0, s[0].shape[1],
+                                s[1].shape[1] if chroma else 0)], width, height)
+    shapes = coeff_shapes(width, height)
+    co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
+          else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
+    dco = [DeviceBuffer.from_numpy(c) for c in co]
+    cb = np.zeros(cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(cus.shape)
+    cs = np.zeros(cus.shape, INTER_RESIDUAL_COST) if costs is None else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(cus.shape)
+    dcb, dcs, dcu = DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(cs.view(np.uint8)), DeviceBuffer.from_numpy(cus.view(np.uint8))
+    ll = _lib.Lossless(chroma, int(implicit_rdpcm), (0, 0))
+    planes = (table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
+              r[1].shape[1] if chroma else 0, dcu.ptr)
+    outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr)
+    if modes is None:
+        check(L.kvz_hip_inter_residual_frame_lossless(*planes, *outs, C.byref(ll), None), "inter_residual frame_lossless")
+    else:
+        dm = DeviceBuffer.from_numpy(modes)
+        g = _grid(tiles) if tiles is not None else None
+        check(L.kvz_hip_intra_recon_frame_lossless(*planes, dm.ptr, *outs, g.ctypes.data if g is not None else None, C.byref(ll), None),
+              "intra_recon frame_lossless")
+    pad = (None,) * (3 - n)
+    return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
+            "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
+            "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
+            "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
+            "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+
+
 # ---- the QP map of a picture whose QP changes per LCU ----
 CU_QP_PARAMS = np.dtype([("start_qp", "<i4"), ("chain_lcus", "<i4")])                            # kvz_hip_cu_qp_params
 CU_QP_TILES_PARAMS = np.dtype([("start_qp", "<i4"), ("chain_rows", "<i4")])                      # kvz_hip_cu_qp_tiles_params

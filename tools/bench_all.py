@@ -234,13 +234,14 @@ def main():
         L.kvz_hip_set_tuning(tune_key.encode(), -1)
     if not args.only or any(o in "inter_recon_frame_p inter_recon_frame_b" for o in args.only.split(",")):
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
-    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp inter_residual_frame_1080p_ts" for o in args.only.split(",")):
+    if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp inter_residual_frame_1080p_ts inter_residual_frame_1080p_lossless" for o in args.only.split(",")):
         inter_residual_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "sao_stats_frame_1080p sao_frame_1080p sao_frame_1080p_tiles4x2" for o in args.only.split(",")):
         sao_frame_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "intra_recon_frame_1080p_mixed intra_recon_frame_1080p_all intra_recon_frame_1080p_mixed_lcu_qp cu_qp_frame_1080p "
                             "intra_recon_frame_1080p_mixed_tiles4x2 intra_recon_frame_1080p_all_tiles4x2 cu_qp_frame_1080p_tiles4x2 "
-                            "intra_recon_frame_1080p_mixed_ts intra_recon_frame_1080p_all_ts intra_recon_frame_1080p_mixed_ts_null intra_recon_frame_1080p_all_ts_null" for o in args.only.split(",")):
+                            "intra_recon_frame_1080p_mixed_ts intra_recon_frame_1080p_all_ts intra_recon_frame_1080p_mixed_ts_null intra_recon_frame_1080p_all_ts_null "
+                            "intra_recon_frame_1080p_mixed_lossless intra_recon_frame_1080p_all_lossless" for o in args.only.split(",")):
         intra_recon_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "deblock_frame_1080p_tiles4x2" for o in args.only.split(",")):
         deblock_tiles_rows(L, st, max(args.rounds, 5), (dby, dbu, dbv, dbc, dbp, DW, DH))
@@ -277,7 +278,10 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
     kvz_hip_cu_qp_frame_tiles as well), interleaved with their untiled rows; `launches` is the number of dependent wavefront launches.
     Rows *_ts: the untiled call through kvz_hip_intra_recon_frame_ts with one bit cost (transform skip: every 4x4 luma TU coded twice),
     in the same rounds; *_ts_null: the same entry with ts == NULL, which runs the kernel of the _tiles entry on one tile -- the
-    instantiation the _ts kernel extends, and so its baseline (the one-QP kernel of the plain row is another instantiation)."""
+    instantiation the _ts kernel extends, and so its baseline (the one-QP kernel of the plain row is another instantiation).
+    Rows *_lossless: the same pictures through kvz_hip_intra_recon_frame_lossless (implicit_rdpcm on), in the same rounds: one launch,
+    no dependence between TUs.  Its traffic -- source read, rec and 2-byte coefficients written, over the intra share of the 4:2:0
+    picture -- and that traffic's share of the 8 TB/s HBM figure are printed below the rows."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import intra_recon_cases as XC
@@ -339,7 +343,14 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
             return L.kvz_hip_intra_recon_frame_ts(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
                                                   cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
                                                   cbf_d.data_ptr(), cost_d.data_ptr(), None, None, None, None, None, prm.ctypes.data, st)
-        rows = [(name, frame, iters), (name + "_ts", frame_ts, iters), (name + "_ts_null", frame_ts_null, iters), (name + "_tiles4x2", frame_tiles, iters)]
+        ll = _lib.Lossless(1, 1, (0, 0))
+
+        def frame_lossless():                            # reads the source only: in place, no fresh copy needed
+            return L.kvz_hip_intra_recon_frame_lossless(table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2,
+                                                        cus_d.data_ptr(), modes_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(),
+                                                        cbf_d.data_ptr(), cost_d.data_ptr(), None, C.byref(ll), st)
+        rows = [(name, frame, iters), (name + "_ts", frame_ts, iters), (name + "_ts_null", frame_ts_null, iters), (name + "_tiles4x2", frame_tiles, iters),
+                (name + "_lossless", frame_lossless, 20)]
         if share < 1.0:
             rows += [(name + "_lcu_qp", frame_qp, iters), ("cu_qp_frame_1080p", qp_map, 20), ("cu_qp_frame_1080p_tiles4x2", qp_map_tiles, 20)]
         cbf_d.zero_()
@@ -351,9 +362,13 @@ def intra_recon_rows(L, st, dev, rounds, iters=3):
         m, _, _ = XC.intra_mask(cus, W, H)
         for (rname, fn, it) in rows:
             ms = float(np.median(t[rname]))
-            launches = 3 if rname.startswith("cu_qp") else n_launch[rname.endswith("_tiles4x2")]
+            launches = 3 if rname.startswith("cu_qp") else (1 if rname.endswith("_lossless") else n_launch[rname.endswith("_tiles4x2")])
             print("%-38s %8.1f %10d %9d %12.1f %10.3f %18s" % (rname, 100 * m.mean(), len(XC.walk_tus(cus, modes, W, H)), launches, 1e3 / ms, ms,
                                                                "%.3f..%.3f" % (min(t[rname]), max(t[rname]))))
+            if rname.endswith("_lossless"):
+                nbytes = m.mean() * 1.5 * W * H * (1 + 1 + 2) + 22.0 * W * H / 16     # source, rec, coefficients; the map and the modes
+                print("#   %s: %.2f MB moved, %.1f GB/s, fraction of the 8 TB/s HBM roofline %.4f" % (rname, nbytes / 1e6, nbytes / ms / 1e6,
+                                                                                                    nbytes / ms / 1e6 / 8000))
 
 
 def inter_recon_rows(L, st, dev, rounds, frames=64):
@@ -447,7 +462,8 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
     round in one process, medians.  The entry works in place, so every timed call gets a fresh copy of the prediction (copied outside
     the timed region).  At 1080p the same picture with a QP per LCU (kvz_hip_inter_residual_frame_qp, QPs 22..42 drawn per LCU) is timed
     in the same rounds, interleaved, and so is kvz_hip_inter_residual_frame_ts with one bit cost (transform skip: the 4x4 launch codes
-    every luma TU twice).  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
+    every luma TU twice), and so is kvz_hip_inter_residual_frame_lossless (one launch: source and prediction read, rec and coefficients
+    written, the same 7.5 bytes per luma pixel).  Then the three-call chain prediction -> residual coding -> deblocking per 1080p picture.
     Algorithmic bytes: 5 per sample = 7.5 per luma pixel, + 20 per 16 luma pixels of map."""
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -495,6 +511,14 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
             return L.kvz_hip_inter_residual_frame_ts(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr(),
                                                      co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(),
                                                      None, None, C.byref(ts), skip_d.data_ptr(), prm.ctypes.data, st)
+        ll = _lib.Lossless(1, 0, (0, 0))
+
+        def frame_lossless():
+            r = recs[turn[0] % len(recs)]
+            turn[0] += 1
+            return L.kvz_hip_inter_residual_frame_lossless(table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2,
+                                                           cus_d.data_ptr(), co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(),
+                                                           cost_d.data_ptr(), C.byref(ll), st)
         # the same TUs, contiguous, per (plane, size)
         groups = {}
         for t in RC.walk_tus(cus, W, H):
@@ -524,7 +548,7 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
                     d.copy_(m)
             torch.cuda.synchronize()
             turn[0] = 0
-        t = {"frame": [], "contig": [], "lcu_qp": [], "ts": []}
+        t = {"frame": [], "contig": [], "lcu_qp": [], "ts": [], "lossless": []}
         for _ in range(rounds):
             refresh()
             t["frame"].append(timed(L, st, lambda: _lib.check(frame(), name), iters=iters - 1, warm=1))
@@ -533,6 +557,8 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
                 t["lcu_qp"].append(timed(L, st, lambda: _lib.check(frame_qp(), name + "_lcu_qp"), iters=iters - 1, warm=1))
                 refresh()
                 t["ts"].append(timed(L, st, lambda: _lib.check(frame_ts(), name + "_ts"), iters=iters - 1, warm=1))
+                refresh()
+                t["lossless"].append(timed(L, st, lambda: _lib.check(frame_lossless(), name + "_lossless"), iters=iters - 1, warm=1))
             t["contig"].append(timed(L, st, lambda: _lib.check(batches(), name + " contiguous"), iters=iters - 1, warm=1))
         ms, ms_c = float(np.median(t["frame"])), float(np.median(t["contig"]))
         n_tus = sum(c[2] for c in contig)
@@ -547,6 +573,10 @@ def inter_residual_rows(L, st, dev, rounds, iters=6):
             ms_t = float(np.median(t["ts"]))
             print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "_ts", n_tus, 1e3 / ms_t, nbytes / ms_t / 1e6, ms_t, "-"))
             print("#   %s_ts over the %d rounds: min..max %.4f..%.4f ms" % (name, rounds, min(t["ts"]), max(t["ts"])))
+            ms_l = float(np.median(t["lossless"]))
+            print("%-28s %10d %12.1f %10.1f %8.4f %8s" % (name + "_lossless", n_tus, 1e3 / ms_l, nbytes / ms_l / 1e6, ms_l, "-"))
+            print("#   %s_lossless over the %d rounds: min..max %.4f..%.4f ms; %.2f MB moved, fraction of the 8 TB/s HBM roofline %.4f; 1 launch" %
+                  (name, rounds, min(t["lossless"]), max(t["lossless"]), nbytes / 1e6, nbytes / ms_l / 1e6 / 8000))
         print("#   fraction of the 8 TB/s HBM roofline: frame %.3f, contiguous sum %.3f; %d launches against %d" %
               (nbytes / ms / 1e6 / 8000, 7.5 * W * H / ms_c / 1e6 / 8000, 5, len(contig)))
         if W != 1920:

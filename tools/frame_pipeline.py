@@ -14,6 +14,7 @@ tools/bench_all.py, whose batches are sized to hide them.  It is a measurement o
 frame-sized workload, not of an encoder: the mode decision around them is not here.
 
   python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR] [--scaling-list [default|none]] [--transform-skip]
+  python tools/frame_pipeline.py --lossless [--tiles CxR]
 
 --lcu-qp: the picture chain of a frame whose QP changes per LCU (rate control, --roi): intra reconstruction through
 kvz_hip_intra_recon_frame_qp with a QP array, then kvz_hip_cu_qp_frame (the QP map and the per-LCU predictor), and deblocking
@@ -28,6 +29,10 @@ entries, which then launch the kernels of the entries without lists -- the basel
 --transform-skip: both residual calls go through their *_ts entries with one bit cost, (int)(lambda + 0.5) at the frame's QP: every 4x4
 luma TU is coded transformed and transform-skipped and the cheaper trial is kept.  Combines with --lcu-qp, --tiles and --scaling-list
 (without --scaling-list the tables are NULL, as with `none`).
+--lossless: the picture chain of a frame coded with --lossless: prediction, then kvz_hip_inter_residual_frame_lossless and
+kvz_hip_intra_recon_frame_lossless (implicit_rdpcm on), one kernel launch each.  The quantising batches, the QP map, deblocking and SAO
+are left out: encoder.c:623-628 switches sign hiding, transform skip, deblocking and SAO off under --lossless.  Combines with --tiles
+(the grid goes to the intra entry); --lcu-qp, --scaling-list and --transform-skip have no meaning without quantisation and are refused.
 """
 import argparse
 import ctypes as C
@@ -46,7 +51,7 @@ from kvazaar_amd._lib import QuantParams  # noqa: E402
 W, H = 1920, 1080
 
 
-def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False):
+def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, lossless=False):
     """-> {stage: [(name, units, launch(stream))]}, plus the tensors kept alive"""
     g = torch.Generator(device=dev); g.manual_seed(7)
     keep = []
@@ -132,6 +137,21 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False):
         ir_qprm = np.zeros(1, dtype=api.CU_QP_PARAMS)
         ir_qprm["start_qp"] = 27
         keep += [ir_qp, ir_cbf, ir_last, ir_qprm]
+    if lossless:
+        # nothing is quantised: the two lossless entries on the maps and planes of the lossy ones, and the chain ends there
+        ll = _lib.Lossless(1, 1, (0, 0))
+        rc_co = [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+        rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
+        rc_src_tab = api.ref_picture_table([(rc_src[0].data_ptr(), rc_src[1].data_ptr(), rc_src[2].data_ptr(), W, W // 2)], W, H)
+        keep += [ll, rc_co, rc_src, rc_src_tab]
+        stages["tu"].append(("inter_residual_frame_lossless", 1, lambda s: L.kvz_hip_inter_residual_frame_lossless(
+            rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
+            rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, C.byref(ll), s)))
+        stages["tu"].append(("intra_recon_frame_lossless", 1, lambda s: L.kvz_hip_intra_recon_frame_lossless(
+            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+            ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), None, None, grid.ctypes.data if tiles else None, C.byref(ll), s)))
+        del stages["sao"]                                            # no deblocking, no SAO (encoder.c:623-628)
+        return stages, keep
     if lists or trskip:
         # the packed tables on the device; `none`: no tables, and params->scaling_list stays 0
         sl = None
@@ -326,7 +346,12 @@ def main():
                     help="the *_sl entries of the inter residual coding and the intra reconstruction; `none`: with tables == NULL (the baseline)")
     ap.add_argument("--transform-skip", action="store_true",
                     help="the *_ts entries of the inter residual coding and the intra reconstruction, with one bit cost")
+    ap.add_argument("--lossless", action="store_true",
+                    help="a frame coded with --lossless: prediction, then the two *_lossless entries; no QP map, deblocking or SAO, which "
+                         "encoder.c:623-628 switches off with sign hiding and transform skip")
     args = ap.parse_args()
+    if args.lossless and (args.lcu_qp or args.scaling_list or args.transform_skip):
+        ap.error("--lossless: nothing is quantised, so --lcu-qp, --scaling-list and --transform-skip do not combine with it")
     tiles = tuple(int(v) for v in args.tiles.lower().split("x")) if args.tiles else None
     assert tiles is None or len(tiles) == 2
     dev = torch.device("cuda", 0)
@@ -337,7 +362,7 @@ def main():
     s = L.kvz_hip_stream_create()
     side = [L.kvz_hip_stream_create() for _ in range(7)]
     events = [L.kvz_hip_event_create() for _ in range(8)]
-    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list, args.transform_skip)
+    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list, args.transform_skip, args.lossless)
     torch.cuda.synchronize()
     n_launch = sum(len(v) for v in stages.values())
 
@@ -363,8 +388,9 @@ def main():
         from kvazaar_amd import api
         g = api.uniform_tile_grid(W, H, tiles[0], tiles[1])
         waves = int(max(np.diff(g["col_bd"][0, :tiles[0] + 1])) + 2 * (max(np.diff(g["row_bd"][0, :tiles[1] + 1])) - 1))
-    print("%-34s %9s %10.1f   (%d calls; the intra reconstruction is %d kernel launches of its own)" % ("sum of the entries", "", total * 1e3, n_launch,
-                                                                                               1 + waves))
+    print("%-34s %9s %10.1f   (%d calls; the intra reconstruction is %d kernel launch%s of its own)" % ("sum of the entries", "", total * 1e3, n_launch,
+                                                                                                  1 if args.lossless else 1 + waves,
+                                                                                                  "" if args.lossless else "es"))
 
     results = {}
     results["eager"] = run(L, s, args.frames, lambda: enqueue_serial(stages, s))
