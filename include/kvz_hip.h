@@ -1422,6 +1422,59 @@ KVZ_HIP_API int kvz_hip_intra_recon_frame_lossless(const kvz_hip_ref_picture *sr
                                                    const kvz_hip_tile_grid *tiles, const kvz_hip_lossless *ll, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
+/* Several independent pictures through the residual stages at once    */
+/*   reference: the pictures the encoder keeps in flight (--owf):      */
+/*   every picture under --period 1, the pictures of the highest       */
+/*   temporal layer of a GOP 8                                         */
+/* ------------------------------------------------------------------ */
+#define KVZ_HIP_MAX_CHAIN_PICTURES 16
+/* One picture of a multi-picture call: the arguments of kvz_hip_inter_residual_frame_qp / kvz_hip_intra_recon_frame_qp as a record.
+ * Every pointer in it is DEVICE memory; the record itself is HOST memory, copied at the call.  Offsets in front of the fields. */
+typedef struct {
+  kvz_hip_ref_picture src;              /*   0: the source picture; its width / height are the picture's */
+  kvz_hip_pixel *rec_y, *rec_u, *rec_v; /*  40, 48, 56 */
+  uint32_t stride_y, stride_c;          /*  64, 68 */
+  kvz_hip_cu_info *cus;                 /*  72 */
+  const uint8_t *intra_modes;           /*  80: read by kvz_hip_intra_recon_frames only; kvz_hip_inter_residual_frames ignores it */
+  kvz_hip_coeff *coeff_y, *coeff_u, *coeff_v;   /* 88, 96, 104 */
+  uint8_t *cbf_out;                     /* 112: optional */
+  kvz_hip_inter_residual_cost *costs;   /* 120: optional */
+  const int8_t *lcu_qp;                 /* 128: optional; NULL = params.qp in every LCU */
+  kvz_hip_inter_residual_params params; /* 136: qp, slice_is_intra, signhide, scaling_list (must be 0), chroma */
+} kvz_hip_chain_picture;                /* 160 bytes */
+/* kvz_hip_inter_residual_frame_qp and kvz_hip_intra_recon_frame_qp for n_pictures (0..KVZ_HIP_MAX_CHAIN_PICTURES) pictures that do not
+ * depend on each other, in one asynchronous call.  A launch of the single-picture intra entry is one wave per LCU row and plane -- 51
+ * waves at 1080p -- and the launches of one picture depend on each other; independent pictures share the launches instead, as the
+ * tiles of one picture do in kvz_hip_intra_recon_frame_tiles.
+ * THE RULE: for every picture i and every output array, the result is byte for byte what kvz_hip_inter_residual_frame_qp /
+ *   kvz_hip_intra_recon_frame_qp leaves when called with the fields of pictures[i] -- lcu_qp == NULL included, which means that
+ *   picture's params.qp in every LCU (not clamped, as in the one-QP entries; the values of an array are clamped into 0..51).
+ *   Everything those entries define holds per picture: which CUs are handled and the transform tree, scans and sign hiding, the
+ *   coefficient layout, cbf_y written back into cus, cbf_out and costs, the alignment and stride rules, and "everything that belongs
+ *   to other records is left untouched".  Pictures of one call may differ in size, chroma format (4:0:0 next to 4:2:0), QP, signhide
+ *   and slice_is_intra, and in whether they carry lcu_qp, cbf_out and costs.
+ * Independence is the caller's promise: no output of one record may be an input or an output of another; sources may be shared.
+ *   Records whose rec_y, cus or coeff_y base pointers coincide are refused.  Any other overlap is a caller error with unspecified
+ *   output, but no access leaves a record's own arrays.
+ * Errors: n_pictures == 0 is a no-op that returns KVZ_HIP_OK (pictures may then be NULL).  KVZ_HIP_ERR_INVALID: n_pictures below 0 or
+ *   above KVZ_HIP_MAX_CHAIN_PICTURES, pictures == NULL, or any record that the single-picture entry would refuse -- a missing pointer,
+ *   a misaligned cus / coefficient / costs array, a bad size or stride, scaling_list != 0, a negative params.qp without lcu_qp.  Every
+ *   record is checked before anything is launched: on refusal nothing is written for any picture, and kvz_hip_last_error() names the
+ *   index of the offending record ("picture 2").
+ * Execution: asynchronous on s; no host synchronisation, no allocation, no workspace -- the call owns no device buffer; the records
+ *   travel in the kernel arguments (152 / 136 bytes per picture) and a workgroup reads its own with scalar loads.  Usable between
+ *   kvz_hip_graph_begin / _end.  The launch shapes depend only on the sizes, the chroma flags and the presence of cbf_out / costs: a
+ *   captured call may be replayed after the CONTENTS of every device array changed.
+ * Launches: kvz_hip_intra_recon_frames makes max over the pictures of ceil(width / 64) + 2 (ceil(height / 64) - 1) wavefront launches,
+ *   plus one init launch if any picture has cbf_out or costs; launch t holds wave t of every picture.  kvz_hip_inter_residual_frames
+ *   makes the single entry's launches (one per transform size, plus the init launch), each covering all pictures.
+ * LEFT OUT ON PURPOSE: pictures with tiles, scaling lists or transform skip and pictures coded with --lossless stay with their
+ *   single-picture entries (_tiles, _sl, _ts, _lossless); prediction (kvz_hip_inter_recon_frame), the QP map, deblocking and SAO of
+ *   several pictures are follow-ups.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_residual_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */
 /* ------------------------------------------------------------------ */
 /* kvz_strategyselector_register (strategyselector.h:87, strategyselector.c:216-256) */

@@ -75,6 +75,29 @@ class Lossless(C.Structure):
     _fields_ = [("chroma", C.c_int32), ("implicit_rdpcm", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class RefPicture(C.Structure):
+    """kvz_hip_ref_picture"""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("stride_y", C.c_uint32), ("stride_c", C.c_uint32),
+                ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class InterResidualParams(C.Structure):
+    """kvz_hip_inter_residual_params"""
+    _fields_ = [("qp", C.c_int32), ("slice_is_intra", C.c_int32), ("signhide", C.c_int32), ("scaling_list", C.c_int32),
+                ("chroma", C.c_int32), ("reserved", C.c_int32)]
+
+
+MAX_CHAIN_PICTURES = 16      # KVZ_HIP_MAX_CHAIN_PICTURES
+
+
+class ChainPicture(C.Structure):
+    """kvz_hip_chain_picture"""
+    _fields_ = [("src", RefPicture), ("rec_y", C.c_void_p), ("rec_u", C.c_void_p), ("rec_v", C.c_void_p),
+                ("stride_y", C.c_uint32), ("stride_c", C.c_uint32), ("cus", C.c_void_p), ("intra_modes", C.c_void_p),
+                ("coeff_y", C.c_void_p), ("coeff_u", C.c_void_p), ("coeff_v", C.c_void_p), ("cbf_out", C.c_void_p),
+                ("costs", C.c_void_p), ("lcu_qp", C.c_void_p), ("params", InterResidualParams)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -183,6 +206,8 @@ SIGNATURES = {
                                           _P, _P]),
     "kvz_hip_inter_residual_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_intra_recon_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
+    "kvz_hip_inter_residual_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
+    "kvz_hip_intra_recon_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -834,6 +834,84 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
     return out
 
 
+# ---- several independent pictures through the two residual stages in one call ----
+MAX_CHAIN_PICTURES = _lib.MAX_CHAIN_PICTURES                       # KVZ_HIP_MAX_CHAIN_PICTURES
+
+
+def inter_residual_frames(pictures):
+    """kvz_hip_inter_residual_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of
+    inter_residual_frame by name (src, pred, cus, qp; optional chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp).
+    Returns the list of inter_residual_frame's result dicts, one per picture."""
+    return _chain_frames(False, pictures)
+
+
+def intra_recon_frames(pictures):
+    """kvz_hip_intra_recon_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of intra_recon_frame
+    by name (src, rec, cus, modes, qp; optional chroma, signhide, slice_is_intra, coeff, cbf_out, costs, lcu_qp).  Returns the list of
+    intra_recon_frame's result dicts, one per picture."""
+    return _chain_frames(True, pictures)
+
+
+class _ChainPicture:
+    """the arrays of one picture of a multi-picture call on the device, and its record"""
+
+    def __init__(self, intra, src, cus, qp, pred=None, rec=None, modes=None, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None,
+                 costs=None, lcu_qp=None):
+        pred = rec if intra else pred
+        chroma = int(chroma)
+        height, width = src[0].shape
+        self.cus = np.ascontiguousarray(cus)
+        assert self.cus.dtype.itemsize == 20 and self.cus.shape == (height // 4, width // 4)
+        n = self.n = 3 if chroma else 1
+        s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
+        self.r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
+        self.ds, self.dr = [DeviceBuffer.from_numpy(p) for p in s], [DeviceBuffer.from_numpy(p) for p in self.r]
+        shapes = coeff_shapes(width, height)
+        self.co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
+                   else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
+        self.dco = [DeviceBuffer.from_numpy(c) for c in self.co]
+        self.cb = np.zeros(self.cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(self.cus.shape)
+        self.cs = (np.zeros(self.cus.shape, INTER_RESIDUAL_COST) if costs is None
+                   else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(self.cus.shape))
+        self.dcb, self.dcs = DeviceBuffer.from_numpy(self.cb), DeviceBuffer.from_numpy(self.cs.view(np.uint8))
+        self.dcu = DeviceBuffer.from_numpy(self.cus.view(np.uint8))
+        rec = _lib.ChainPicture()
+        rec.src = _lib.RefPicture(self.ds[0].ptr, self.ds[1].ptr if chroma else None, self.ds[2].ptr if chroma else None, s[0].shape[1],
+                                  s[1].shape[1] if chroma else 0, width, height)
+        rec.rec_y, rec.stride_y = self.dr[0].ptr, self.r[0].shape[1]
+        if chroma:
+            rec.rec_u, rec.rec_v, rec.stride_c = self.dr[1].ptr, self.dr[2].ptr, self.r[1].shape[1]
+            rec.coeff_u, rec.coeff_v = self.dco[1].ptr, self.dco[2].ptr
+        rec.cus, rec.coeff_y, rec.cbf_out, rec.costs = self.dcu.ptr, self.dco[0].ptr, self.dcb.ptr, self.dcs.ptr
+        if intra:
+            m = np.ascontiguousarray(modes, dtype=np.uint8)
+            assert m.shape == self.cus.shape + (2,)
+            self.dm = DeviceBuffer.from_numpy(m)
+            rec.intra_modes = self.dm.ptr
+        if lcu_qp is not None:
+            self.dq = DeviceBuffer.from_numpy(np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(lcu_count(width, height)))
+            rec.lcu_qp = self.dq.ptr
+        rec.params = _lib.InterResidualParams(int(qp), int(slice_is_intra), int(signhide), 0, chroma, 0)
+        self.record = rec
+
+    def result(self):
+        pad = (None,) * (3 - self.n)
+        return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(self.dr, self.r)) + pad,
+                "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(self.dco, self.co)) + pad,
+                "cus": self.dcu.to_numpy(np.uint8, self.cus.shape + (20,)).view(self.cus.dtype).reshape(self.cus.shape),
+                "cbf_out": self.dcb.to_numpy(np.uint8, self.cb.shape),
+                "costs": self.dcs.to_numpy(np.uint8, self.cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(self.cs.shape)}
+
+
+def _chain_frames(intra, pictures):
+    L = _lib.init()
+    staged = [_ChainPicture(intra, **p) for p in pictures]
+    records = (_lib.ChainPicture * max(len(staged), 1))(*[st.record for st in staged])
+    entry = L.kvz_hip_intra_recon_frames if intra else L.kvz_hip_inter_residual_frames
+    check(entry(records, len(staged), None), "intra_recon frames" if intra else "inter_residual frames")
+    return [st.result() for st in staged]
+
+
 # ---- lossless coding: the two residual stages of a picture coded with --lossless ----
 def inter_residual_frame_lossless(src, pred, cus, chroma=1, implicit_rdpcm=0, coeff=None, cbf_out=None, costs=None):
     """kvz_hip_inter_residual_frame_lossless.  Arguments and the returned dict as inter_residual_frame, without a QP: coeff = source -

@@ -1,5 +1,5 @@
 // inter_residual_core.h -- the kernels and the host side of the whole-picture inter residual entries (inter_residual.hip: one QP per
-// call and a QP per LCU; inter_residual_sl.hip: scaling lists; inter_residual_ts.hip: transform skip).  Everything here has internal linkage: each translation unit gets
+// call and a QP per LCU; inter_residual_sl.hip: scaling lists; inter_residual_ts.hip: transform skip; inter_residual_multi.hip: several pictures in one call).  Everything here has internal linkage: each translation unit gets
 // its own copy and instantiates its own kernels.  The algorithm is described in inter_residual.hip.
 #pragma once
 
@@ -27,9 +27,35 @@ struct resid_args {
   int width, height;
 };
 
+// One picture of a multi-picture call (kvz_hip_inter_residual_frames): resid_args under the same member names, and what a TU derives
+// its constants from (flat_consts with lcu_qp[] or qp, as the per-LCU kernel).  136 bytes; sixteen of them are the kernel's argument,
+// and a workgroup reads its own at blockIdx.y: every address is wave-uniform and in the kernel-argument segment, so the fields come
+// through scalar loads into scalar registers.
+struct resid_pic {
+  const u8 *src_y, *src_u, *src_v;
+  u8 *rec_y, *rec_u, *rec_v;
+  i16 *coeff_y, *coeff_u, *coeff_v;
+  u32 *cus;
+  u8 *cbf_out;                   // or nullptr
+  u32 *cost;                     // or nullptr
+  const int8_t *lcu_qp;          // or nullptr: qp in every LCU
+  u32 src_stride_y, src_stride_c, rec_stride_y, rec_stride_c;
+  int qp;
+  uint16_t width, height, cus_stride, lcus_x;      // a picture is at most 16384 wide and high
+  u8 chroma, slice_is_intra, signhide, pad;
+};
+struct resid_batch { resid_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; };
+static_assert(sizeof(resid_pic) == 136 && sizeof(resid_batch) <= 3072, "the records travel in the kernel arguments");
+// The kernel works on a COPY of its picture's block, which the compiler takes apart into the loads of the fields that are used: for
+// resid_args that is the kernel as it was compiled with the argument itself, instruction for instruction, which a reference to the
+// argument is not (tools/compare_kernels.py); for resid_pic they are scalar loads at an offset that blockIdx.y gives.
+__device__ __forceinline__ resid_args picture_of(const resid_args &a) { return a; }
+__device__ __forceinline__ resid_pic picture_of(const resid_batch &b) { return b.p[blockIdx.y]; }
+
 // the inter CU that holds the luma position (x, y), from the record of that position alone: false for another type, a
 // depth beyond 3 or a CU that would leave the picture (the rule of kvz_hip_inter_recon_frame)
-__device__ __forceinline__ bool inter_cu_at(const resid_args &a, int x, int y, int &cu_x, int &cu_y, int &leaf)
+template <typename ARGS>
+__device__ __forceinline__ bool inter_cu_at(const ARGS &a, int x, int y, int &cu_x, int &cu_y, int &leaf)
 {
   const u32 head = a.cus[((size_t)(y >> 2) * a.cus_stride + (x >> 2)) * 5];
   const int depth = (head >> 8) & 255, trd = (int)(head >> 24);
@@ -86,11 +112,14 @@ template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>:
 
 // Slots: [0, n_y) the N-aligned positions of Y, nx_y per row; then n_c of U and n_c of V, nx_c per row (n_c = 0 for
 // 4:0:0 and for N = 32).  A chroma slot (tx, ty) lies at the luma position (2 N tx, 2 N ty).
-template <int N, typename... PER_LCU>
-__global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, quant_consts ky, quant_consts kc,
+// Several pictures (ARGS = resid_batch, kvz_hip_inter_residual_frames): grid (workgroups of the picture with the most slots, pictures);
+// the workgroup takes its picture's record at blockIdx.y, counts that picture's slots itself (ky, kc and the four counts are not read)
+// and derives every TU's constants as the per-LCU kernel does.
+template <int N, typename ARGS, typename... PER_LCU>
+__global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant_consts ky, quant_consts kc,
                                                                 int nx_y, int n_y, int nx_c, int n_c, PER_LCU... per_lcu)
 {
-  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, SL = pack_has<sl_source, PER_LCU...>, TS = pack_has<ts_source, PER_LCU...>;
+  constexpr bool MULTI = same_type<ARGS, resid_batch>::value, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, SL = pack_has<sl_source, PER_LCU...>, TS = pack_has<ts_source, PER_LCU...>;
   static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
   constexpr int TPB = 256 / N, W4 = N / 4;
   constexpr int LD = lds_tile_ld(N);
@@ -99,6 +128,12 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
   __shared__ __attribute__((aligned(16))) i16 sq[TPB * N * LD];     // quantized coefficients
   __shared__ int s_has[TPB];
 
+  const auto a = picture_of(args);                                         // the call's picture, or this workgroup's
+  if constexpr (MULTI) {
+    // launch_size below, per picture; a workgroup beyond its picture's slots leaves with the others that hold no TU
+    nx_y = (a.width + N - 1) / N; n_y = nx_y * ((a.height + N - 1) / N);
+    nx_c = ((a.width >> 1) + N - 1) / N; n_c = (a.chroma && N < 32) ? nx_c * (((a.height >> 1) + N - 1) / N) : 0;
+  }
   const int tid = threadIdx.x, tu = tid / N, row = tid % N;
   const int slot = blockIdx.x * TPB + tu;
   int plane = 0, lx = 0, ly = 0, cu_x = 0, cu_y = 0, leaf = 0;
@@ -123,7 +158,13 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(resid_args a, qu
   quant_consts k = plane ? kc : ky;
   k.qtable = nullptr; k.dqtable = nullptr; k.dq_mode = 0;                  // flat lists only
   [[maybe_unused]] int tu_qp = 0;                                          // TS: state->qp of the TU's LCU
-  if constexpr (LCU_QP) {
+  if constexpr (MULTI) {
+    // the array's value clamped as in the per-LCU entry, or the picture's QP as it stands as in the one-QP entry; a slot that is no
+    // TU runs the barriers with the constants of QP 0 and reads nothing
+    constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
+    const int qp = valid ? (a.lcu_qp ? clip_lcu_qp(a.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)]) : a.qp) : 0;
+    k = flat_consts(qp, LOG2, plane, a.slice_is_intra, a.signhide);
+  } else if constexpr (LCU_QP) {
     constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
     // ky and kc are not used.  A slot that is no TU runs the barriers with the constants of QP 0 and reads nothing
     const lcu_qp_source &q = only(per_lcu...);
@@ -387,7 +428,7 @@ void launch_size(const resid_args &a, const quant_consts &ky, const quant_consts
   const int nx_c = (cw + N - 1) / N, n_c = (chroma && N < 32) ? nx_c * ((chh + N - 1) / N) : 0;
   constexpr int TPB = 256 / N;
   const int slots = n_y + 2 * n_c;
-  hipLaunchKernelGGL((inter_residual_tu_kernel<N, PER_LCU...>), dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(256), 0, st, a, ky, kc, nx_y, n_y, nx_c, n_c, q...);
+  hipLaunchKernelGGL((inter_residual_tu_kernel<N, resid_args, PER_LCU...>), dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(256), 0, st, a, ky, kc, nx_y, n_y, nx_c, n_c, q...);
 }
 
 template <typename... PER_LCU>
@@ -402,6 +443,24 @@ void launch_width(int n, const resid_args &a, const quant_consts &ky, const quan
 // the three entries: lcu_qp == nullptr is one QP per call (params->qp).  SL: the entry with scaling lists, tables required and checked;
 // it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only.  TS: the 4x4 launch
 // takes *skip (checked by the caller); the launches of the other sizes are those of the entry without it
+// what every entry requires of one picture's arguments, the QP and the tables aside; lists: the entry takes scaling lists
+inline bool residual_frame_args_ok(const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
+                                   const kvz_hip_pixel *rec_v, uint32_t stride_c, const kvz_hip_cu_info *cus, const kvz_hip_coeff *coeff_y,
+                                   const kvz_hip_coeff *coeff_u, const kvz_hip_coeff *coeff_v, const kvz_hip_inter_residual_cost *costs,
+                                   const kvz_hip_inter_residual_params *params, bool lists)
+{
+  if (!src || !params || !rec_y || !cus || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
+    return false;
+  const int width = src->width, height = src->height;
+  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
+      (params->scaling_list != 0) != lists)
+    return false;
+  if (params->chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
+                         src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
+    return false;
+  return true;
+}
+
 template <bool SL, bool TS = false>
 int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                    kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
@@ -409,16 +468,10 @@ int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pi
                    const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s,
                    const ts_source *skip = nullptr)
 {
-  if (!src || !params || !rec_y || !cus || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
+  if (!residual_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, costs, params, SL))
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      (params->scaling_list != 0) != SL)
-    return kvzhip::invalid_arg(entry);
   if (SL && (!tables || !tables->quant || !tables->dequant || (((uintptr_t)tables->quant | (uintptr_t)tables->dequant) & 15)))
-    return kvzhip::invalid_arg(entry);
-  if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
-                 src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
     return kvzhip::invalid_arg(entry);
   const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
   quant_consts ky = {}, kc = {};                                              // not read with a QP array

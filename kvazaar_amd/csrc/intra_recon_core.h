@@ -1,6 +1,6 @@
 // intra_recon_core.h -- the kernels and the host side of the whole-picture intra entries (intra_recon.hip: one QP per call,
 // intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture, intra_recon_sl.hip: scaling lists, intra_recon_ts.hip:
-// transform skip).  Everything here has
+// transform skip, intra_recon_multi.hip: several pictures in one call).  Everything here has
 // internal linkage: each of the translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is
 // described in intra_recon.hip.
 #pragma once
@@ -32,6 +32,29 @@ struct intra_args {
   int width, height;
   quant_consts k[2][4];          // [luma / chroma][log2 N - 2]
 };
+
+// One picture of a multi-picture call (kvz_hip_intra_recon_frames): what intra_args holds without the host-made constants, under the
+// same member names, and what the workgroup derives its constants from instead (flat_consts with lcu_qp[] or qp, as the per-LCU
+// kernel does).  152 bytes; sixteen of them are the kernel's argument, and a workgroup reads its own at blockIdx.z: every address is
+// wave-uniform and in the kernel-argument segment, so the fields come through scalar loads into scalar registers.
+struct intra_pic {
+  const u8 *src[3];
+  u8 *rec[3];
+  i16 *coeff[3];
+  u32 *cus;
+  const u8 *modes;
+  u8 *cbf_out;                   // or nullptr
+  u32 *cost;                     // or nullptr
+  const int8_t *lcu_qp;          // or nullptr: qp in every LCU
+  u32 src_stride[3], rec_stride[3];
+  int qp;
+  uint16_t width, height, cus_stride, lcus_x;      // a picture is at most 16384 wide and high
+  u8 chroma, slice_is_intra, signhide, pad;
+};
+struct intra_batch { intra_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; };
+static_assert(sizeof(intra_pic) == 152 && sizeof(intra_batch) <= 3072, "the records travel in the kernel arguments");
+template <typename ARGS> struct picture_type { using type = ARGS; };
+template <> struct picture_type<intra_batch> { using type = intra_pic; };
 
 // The LCU's tile in LDS: pixel (x, y) of the plane relative to the LCU's top-left, x = -1 .. T + T/2 - 1, y = -1 .. T - 1
 // (T = 64 luma, 32 chroma).  Column 0 stands at a dword boundary.
@@ -91,8 +114,8 @@ struct ts_lcu { int qp; u32 bit_cost; u8 *out; };
 // kvz_itransformskip.  They meet once, after the reconstruction: each quad sums its SSD and |coeff|, prices its trial, reads the
 // other quad's cost through a lane exchange, and the lanes of the trial that stands write the tile, the coefficients and the flags.
 // The lanes beyond 8 repeat lane % 8.  A chroma TU of the same kernel is coded as without TS.
-template <int N, bool TILES, bool SL = false, bool TS = false>
-__device__ __forceinline__ void intra_tu(const intra_args &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
+template <int N, bool TILES, bool SL = false, bool TS = false, typename ARGS>
+__device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
                                         u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq, const ts_lcu ts = {})
 {
   static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
@@ -429,15 +452,17 @@ __device__ __forceinline__ int compact4(int i) { i &= 0x55; i = (i | (i >> 1)) &
 
 // wave t of the picture: grid (lcus_y, planes), LCU (t - 2 ly, ly).  Tiled: grid (lcus_y * cols, planes), a workgroup per LCU row and
 // tile column, LCU (x0 + t - 2 (ly - y0), ly) of the tile that begins at LCU (x0, y0): the waves of all tiles share the launches, and the
-// rectangle that stands for the picture in everything about neighbours is the tile.  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
+// rectangle that stands for the picture in everything about neighbours is the tile.  Several pictures (ARGS = intra_batch,
+// kvz_hip_intra_recon_frames): grid (max lcus_y, planes, pictures); the workgroup takes its picture's record at blockIdx.z, leaves at
+// once where that picture has no such plane, row or wave, and derives its constants as the per-LCU kernel does.  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
 // the lanes beyond a TU's N rows repeat row lane % N, which is the same value to the same LDS address only while all of them are
 // one wave in lockstep; with a second wave the read-modify-write of ta / tq would race.
 constexpr int WG = 64;
 static_assert(WG == 64, "one wave per workgroup: see intra_tu");
-template <typename... PER_LCU>
-__global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int t, PER_LCU... per_lcu)
+template <typename ARGS, typename... PER_LCU>
+__global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, PER_LCU... per_lcu)
 {
-  constexpr bool LCU_QP = sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2, SL = pack_has<sl_source, PER_LCU...>,
+  constexpr bool MULTI = same_type<ARGS, intra_batch>::value, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2, SL = pack_has<sl_source, PER_LCU...>,
                  TS = pack_has<ts_source, PER_LCU...>;
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
@@ -448,8 +473,16 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   __shared__ __attribute__((aligned(16))) i16 sq[32 * lds_tile_ld(32)];     // quantized coefficients
   __shared__ u8 s_intra[256];                                                // SCU (raster) belongs to an intra CU of this call
 
+  // the call's picture, or this workgroup's: picture blockIdx.z of the table.  Bound without a call in between: through a function the
+  // one-QP kernel is no longer compiled to the code it was (tools/compare_kernels.py)
+  using PIC = typename picture_type<ARGS>::type;
+  const PIC &a = ((const PIC *)&args)[MULTI ? blockIdx.z : 0];
   const int lane = threadIdx.x, plane = blockIdx.y, sh = plane ? 1 : 0;
   int lcu_y = blockIdx.x, lcu_x = t - 2 * lcu_y;
+  if constexpr (MULTI) {
+    // the grid is that of the tallest picture with chroma (a wave of a picture that has run out fails the test of lcu_x below)
+    if ((plane && !a.chroma) || 64 * lcu_y >= a.height) return;
+  }
   tile_rect tr;                                                              // read with tiles only
   if constexpr (TILES) {
     // wave-uniform: scalar loads of the grid, scalar compares and selects
@@ -504,7 +537,12 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
 
   lcu_sets<LCU_QP> own;                                                      // the LCU's own sets, [log2 N - 2]
   [[maybe_unused]] ts_lcu skip = {};
-  if constexpr (LCU_QP) {
+  if constexpr (MULTI) {
+    // the array's value clamped as in the per-LCU entry, or the picture's QP as it stands as in the one-QP entry
+    const int qp = (int)__builtin_amdgcn_readfirstlane((u32)(a.lcu_qp ? clip_lcu_qp((int)a.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]) : a.qp));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, a.slice_is_intra, a.signhide);
+  } else if constexpr (LCU_QP) {
     const lcu_qp_source &q = only(per_lcu...);
     int qp;
     if constexpr (TILES) qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(q.lcu_qp ? (int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x] : tiles_of(per_lcu...).qp)));
@@ -546,8 +584,9 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
     // kvz_get_scan_order (encoderstate.c:1384-1398): luma TUs 8 and 4 wide, chroma TUs 4 wide
     p.scan = (leaf <= 8) ? ((p.mode >= 6 && p.mode <= 14) ? 2 : ((p.mode >= 22 && p.mode <= 30) ? 1 : 0)) : 0;
     p.tx = (p.lx - X0) >> sh; p.ty = (p.ly - Y0) >> sh;
-    const quant_consts *kk = a.k[plane ? 1 : 0];
+    const quant_consts *kk;
     if constexpr (LCU_QP) kk = own.k;
+    else kk = a.k[plane ? 1 : 0];
     if (n == 32) intra_tu<32, TILES, SL>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 16) intra_tu<16, TILES, SL>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 8) intra_tu<8, TILES, SL>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
@@ -566,6 +605,25 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(intra_args a, int 
   }
 }
 
+// what every entry requires of one picture's arguments, the QP aside; lists: the entry takes scaling lists
+inline bool intra_frame_args_ok(const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
+                                const kvz_hip_pixel *rec_v, uint32_t stride_c, const kvz_hip_cu_info *cus, const uint8_t *intra_modes,
+                                const kvz_hip_coeff *coeff_y, const kvz_hip_coeff *coeff_u, const kvz_hip_coeff *coeff_v,
+                                const kvz_hip_inter_residual_cost *costs, const kvz_hip_inter_residual_params *params, bool lists)
+{
+  if (!src || !params || !rec_y || !cus || !intra_modes || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) ||
+      ((uintptr_t)costs & 3))
+    return false;
+  const int width = src->width, height = src->height;
+  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
+      (params->scaling_list != 0) != lists)
+    return false;
+  if (params->chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
+                         src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
+    return false;
+  return true;
+}
+
 // the four entries; per_lcu: nothing (one QP per call, params->qp), one lcu_qp_source, that and a tile_source, or those and an
 // sl_source (the only one that takes, and requires, params->scaling_list != 0)
 template <typename... PER_LCU>
@@ -574,16 +632,10 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
                 kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                 const kvz_hip_inter_residual_params *params, kvz_hip_stream s, PER_LCU... per_lcu)
 {
-  if (!src || !params || !rec_y || !cus || !intra_modes || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) ||
-      ((uintptr_t)costs & 3))
+  if (!intra_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, costs, params,
+                           pack_has<sl_source, PER_LCU...>))
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      (params->scaling_list != 0) != pack_has<sl_source, PER_LCU...>)
-    return kvzhip::invalid_arg(entry);
-  if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
-                 src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
-    return kvzhip::invalid_arg(entry);
   const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
   intra_args a;
   // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants.  The shift of
@@ -615,7 +667,7 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
     groups = lcus_y * g.cols;
   }
   for (int t = 0; t < waves; ++t) {
-    hipLaunchKernelGGL(intra_recon_wave_kernel<PER_LCU...>, dim3((unsigned)groups, chroma ? 3u : 1u), dim3(WG), 0, st, a, t, per_lcu...);
+    hipLaunchKernelGGL((intra_recon_wave_kernel<intra_args, PER_LCU...>), dim3((unsigned)groups, chroma ? 3u : 1u), dim3(WG), 0, st, a, t, per_lcu...);
     KVZ_CHECK_LAUNCH("intra_recon_wave_kernel");
   }
   return KVZ_HIP_OK;
