@@ -1469,10 +1469,67 @@ typedef struct {
  *   plus one init launch if any picture has cbf_out or costs; launch t holds wave t of every picture.  kvz_hip_inter_residual_frames
  *   makes the single entry's launches (one per transform size, plus the init launch), each covering all pictures.
  * LEFT OUT ON PURPOSE: pictures with tiles, scaling lists or transform skip and pictures coded with --lossless stay with their
- *   single-picture entries (_tiles, _sl, _ts, _lossless); prediction (kvz_hip_inter_recon_frame), the QP map, deblocking and SAO of
+ *   single-picture entries (_tiles, _sl, _ts, _lossless) -- for tiles, scaling lists and transform skip see kvz_hip_*_frames_ts
+ *   below, which take them; prediction (kvz_hip_inter_recon_frame), the QP map, deblocking and SAO of
  *   several pictures are follow-ups.  The ABI version stays 4. */
 KVZ_HIP_API int kvz_hip_inter_residual_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Several independent pictures with tiles, scaling lists and          */
+/*   transform skip through the residual stages at once                */
+/*   reference: the pictures in flight (--owf) of an encode run with   */
+/*   --tiles, --scaling-list / --cqmfile or --transform-skip           */
+/* ------------------------------------------------------------------ */
+/* The tile boundaries of the records of one call travel in the kernel arguments, packed into one shared pool of this many 16-bit
+ * values: the sum of cols + rows + 2 over the records that carry a grid must not exceed it.  Sixteen pictures of 7 x 7 tiles use all
+ * of it, fourteen pictures of 8 x 8 tiles 252; records and pool together stay below the 4 KB that a kernel's arguments may take. */
+#define KVZ_HIP_CHAIN_TILE_BOUNDS 256
+/* One picture of kvz_hip_*_frames_ts: the arguments of kvz_hip_inter_residual_frame_ts / kvz_hip_intra_recon_frame_ts as a record.
+ * The record is HOST memory, copied at the call, and so is what grid and ts point to.  Offsets in front of the fields. */
+typedef struct {
+  kvz_hip_chain_picture pic;        /*   0: as for kvz_hip_*_frames; pic.params.scaling_list != 0 exactly when tables are given */
+  const kvz_hip_tile_grid *grid;    /* 160: HOST, optional, copied at the call; NULL = one tile.  Read by the intra entry only */
+  kvz_hip_scaling_tables tables;    /* 168: both NULL = flat lists; else both DEVICE, non-NULL, 16-byte aligned */
+  const kvz_hip_trskip *ts;         /* 184: HOST, optional, copied at the call; NULL = no transform skip */
+  uint8_t *tr_skip_out;             /* 192: DEVICE, one byte per SCU; required with ts, not touched without */
+} kvz_hip_chain_picture_ts;         /* 200 bytes */
+/* kvz_hip_inter_residual_frame_ts and kvz_hip_intra_recon_frame_ts for n_pictures (0..KVZ_HIP_MAX_CHAIN_PICTURES) pictures that do
+ * not depend on each other, in one asynchronous call: the wavefronts of all tiles of all pictures share the launches of the intra stage.
+ * THE RULE: for every picture i and every output array (the rec planes, the coefficients, cus[].cbf_y, cbf_out, costs, tr_skip_out),
+ *   the result is byte for byte what kvz_hip_inter_residual_frame_ts / kvz_hip_intra_recon_frame_ts leaves when called with the fields
+ *   of pictures[i].  Everything those entries define holds per picture: the tile rule for an intra TU's neighbours, the tables a TU
+ *   takes, the two trials of a 4x4 luma TU and their price, the clamping of lcu_qp, which bytes of tr_skip_out are written.  Pictures
+ *   of one call may differ in size, chroma format, QP, signhide and slice_is_intra; in their tile grid, tiled pictures beside untiled
+ *   ones included; in whether they carry lcu_qp, lcu_bit_cost, cbf_out and costs; and in which tables they point to.
+ * ONE RESTRICTION: a call is homogeneous in the two options that select a kernel instantiation.  Either every record carries tables
+ *   or none does; either every record carries ts or none does (both are encoder-wide settings: --scaling-list, --transform-skip).  A
+ *   record that differs from record 0 in either is refused.  Tiles are no such option: a record with grid == NULL stands beside
+ *   tiled ones.
+ * No options at all: when no record carries tables or ts -- and, for the intra entry, no record carries a grid -- the call IS
+ *   kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames on the embedded records, byte for byte (it calls it, and that entry
+ *   names itself in kvz_hip_last_error).
+ * Independence is the caller's promise, as for kvz_hip_*_frames.  Records whose rec_y, cus, coeff_y or (with ts) tr_skip_out base
+ *   pointers coincide are refused; tables, lcu_qp and lcu_bit_cost are inputs and may be shared.
+ * Errors: those of kvz_hip_*_frames (n_pictures == 0 is a no-op), and per record what the _ts single entry refuses: an invalid grid
+ *   (intra entry); ts without tr_skip_out; a negative bit_cost without lcu_bit_cost; a lcu_bit_cost that is not 4-byte aligned; one
+ *   table NULL or not 16-byte aligned; pic.params.scaling_list != 0 without tables or 0 with them; a negative params.qp without lcu_qp.
+ *   Also: the homogeneity rule; shared outputs; and (intra entry) a record whose grid no longer fits the pool of
+ *   KVZ_HIP_CHAIN_TILE_BOUNDS boundaries.  Every record is checked before anything is launched: a refusal returns
+ *   KVZ_HIP_ERR_INVALID, writes nothing for any picture, and kvz_hip_last_error() names the record's index ("picture 2") -- for the
+ *   pool, the record at which it overflowed.
+ * Execution: asynchronous on s; no host synchronisation, no allocation, no workspace -- the call owns no device buffer.  The records
+ *   (200 / 176 bytes per picture) and the pool travel in the kernel arguments and are read with scalar loads.  Usable between
+ *   kvz_hip_graph_begin / _end.  The launch shapes depend only on the sizes, the chroma flags, the grids and the presence of cbf_out /
+ *   costs: a captured call may be replayed after the CONTENTS of every device array changed.
+ * Launches: kvz_hip_intra_recon_frames_ts makes max over the pictures of (max over the picture's tiles of w_t + 2 (h_t - 1)) wavefront
+ *   launches, w_t x h_t the tile in LCUs, plus one init launch if any picture has cbf_out or costs.  kvz_hip_inter_residual_frames_ts
+ *   makes the single entry's launches (one per transform size, plus the init launch), each covering all pictures.
+ * LEFT OUT ON PURPOSE: a call that mixes pictures with and without tables, or with and without ts (a kernel that takes both paths at
+ *   run time would carry the code of both); pictures coded with --lossless (one launch each already); prediction, the QP map,
+ *   deblocking and SAO of several pictures; RDOQ.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_residual_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */

@@ -98,6 +98,15 @@ class ChainPicture(C.Structure):
                 ("costs", C.c_void_p), ("lcu_qp", C.c_void_p), ("params", InterResidualParams)]
 
 
+CHAIN_TILE_BOUNDS = 256      # KVZ_HIP_CHAIN_TILE_BOUNDS
+
+
+class ChainPictureTs(C.Structure):
+    """kvz_hip_chain_picture_ts"""
+    _fields_ = [("pic", ChainPicture), ("grid", C.POINTER(TileGrid)), ("tables", ScalingTables), ("ts", C.POINTER(TrSkip)),
+                ("tr_skip_out", C.c_void_p)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -208,6 +217,8 @@ SIGNATURES = {
     "kvz_hip_intra_recon_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_inter_residual_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
     "kvz_hip_intra_recon_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
+    "kvz_hip_inter_residual_frames_ts": (_I, [C.POINTER(ChainPictureTs), _I, _P]),
+    "kvz_hip_intra_recon_frames_ts": (_I, [C.POINTER(ChainPictureTs), _I, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

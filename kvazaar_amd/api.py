@@ -912,6 +912,69 @@ def _chain_frames(intra, pictures):
     return [st.result() for st in staged]
 
 
+# ---- several independent pictures with tiles, scaling lists and transform skip ----
+CHAIN_TILE_BOUNDS = _lib.CHAIN_TILE_BOUNDS                         # KVZ_HIP_CHAIN_TILE_BOUNDS
+
+
+def inter_residual_frames_ts(pictures):
+    """kvz_hip_inter_residual_frames_ts.  pictures: as for inter_residual_frames, each dict with the optional keys
+    tables=(quant, dequant), the packed arrays of scaling_tables_pack, and trskip=dict(bit_cost=..., lcu_bit_cost=...), either of the two
+    (tr_skip_out=...: what the array of choices holds before the call, zeros by default).  Either every picture carries tables or none
+    does, and the same for trskip.  grid is accepted and ignored: the stage does not depend on tiles.  Returns inter_residual_frames'
+    list of dicts, with "tr_skip_out" where trskip was given."""
+    return _chain_frames_ts(False, pictures)
+
+
+def intra_recon_frames_ts(pictures):
+    """kvz_hip_intra_recon_frames_ts.  pictures: as for intra_recon_frames, each dict with the optional keys grid=(col_bd, row_bd), the
+    tile boundaries in LCUs as tile_grid takes them, and tables / trskip / tr_skip_out as for inter_residual_frames_ts.  Tiled pictures
+    may stand beside untiled ones."""
+    return _chain_frames_ts(True, pictures)
+
+
+class _ChainPictureTs(_ChainPicture):
+    """_ChainPicture with the grid, the tables and the transform-skip arguments of one picture, and the 200-byte record"""
+
+    def __init__(self, intra, grid=None, tables=None, trskip=None, tr_skip_out=None, **plain):
+        super().__init__(intra, **plain)
+        height, width = plain["src"][0].shape
+        rec = _lib.ChainPictureTs()
+        rec.pic = self.record
+        self.dts = None
+        if grid is not None and intra:
+            self.grid = _lib.TileGrid.from_buffer_copy(tile_grid(width, height, grid[0], grid[1]).tobytes())
+            rec.grid = C.pointer(self.grid)
+        if tables is not None:
+            self.dt = [DeviceBuffer.from_numpy(np.ascontiguousarray(t, dtype=np.int32).reshape(SL_TABLE_LEN)) for t in tables]
+            rec.tables = _lib.ScalingTables(self.dt[0].ptr, self.dt[1].ptr)
+            rec.pic.params.scaling_list = 1
+        if trskip is not None:
+            self.ts = _lib.TrSkip(int(trskip.get("bit_cost", 0)), 0, None)
+            if trskip.get("lcu_bit_cost") is not None:
+                self.dbc = DeviceBuffer.from_numpy(np.ascontiguousarray(trskip["lcu_bit_cost"], dtype=np.int32).reshape(lcu_count(width, height)))
+                self.ts.lcu_bit_cost = self.dbc.ptr
+            tsk = (np.zeros(self.cus.shape, np.uint8) if tr_skip_out is None
+                   else np.ascontiguousarray(tr_skip_out, dtype=np.uint8).reshape(self.cus.shape))
+            self.dts = DeviceBuffer.from_numpy(tsk)
+            rec.ts, rec.tr_skip_out = C.pointer(self.ts), self.dts.ptr
+        self.record_ts = rec
+
+    def result(self):
+        out = super().result()
+        if self.dts is not None:
+            out["tr_skip_out"] = self.dts.to_numpy(np.uint8, self.cus.shape)
+        return out
+
+
+def _chain_frames_ts(intra, pictures):
+    L = _lib.init()
+    staged = [_ChainPictureTs(intra, **p) for p in pictures]
+    records = (_lib.ChainPictureTs * max(len(staged), 1))(*[st.record_ts for st in staged])
+    entry = L.kvz_hip_intra_recon_frames_ts if intra else L.kvz_hip_inter_residual_frames_ts
+    check(entry(records, len(staged), None), "intra_recon frames_ts" if intra else "inter_residual frames_ts")
+    return [st.result() for st in staged]
+
+
 # ---- lossless coding: the two residual stages of a picture coded with --lossless ----
 def inter_residual_frame_lossless(src, pred, cus, chroma=1, implicit_rdpcm=0, coeff=None, cbf_out=None, costs=None):
     """kvz_hip_inter_residual_frame_lossless.  Arguments and the returned dict as inter_residual_frame, without a QP: coeff = source -

@@ -1,5 +1,6 @@
 // inter_residual_core.h -- the kernels and the host side of the whole-picture inter residual entries (inter_residual.hip: one QP per
-// call and a QP per LCU; inter_residual_sl.hip: scaling lists; inter_residual_ts.hip: transform skip; inter_residual_multi.hip: several pictures in one call).  Everything here has internal linkage: each translation unit gets
+// call and a QP per LCU; inter_residual_sl.hip: scaling lists; inter_residual_ts.hip: transform skip; inter_residual_multi.hip: several pictures in one call;
+// inter_residual_multi_ts.hip: several pictures with scaling lists and transform skip).  Everything here has internal linkage: each translation unit gets
 // its own copy and instantiates its own kernels.  The algorithm is described in inter_residual.hip.
 #pragma once
 
@@ -51,6 +52,22 @@ static_assert(sizeof(resid_pic) == 136 && sizeof(resid_batch) <= 3072, "the reco
 // argument is not (tools/compare_kernels.py); for resid_pic they are scalar loads at an offset that blockIdx.y gives.
 __device__ __forceinline__ resid_args picture_of(const resid_args &a) { return a; }
 __device__ __forceinline__ resid_pic picture_of(const resid_batch &b) { return b.p[blockIdx.y]; }
+// One picture of kvz_hip_inter_residual_frames_ts: resid_pic, then what the _sl and _ts entries take as trailing arguments.  176 bytes.
+// The options that select an instantiation are the type of the table: a call is homogeneous in them.
+struct resid_pic_ts : resid_pic {
+  const int32_t *quant, *dequant;          // SL: the packed tables
+  const int32_t *lcu_bit_cost;             // TS: or nullptr, bit_cost in every LCU
+  u8 *tr_skip_out;                         // TS
+  int bit_cost, pad2;
+};
+struct resid_batch_ts_data { resid_pic_ts p[KVZ_HIP_MAX_CHAIN_PICTURES]; };
+template <bool SL, bool TS> struct resid_batch_ts : resid_batch_ts_data {};
+static_assert(sizeof(resid_pic_ts) == 176 && sizeof(resid_batch_ts<true, true>) <= 3072, "the records travel in the kernel arguments");
+template <bool SL, bool TS> __device__ __forceinline__ resid_pic_ts picture_of(const resid_batch_ts<SL, TS> &b) { return b.p[blockIdx.y]; }
+// what the type of the kernel's first argument says about the instantiation
+template <typename ARGS> struct batch_of { static constexpr bool multi = false, sl = false, ts = false; };
+template <> struct batch_of<resid_batch> { static constexpr bool multi = true, sl = false, ts = false; };
+template <bool SL, bool TS> struct batch_of<resid_batch_ts<SL, TS>> { static constexpr bool multi = true, sl = SL, ts = TS; };
 
 // the inter CU that holds the luma position (x, y), from the record of that position alone: false for another type, a
 // depth beyond 3 or a CU that would leave the picture (the rule of kvz_hip_inter_recon_frame)
@@ -106,6 +123,9 @@ __device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, con
 __device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t, const ts_source &) { return t; }
 __device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const ts_source &t) { return t; }
 __device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const sl_source &, const ts_source &t) { return t; }
+// the trailing argument, or where the kernel takes none (several pictures) what it made of its picture's record
+__device__ __forceinline__ const ts_source &skip_or(const ts_source &m) { return m; }
+template <typename... P> __device__ __forceinline__ const ts_source &skip_or(const ts_source &, const lcu_qp_source &q, const P &...p) { return skip_of(q, p...); }
 template <typename T, typename U> struct same_type { static constexpr bool value = false; };
 template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
 template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
@@ -119,7 +139,8 @@ template <int N, typename ARGS, typename... PER_LCU>
 __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant_consts ky, quant_consts kc,
                                                                 int nx_y, int n_y, int nx_c, int n_c, PER_LCU... per_lcu)
 {
-  constexpr bool MULTI = same_type<ARGS, resid_batch>::value, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, SL = pack_has<sl_source, PER_LCU...>, TS = pack_has<ts_source, PER_LCU...>;
+  constexpr bool MULTI = batch_of<ARGS>::multi, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl,
+                 TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts;
   static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
   constexpr int TPB = 256 / N, W4 = N / 4;
   constexpr int LD = lds_tile_ld(N);
@@ -163,7 +184,9 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
     // TU runs the barriers with the constants of QP 0 and reads nothing
     constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
     const int qp = valid ? (a.lcu_qp ? clip_lcu_qp(a.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)]) : a.qp) : 0;
-    k = flat_consts(qp, LOG2, plane, a.slice_is_intra, a.signhide);
+    if constexpr (SL) k = sl_consts(qp, LOG2, plane, 0, a.slice_is_intra, a.signhide, a.quant, a.dequant);   // no TU: the tables of QP 0, inside the arrays
+    else k = flat_consts(qp, LOG2, plane, a.slice_is_intra, a.signhide);
+    if constexpr (TS) tu_qp = qp;
   } else if constexpr (LCU_QP) {
     constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
     // ky and kc are not used.  A slot that is no TU runs the barriers with the constants of QP 0 and reads nothing
@@ -300,7 +323,9 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
     // shift, so nothing crosses rows but the sign-hiding pass and the sums.  A thread reads and writes its own row of ta / tq since
     // the last barrier; the first trial's row of levels waits in registers.  Chroma slots run it too (the barriers are the
     // workgroup's) and never take it.
-    const ts_source &ts = skip_of(per_lcu...);
+    [[maybe_unused]] ts_source of_picture = {};                              // several pictures: from the picture's record
+    if constexpr (MULTI) of_picture = { a.lcu_bit_cost, a.tr_skip_out, a.bit_cost, 0 };
+    const ts_source &ts = skip_or(of_picture, per_lcu...);
     const uint2 q1 = make_uint2(*(const u32 *)(tq + row * LD), *(const u32 *)(tq + row * LD + 2));
     int any2 = 0;
 #pragma unroll

@@ -1,6 +1,7 @@
 // intra_recon_core.h -- the kernels and the host side of the whole-picture intra entries (intra_recon.hip: one QP per call,
 // intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture, intra_recon_sl.hip: scaling lists, intra_recon_ts.hip:
-// transform skip, intra_recon_multi.hip: several pictures in one call).  Everything here has
+// transform skip, intra_recon_multi.hip: several pictures in one call, intra_recon_multi_ts.hip: several pictures with tiles, scaling
+// lists and transform skip).  Everything here has
 // internal linkage: each of the translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is
 // described in intra_recon.hip.
 #pragma once
@@ -55,6 +56,33 @@ struct intra_batch { intra_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; };
 static_assert(sizeof(intra_pic) == 152 && sizeof(intra_batch) <= 3072, "the records travel in the kernel arguments");
 template <typename ARGS> struct picture_type { using type = ARGS; };
 template <> struct picture_type<intra_batch> { using type = intra_pic; };
+
+// One picture of kvz_hip_intra_recon_frames_ts: intra_pic, then what the _sl and _ts entries take as trailing arguments, and the
+// picture's tile grid as counts and offsets into the pool of boundaries that the records of a call share.  cols == 0: no grid, one
+// tile.  200 bytes.  Sixteen kvz_hip_tile_grid (392 bytes each) do not fit the kernel arguments beside sixteen records, the
+// boundaries that a call uses do: LCU indices are at most 256, two of them to a dword, and the dword is read with a scalar load.
+struct intra_pic_ts : intra_pic {
+  const int32_t *quant, *dequant;          // SL: the packed tables
+  const int32_t *lcu_bit_cost;             // TS: or nullptr, bit_cost in every LCU
+  u8 *tr_skip_out;                         // TS
+  int bit_cost;
+  uint16_t col_at, row_at;                 // where col_bd[0] and row_bd[0] stand in the pool
+  u8 cols, rows, pad2[2];
+};
+struct intra_batch_ts_data {
+  intra_pic_ts p[KVZ_HIP_MAX_CHAIN_PICTURES];
+  u32 bd[KVZ_HIP_CHAIN_TILE_BOUNDS / 2];
+  __device__ __forceinline__ int bound(int i) const { return (int)((bd[i >> 1] >> (16 * (i & 1))) & 0xffffu); }
+};
+// the options that select an instantiation are the type of the table: a call is homogeneous in them
+template <bool SL, bool TS> struct intra_batch_ts : intra_batch_ts_data {};
+static_assert(sizeof(intra_pic_ts) == 200 && sizeof(intra_batch_ts_data) == 3200 + 2 * KVZ_HIP_CHAIN_TILE_BOUNDS && sizeof(intra_batch_ts<true, true>) + 8 <= 4096,
+              "the records and the pool travel in the kernel arguments: 4 KB with the wave index");
+template <bool SL, bool TS> struct picture_type<intra_batch_ts<SL, TS>> { using type = intra_pic_ts; };
+// what the type of the kernel's first argument says about the instantiation
+template <typename ARGS> struct batch_of { static constexpr bool multi = false, tiles = false, sl = false, ts = false; };
+template <> struct batch_of<intra_batch> { static constexpr bool multi = true, tiles = false, sl = false, ts = false; };
+template <bool SL, bool TS> struct batch_of<intra_batch_ts<SL, TS>> { static constexpr bool multi = true, tiles = true, sl = SL, ts = TS; };
 
 // The LCU's tile in LDS: pixel (x, y) of the plane relative to the LCU's top-left, x = -1 .. T + T/2 - 1, y = -1 .. T - 1
 // (T = 64 luma, 32 chroma).  Column 0 stands at a dword boundary.
@@ -462,8 +490,8 @@ static_assert(WG == 64, "one wave per workgroup: see intra_tu");
 template <typename ARGS, typename... PER_LCU>
 __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, PER_LCU... per_lcu)
 {
-  constexpr bool MULTI = same_type<ARGS, intra_batch>::value, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2, SL = pack_has<sl_source, PER_LCU...>,
-                 TS = pack_has<ts_source, PER_LCU...>;
+  constexpr bool MULTI = batch_of<ARGS>::multi, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2 || batch_of<ARGS>::tiles,
+                 SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl, TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts;
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -479,12 +507,35 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
   const PIC &a = ((const PIC *)&args)[MULTI ? blockIdx.z : 0];
   const int lane = threadIdx.x, plane = blockIdx.y, sh = plane ? 1 : 0;
   int lcu_y = blockIdx.x, lcu_x = t - 2 * lcu_y;
-  if constexpr (MULTI) {
+  if constexpr (MULTI && !TILES) {
     // the grid is that of the tallest picture with chroma (a wave of a picture that has run out fails the test of lcu_x below)
     if ((plane && !a.chroma) || 64 * lcu_y >= a.height) return;
   }
   tile_rect tr;                                                              // read with tiles only
-  if constexpr (TILES) {
+  if constexpr (MULTI && TILES) {
+    // the grid's x extent is that of the picture with the most LCU rows x tile columns.  Wave-uniform: the picture's counts and
+    // offsets from its record, its boundaries from the pool, all scalar loads from the kernel arguments
+    if (plane && !a.chroma) return;
+    const int lcus_y = (a.height + 63) >> 6;
+    int cx0 = 0, cx1 = a.lcus_x, ry0 = 0, ry1 = lcus_y;
+    if (a.cols) {
+      const int cols = a.cols, col = (int)blockIdx.x % cols;
+      lcu_y = (int)blockIdx.x / cols;
+      if (lcu_y >= lcus_y) return;
+      cx0 = args.bound(a.col_at + col);
+      cx1 = args.bound(a.col_at + col + 1);
+      // row_bd[rows] is the picture's count of LCU rows, above lcu_y: the walk ends at the tile row that holds lcu_y
+      for (int j = 1; j <= a.rows; ++j) {
+        const int b = args.bound(a.row_at + j);
+        if (b > lcu_y) { ry1 = b; break; }
+        ry0 = b;
+      }
+    }
+    if (lcu_y >= lcus_y) return;
+    lcu_x = cx0 + t - 2 * (lcu_y - ry0);
+    if (lcu_x < cx0 || lcu_x >= cx1) return;
+    tr = { 64 * cx0, 64 * ry0, min(64 * cx1, (int)a.width), min(64 * ry1, (int)a.height) };
+  } else if constexpr (TILES) {
     // wave-uniform: scalar loads of the grid, scalar compares and selects
     const kvz_hip_tile_grid &g = tiles_of(per_lcu...).grid;
     const int cols = g.cols, col = (int)blockIdx.x % cols;
@@ -541,7 +592,14 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
     // the array's value clamped as in the per-LCU entry, or the picture's QP as it stands as in the one-QP entry
     const int qp = (int)__builtin_amdgcn_readfirstlane((u32)(a.lcu_qp ? clip_lcu_qp((int)a.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]) : a.qp));
 #pragma unroll
-    for (int i = 0; i < 4; ++i) own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, a.slice_is_intra, a.signhide);
+    for (int i = 0; i < 4; ++i) {
+      if constexpr (SL) own.k[i] = sl_consts(qp, 2 + i, plane, 1, a.slice_is_intra, a.signhide, a.quant, a.dequant);
+      else own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, a.slice_is_intra, a.signhide);
+    }
+    if constexpr (TS) {
+      const int v = (int)__builtin_amdgcn_readfirstlane((u32)(a.lcu_bit_cost ? a.lcu_bit_cost[(size_t)lcu_y * a.lcus_x + lcu_x] : a.bit_cost));
+      skip = { qp, (u32)max(v, 0), a.tr_skip_out };
+    }
   } else if constexpr (LCU_QP) {
     const lcu_qp_source &q = only(per_lcu...);
     int qp;

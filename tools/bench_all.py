@@ -247,6 +247,142 @@ def main():
         deblock_tiles_rows(L, st, max(args.rounds, 5), (dby, dbu, dbv, dbc, dbp, DW, DH))
     if not args.only or any(o in "intra_recon_frames_1080p_all_x4 intra_recon_frames_1080p_mixed_x4 inter_residual_frames_1080p_x4" for o in args.only.split(",")):
         chain_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "intra_recon_frames_ts_1080p_all_tiles4x2_x4 intra_recon_frames_ts_1080p_mixed_tiles4x2_x4 intra_recon_frames_ts_1080p_all_trskip_x4 "
+                            "inter_residual_frames_ts_1080p_x4" for o in args.only.split(",")):
+        chain_multi_ts_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+
+
+def chain_multi_ts_rows(L, st, dev, rounds, only, pictures=4):
+    """The pictures of chain_multi_rows through ONE call of kvz_hip_intra_recon_frames_ts / kvz_hip_inter_residual_frames_ts and, in the same
+    rounds, interleaved, through four back-to-back calls of the single-picture entry that takes the same options: *_tiles4x2_x4 with 4 x 2
+    uniform tiles in every picture against kvz_hip_intra_recon_frame_tiles, *_trskip_x4 untiled with one bit cost against
+    kvz_hip_intra_recon_frame_ts, the inter row with one bit cost against kvz_hip_inter_residual_frame_ts.  One QP per picture, flat lists.
+    ms per batch of four pictures: median and min..max over the rounds, and the ratio of the medians; `launches` counts dependent launches."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inter_residual_cases as RC
+    import intra_recon_cases as XC
+    from kvazaar_amd import api
+    W, H = 1920, 1080
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+    shapes = api.coeff_shapes(W, H)
+    grid = api.uniform_tile_grid(W, H, 4, 2)
+    grid_p = C.cast(grid.ctypes.data, C.POINTER(_lib.TileGrid))
+    waves = {False: (W + 63) // 64 + 2 * ((H + 63) // 64 - 1),
+             True: int(max(np.diff(grid["col_bd"][0, :5])) + 2 * (max(np.diff(grid["row_bd"][0, :3])) - 1))}
+    ts = _lib.TrSkip(58, 0, None)                       # (int)(lambda + 0.5) at QP 32
+    print("%-46s %9s %10s %18s %10s %18s %7s" % ("kernel", "launches", "ms", "min..max ms", "4 calls ms", "min..max ms", "ratio"))
+
+    def outputs(cus):
+        return ([torch.empty(shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)],
+                torch.zeros(cus.shape, dtype=torch.uint8, device=dev), torch.empty(cus.shape + (6,), dtype=torch.int32, device=dev),
+                torch.zeros(cus.shape, dtype=torch.uint8, device=dev))
+
+    def record(src_d, rec_d, cus_d, modes_d, co_d, cbf_d, cost_d, skip_d, prm, tiled, skip):
+        r = _lib.ChainPictureTs()
+        r.pic.src = _lib.RefPicture(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2, W, H)
+        r.pic.rec_y, r.pic.rec_u, r.pic.rec_v, r.pic.stride_y, r.pic.stride_c = rec_d[0].data_ptr(), rec_d[1].data_ptr(), rec_d[2].data_ptr(), W, W // 2
+        r.pic.cus, r.pic.intra_modes = cus_d.data_ptr(), modes_d.data_ptr() if modes_d is not None else None
+        r.pic.coeff_y, r.pic.coeff_u, r.pic.coeff_v = co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr()
+        r.pic.cbf_out, r.pic.costs = cbf_d.data_ptr(), cost_d.data_ptr()
+        r.pic.params = _lib.InterResidualParams(int(prm["qp"][0]), int(prm["slice_is_intra"][0]), int(prm["signhide"][0]), 0, 1, 0)
+        if tiled:
+            r.grid = grid_p
+        if skip:
+            r.ts, r.tr_skip_out = C.pointer(ts), skip_d.data_ptr()
+        return r
+
+    def report(name, launches, multi, single):
+        ms, ms4 = float(np.median(multi)), float(np.median(single))
+        print("%-46s %9s %10.3f %18s %10.3f %18s %7.2f" % (name, "%d/%d" % (launches, pictures * launches), ms, "%.3f..%.3f" % (min(multi), max(multi)), ms4,
+                                                           "%.3f..%.3f" % (min(single), max(single)), ms4 / ms))
+
+    for name, share, tiled, skip in (("intra_recon_frames_ts_1080p_mixed_tiles4x2_x4", 0.1, True, False),
+                                     ("intra_recon_frames_ts_1080p_all_tiles4x2_x4", 1.0, True, False),
+                                     ("intra_recon_frames_ts_1080p_all_trskip_x4", 1.0, False, True)):
+        if not any(o in name for o in only):
+            continue
+        prm = api.inter_residual_params(32, 0, 1, 1)
+        keep, calls = [], []
+        for i in range(pictures):
+            cus, _, modes = XC.make_map(W, H, 151 + 10 * i, intra_share=share, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+            src, rec = XC.make_planes(cus, 152 + 10 * i)
+            src_d, rec_d, cus_d, modes_d = [up(p) for p in src], [up(p) for p in rec], up(cus), up(modes)
+            co_d, cbf_d, cost_d, skip_d = outputs(cus)
+            table = api.ref_picture_table([(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2)], W, H)
+            keep.append((src_d, rec_d, cus_d, modes_d, co_d, cbf_d, cost_d, skip_d, table))
+            planes = (table.ctypes.data, rec_d[0].data_ptr(), W, rec_d[1].data_ptr(), rec_d[2].data_ptr(), W // 2, cus_d.data_ptr(), modes_d.data_ptr(),
+                      co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr(), None)
+            if skip:
+                calls.append(planes + (None, None, C.byref(ts), skip_d.data_ptr(), prm.ctypes.data, st))
+            else:
+                calls.append(planes + (grid.ctypes.data, prm.ctypes.data, st))
+        records = (_lib.ChainPictureTs * pictures)(*[record(*k[:8], prm, tiled, skip) for k in keep])
+        entry = L.kvz_hip_intra_recon_frame_ts if skip else L.kvz_hip_intra_recon_frame_tiles
+
+        def multi():                                     # in place and independent of what the intra CUs hold: no fresh copy needed
+            return L.kvz_hip_intra_recon_frames_ts(records, pictures, st)
+
+        def single():
+            for a in calls:
+                rc = entry(*a)
+                if rc:
+                    return rc
+            return 0
+        torch.cuda.synchronize()
+        t = {"multi": [], "single": []}
+        for _ in range(rounds):                          # interleaved round by round
+            t["multi"].append(timed(L, st, lambda: _lib.check(multi(), name), iters=3, warm=1))
+            t["single"].append(timed(L, st, lambda: _lib.check(single(), name + " (4 calls)"), iters=3, warm=1))
+        report(name, waves[tiled] + 1, t["multi"], t["single"])
+    name = "inter_residual_frames_ts_1080p_x4"
+    if any(o in name for o in only):
+        iters = 6
+        prm = api.inter_residual_params(32, 0, 0, 1)
+        keep = []
+        for i in range(pictures):
+            cus, _ = RC.make_map(W, H, 141 + 10 * i, intra_share=0.0, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+            pred = RC.smooth_planes(W, H, 142 + 10 * i)
+            src = RC.make_source(pred, cus, 143 + 10 * i)
+            src_d, master, cus_d = [up(p) for p in src], [up(p) for p in pred], up(cus)
+            recs = [[torch.empty_like(m) for m in master] for _ in range(iters)]
+            co_d, cbf_d, cost_d, skip_d = outputs(cus)
+            table = api.ref_picture_table([(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2)], W, H)
+            keep.append((src_d, master, recs, cus_d, co_d, cbf_d, cost_d, skip_d, table))
+        # one table of records and one argument list per picture for every set of fresh predictions
+        batches = [(_lib.ChainPictureTs * pictures)(*[record(k[0], k[2][j], k[3], None, k[4], k[5], k[6], k[7], prm, False, True) for k in keep])
+                   for j in range(iters)]
+        calls = [[(k[8].ctypes.data, k[2][j][0].data_ptr(), W, k[2][j][1].data_ptr(), k[2][j][2].data_ptr(), W // 2, k[3].data_ptr(), k[4][0].data_ptr(),
+                   k[4][1].data_ptr(), k[4][2].data_ptr(), k[5].data_ptr(), k[6].data_ptr(), None, None, C.byref(ts), k[7].data_ptr(), prm.ctypes.data, st)
+                  for k in keep] for j in range(iters)]
+        turn = [0]
+
+        def multi():
+            turn[0] += 1
+            return L.kvz_hip_inter_residual_frames_ts(batches[(turn[0] - 1) % iters], pictures, st)
+
+        def single():
+            turn[0] += 1
+            for a in calls[(turn[0] - 1) % iters]:
+                rc = L.kvz_hip_inter_residual_frame_ts(*a)
+                if rc:
+                    return rc
+            return 0
+
+        def refresh():
+            for k in keep:
+                for r in k[2]:
+                    for d, m in zip(r, k[1]):
+                        d.copy_(m)
+            torch.cuda.synchronize()
+            turn[0] = 0
+        t = {"multi": [], "single": []}
+        for _ in range(rounds):
+            refresh()
+            t["multi"].append(timed(L, st, lambda: _lib.check(multi(), name), iters=iters - 1, warm=1))
+            refresh()
+            t["single"].append(timed(L, st, lambda: _lib.check(single(), name + " (4 calls)"), iters=iters - 1, warm=1))
+        report(name, 5, t["multi"], t["single"])
 
 
 def chain_multi_rows(L, st, dev, rounds, only, pictures=4):

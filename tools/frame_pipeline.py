@@ -15,7 +15,7 @@ frame-sized workload, not of an encoder: the mode decision around them is not he
 
   python tools/frame_pipeline.py [--frames 200] [--lcu-qp] [--tiles CxR] [--scaling-list [default|none]] [--transform-skip]
   python tools/frame_pipeline.py --lossless [--tiles CxR]
-  python tools/frame_pipeline.py --pictures N
+  python tools/frame_pipeline.py --pictures N [--tiles CxR] [--scaling-list [default|none]] [--transform-skip]
 
 --lcu-qp: the picture chain of a frame whose QP changes per LCU (rate control, --roi): intra reconstruction through
 kvz_hip_intra_recon_frame_qp with a QP array, then kvz_hip_cu_qp_frame (the QP map and the per-LCU predictor), and deblocking
@@ -35,8 +35,10 @@ kvz_hip_intra_recon_frame_lossless (implicit_rdpcm on), one kernel launch each. 
 are left out: encoder.c:623-628 switches sign hiding, transform skip, deblocking and SAO off under --lossless.  Combines with --tiles
 (the grid goes to the intra entry); --lcu-qp, --scaling-list and --transform-skip have no meaning without quantisation and are refused.
 --pictures N (1..16): N independent pictures in flight.  Each is predicted by a kvz_hip_inter_recon_frame call of its own; then the two
-residual stages of all N go through ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames call (one QP per picture).  The
-multi-picture entries take none of the other variants, so --pictures combines with no other option of the picture chain.
+residual stages of all N go through ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames call (one QP per picture).
+Combines with --tiles, --scaling-list and --transform-skip: the two calls are then kvz_hip_inter_residual_frames_ts and
+kvz_hip_intra_recon_frames_ts, every picture with the same grid, the same tables and the same bit cost.  --lcu-qp (the QP map of
+several pictures is a follow-up) and --lossless (one launch per picture already) stay single-picture and are refused with --pictures.
 """
 import argparse
 import ctypes as C
@@ -156,7 +158,61 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
             ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), None, None, grid.ctypes.data if tiles else None, C.byref(ll), s)))
         del stages["sao"]                                            # no deblocking, no SAO (encoder.c:623-628)
         return stages, keep
-    if lists or trskip:
+    if pictures:
+        # N independent pictures in flight: each is predicted by a call of its own (prediction of several pictures is a follow-up),
+        # then ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames take all of them.  Picture 0 is the frame's own;
+        # the others have planes, coefficients and intra maps of their own (the inter map and the references are shared inputs).
+        # With --tiles, --scaling-list or --transform-skip the two calls are kvz_hip_inter_residual_frames_ts / kvz_hip_intra_recon_frames_ts:
+        # every picture carries the grid, the tables (one set, shared) and a bit cost with an array of choices of its own per stage
+        options = bool(tiles or lists == "default" or trskip)
+        Record = _lib.ChainPictureTs if options else _lib.ChainPicture
+        sl = None
+        if lists == "default":
+            z = np.load(os.path.join(ROOT, "tests", "golden", "scaling_list.npz"), allow_pickle=False)
+            sl_q, sl_d = up(z["default_quant"]), up(z["default_dequant"])
+            sl = _lib.ScalingTables(sl_q.data_ptr(), sl_d.data_ptr())
+            keep += [sl_q, sl_d, sl]
+        ts = _lib.TrSkip(18, 0, None) if trskip else None                # (int)(lambda + 0.5) at QP 27
+        grid_p = C.cast(grid.ctypes.data, C.POINTER(_lib.TileGrid)) if tiles else None
+        keep += [ts, grid_p]
+        rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
+        inter, intra = (Record * pictures)(), (Record * pictures)()
+        keep += [rc_src, inter, intra]
+        for i in range(pictures):
+            dst, co = rc_dst, [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+            x_src, x_rec, x_cus, x_modes, x_co = ir_src, ir_rec, ir_cus_d, ir_modes_d, ir_co
+            if i:
+                dst = [torch.empty_like(p) for p in rc_dst]
+                stages["tu"].append(("inter_recon_frame", 1, lambda s, dst=dst: L.kvz_hip_inter_recon_frame(
+                    dst[0].data_ptr(), W, dst[1].data_ptr(), dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data, rc_prm.ctypes.data, s)))
+                cus_h, _, modes_h = XC.make_map(W, H, 33 + 10 * i, intra_share=0.1, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+                src_h, rec_h = XC.make_planes(cus_h, 34 + 10 * i)
+                x_src, x_rec, x_cus, x_modes = [up(p) for p in src_h], [up(p) for p in rec_h], up(cus_h), up(modes_h)
+                x_co = [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+            cus_copy = rc_cus_d.clone()                                  # cbf_y is written back: a map per picture
+            keep += [dst, co, x_src, x_rec, x_cus, x_modes, x_co, cus_copy]
+            for full, src, rec, cus_d, modes_d, c in ((inter[i], rc_src, dst, cus_copy, None, co), (intra[i], x_src, x_rec, x_cus, x_modes, x_co)):
+                r = full.pic if options else full
+                r.src = _lib.RefPicture(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), W, W // 2, W, H)
+                r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), W, W // 2
+                r.cus, r.intra_modes = cus_d.data_ptr(), modes_d.data_ptr() if modes_d is not None else None
+                r.coeff_y, r.coeff_u, r.coeff_v = c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr()
+                r.params = _lib.InterResidualParams(27, 0, 0, 1 if sl is not None else 0, 1, 0)
+                if options:
+                    full.grid = grid_p
+                    if sl is not None:
+                        full.tables = sl
+                    if trskip:
+                        skip = torch.zeros(ir_cus.shape, dtype=torch.uint8, device=dev)
+                        keep.append(skip)
+                        full.ts, full.tr_skip_out = C.pointer(ts), skip.data_ptr()
+        if options:
+            stages["tu"].append(("inter_residual_frames_ts", pictures, lambda s: L.kvz_hip_inter_residual_frames_ts(inter, pictures, s)))
+            stages["tu"].append(("intra_recon_frames_ts", pictures, lambda s: L.kvz_hip_intra_recon_frames_ts(intra, pictures, s)))
+        else:
+            stages["tu"].append(("inter_residual_frames", pictures, lambda s: L.kvz_hip_inter_residual_frames(inter, pictures, s)))
+            stages["tu"].append(("intra_recon_frames", pictures, lambda s: L.kvz_hip_intra_recon_frames(intra, pictures, s)))
+    elif lists or trskip:
         # the packed tables on the device; `none`: no tables, and params->scaling_list stays 0
         sl = None
         if lists == "default":
@@ -221,34 +277,6 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
             ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr(), None, ir_qp.data_ptr(), ir_prm.ctypes.data, s)))
         stages["tu"].append(("cu_qp_frame", 1, lambda s: L.kvz_hip_cu_qp_frame(
             ir_cus_d.data_ptr(), ir_cbf.data_ptr(), W, H, ir_qp.data_ptr(), ir_last.data_ptr(), ir_qprm.ctypes.data, s)))
-    elif pictures:
-        # N independent pictures in flight: each is predicted by a call of its own (prediction of several pictures is a follow-up),
-        # then ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames take all of them.  Picture 0 is the frame's own;
-        # the others have planes, coefficients and intra maps of their own (the inter map and the references are shared inputs)
-        rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
-        inter, intra = (_lib.ChainPicture * pictures)(), (_lib.ChainPicture * pictures)()
-        keep += [rc_src, inter, intra]
-        for i in range(pictures):
-            dst, co = rc_dst, [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
-            x_src, x_rec, x_cus, x_modes, x_co = ir_src, ir_rec, ir_cus_d, ir_modes_d, ir_co
-            if i:
-                dst = [torch.empty_like(p) for p in rc_dst]
-                stages["tu"].append(("inter_recon_frame", 1, lambda s, dst=dst: L.kvz_hip_inter_recon_frame(
-                    dst[0].data_ptr(), W, dst[1].data_ptr(), dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data, rc_prm.ctypes.data, s)))
-                cus_h, _, modes_h = XC.make_map(W, H, 33 + 10 * i, intra_share=0.1, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
-                src_h, rec_h = XC.make_planes(cus_h, 34 + 10 * i)
-                x_src, x_rec, x_cus, x_modes = [up(p) for p in src_h], [up(p) for p in rec_h], up(cus_h), up(modes_h)
-                x_co = [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
-            cus_copy = rc_cus_d.clone()                                  # cbf_y is written back: a map per picture
-            keep += [dst, co, x_src, x_rec, x_cus, x_modes, x_co, cus_copy]
-            for r, src, rec, cus_d, modes_d, c in ((inter[i], rc_src, dst, cus_copy, None, co), (intra[i], x_src, x_rec, x_cus, x_modes, x_co)):
-                r.src = _lib.RefPicture(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), W, W // 2, W, H)
-                r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), W, W // 2
-                r.cus, r.intra_modes = cus_d.data_ptr(), modes_d.data_ptr() if modes_d is not None else None
-                r.coeff_y, r.coeff_u, r.coeff_v = c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr()
-                r.params = _lib.InterResidualParams(27, 0, 0, 0, 1, 0)
-        stages["tu"].append(("inter_residual_frames", pictures, lambda s: L.kvz_hip_inter_residual_frames(inter, pictures, s)))
-        stages["tu"].append(("intra_recon_frames", pictures, lambda s: L.kvz_hip_intra_recon_frames(intra, pictures, s)))
     else:
         stages["tu"].append(("intra_recon_frame", 1, lambda s: L.kvz_hip_intra_recon_frame(
             ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
@@ -382,11 +410,12 @@ def main():
                     help="a frame coded with --lossless: prediction, then the two *_lossless entries; no QP map, deblocking or SAO, which "
                          "encoder.c:623-628 switches off with sign hiding and transform skip")
     ap.add_argument("--pictures", type=int, default=0, metavar="N",
-                    help="N independent pictures (1..16): their two residual stages through kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames")
+                    help="N independent pictures (1..16): their two residual stages through kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames, or "
+                         "through the *_frames_ts entries with --tiles, --scaling-list or --transform-skip")
     args = ap.parse_args()
-    if args.pictures and (args.lossless or args.lcu_qp or args.scaling_list or args.transform_skip or args.tiles or not 1 <= args.pictures <= 16):
-        ap.error("--pictures N: 1..16, and without --lcu-qp, --tiles, --scaling-list, --transform-skip and --lossless, which stay with the "
-                 "single-picture entries")
+    if args.pictures and (args.lossless or args.lcu_qp or not 1 <= args.pictures <= 16):
+        ap.error("--pictures N: 1..16, and without --lcu-qp (the QP map of several pictures is not built) and --lossless (one launch per "
+                 "picture already), which stay with the single-picture entries; --tiles, --scaling-list and --transform-skip combine with it")
     if args.lossless and (args.lcu_qp or args.scaling_list or args.transform_skip):
         ap.error("--lossless: nothing is quantised, so --lcu-qp, --scaling-list and --transform-skip do not combine with it")
     tiles = tuple(int(v) for v in args.tiles.lower().split("x")) if args.tiles else None
