@@ -1470,8 +1470,10 @@ typedef struct {
  *   makes the single entry's launches (one per transform size, plus the init launch), each covering all pictures.
  * LEFT OUT ON PURPOSE: pictures with tiles, scaling lists or transform skip and pictures coded with --lossless stay with their
  *   single-picture entries (_tiles, _sl, _ts, _lossless) -- for tiles, scaling lists and transform skip see kvz_hip_*_frames_ts
- *   below, which take them; prediction (kvz_hip_inter_recon_frame), the QP map, deblocking and SAO of
- *   several pictures are follow-ups.  The ABI version stays 4. */
+ *   below, which take them.  Behind these two stages, the QP map, deblocking and SAO of several pictures are kvz_hip_cu_qp_frames,
+ *   kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames further below.  Prediction of several pictures
+ *   (kvz_hip_inter_recon_frame) is
+ *   not built: sixteen tables of reference pictures do not fit the kernel arguments (see there).  The ABI version stays 4. */
 KVZ_HIP_API int kvz_hip_inter_residual_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
 
@@ -1526,10 +1528,81 @@ typedef struct {
  *   launches, w_t x h_t the tile in LCUs, plus one init launch if any picture has cbf_out or costs.  kvz_hip_inter_residual_frames_ts
  *   makes the single entry's launches (one per transform size, plus the init launch), each covering all pictures.
  * LEFT OUT ON PURPOSE: a call that mixes pictures with and without tables, or with and without ts (a kernel that takes both paths at
- *   run time would carry the code of both); pictures coded with --lossless (one launch each already); prediction, the QP map,
- *   deblocking and SAO of several pictures; RDOQ.  The ABI version stays 4. */
+ *   run time would carry the code of both); pictures coded with --lossless (one launch each already); prediction of several
+ *   pictures (the QP map, deblocking and SAO of several pictures are kvz_hip_cu_qp_frames, kvz_hip_deblock_frames,
+ *   kvz_hip_sao_stats_frames and kvz_hip_sao_frames below); RDOQ.  The ABI version stays 4. */
 KVZ_HIP_API int kvz_hip_inter_residual_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Several independent pictures through the QP map, deblocking and     */
+/*   SAO at once: the stages behind kvz_hip_*_frames(_ts)              */
+/*   reference: set_cu_qps (encoderstate.c:550-609), filter.c:690-779  */
+/*   and sao.c:278-337, :580-644 of the pictures in flight (--owf)     */
+/* ------------------------------------------------------------------ */
+/* One picture of kvz_hip_cu_qp_frames, kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames: the arguments of
+ * kvz_hip_cu_qp_frame_tiles, kvz_hip_deblock_frame_tiles, kvz_hip_sao_stats_frame and kvz_hip_sao_frame_tiles as ONE record, so that
+ * a host fills it once and hands it to the four calls.  Each entry reads its own fields and ignores the rest ([Q] the QP map, [D]
+ * deblocking, [T] the statistics, [S] SAO; width, height and chroma are read by all four).  Every pointer is DEVICE memory except
+ * grid, which is HOST memory like the record itself, both copied at the call.  Offsets in front of the fields; no implicit padding. */
+typedef struct {
+  int32_t width, height;                /*   0, 4: the picture; the size and stride rules are the single-picture entries' */
+  int32_t chroma;                       /*   8: 0 = 4:0:0 (the u / v planes and sao_chroma are unused), 1 = 4:2:0 */
+  int32_t reserved;                     /*  12: not read */
+  kvz_hip_ref_picture src;              /*  16: [T] the source planes; src.width / src.height must equal width / height */
+  kvz_hip_pixel *rec_y, *rec_u, *rec_v; /*  56, 64, 72: [D] deblocked in place; [T] [S] read */
+  uint32_t stride_y, stride_c;          /*  80, 84: of rec_y and of rec_u / rec_v */
+  kvz_hip_pixel *dst_y, *dst_u, *dst_v; /*  88, 96, 104: [S] written */
+  uint32_t dst_stride_y, dst_stride_c;  /* 112, 116: of dst_y and of dst_u / dst_v */
+  kvz_hip_cu_info *cus;                 /* 120: [Q] cus[].qp written; [D] read */
+  const uint8_t *cbf;                   /* 128: [Q] one byte per SCU */
+  const int8_t *lcu_qp;                 /* 136: [Q] */
+  int8_t *lcu_last_qp;                  /* 144: [Q] written */
+  kvz_hip_sao_lcu_stats *stats;         /* 152: [T] written */
+  kvz_hip_sao_lcu_cand *cands;          /* 160: [T] written; optional */
+  const kvz_hip_sao_info *sao_luma;     /* 168: [S] */
+  const kvz_hip_sao_info *sao_chroma;   /* 176: [S] with chroma */
+  const kvz_hip_tile_grid *grid;        /* 184: [Q] [D] [S] HOST, optional, copied at the call; NULL = one tile */
+  kvz_hip_deblock_params deblock;       /* 192: [D]; deblock.chroma must equal chroma, in every entry */
+  kvz_hip_cu_qp_tiles_params cu_qp;     /* 256: [Q] start_qp, chain_rows */
+} kvz_hip_filter_picture;               /* 264 bytes */
+/* kvz_hip_cu_qp_frame_tiles, kvz_hip_deblock_frame_tiles, kvz_hip_sao_stats_frame and kvz_hip_sao_frame_tiles for n_pictures
+ * (0..KVZ_HIP_MAX_CHAIN_PICTURES) pictures that do not depend on each other, in one asynchronous call each.  The stages are a few
+ * short launches per picture and bound by them; independent pictures share the launches, the picture being one more grid dimension.
+ * THE RULE: for every picture i and every output array, the result is byte for byte what the single-picture entry leaves when called
+ *   with the fields of pictures[i]: kvz_hip_cu_qp_frame_tiles (cus[].qp, lcu_last_qp), kvz_hip_deblock_frame_tiles (the rec planes),
+ *   kvz_hip_sao_frame_tiles (the dst planes), and kvz_hip_sao_stats_frame (stats, cands), which has no tiled form.  grid == NULL is
+ *   one tile, byte for byte the untiled entry; with grid == NULL, cu_qp.chain_rows 0 and 1 mean what chain_lcus = 0 and chain_lcus =
+ *   ceil(width / 64) mean in kvz_hip_cu_qp_frame.  Pictures of one call may differ in size, chroma format (4:0:0 beside 4:2:0), tile
+ *   grid (tiled beside untiled), chain_rows, every field of deblock, and in whether they carry cands.  There is no homogeneity rule:
+ *   the kernels always take a grid, one tile for NULL, so no option selects an instantiation.
+ * Independence is the caller's promise, as for kvz_hip_*_frames: no output of one record may be an input or an output of another;
+ *   inputs may be shared.  Records whose output base pointers coincide are refused: rec_y (kvz_hip_deblock_frames), dst_y
+ *   (kvz_hip_sao_frames), cus or lcu_last_qp (kvz_hip_cu_qp_frames), stats (kvz_hip_sao_stats_frames).
+ * Errors: n_pictures == 0 is a no-op that returns KVZ_HIP_OK (pictures may then be NULL).  KVZ_HIP_ERR_INVALID: n_pictures below 0 or
+ *   above KVZ_HIP_MAX_CHAIN_PICTURES, pictures == NULL, any record that the single-picture entry would refuse (a missing pointer, a
+ *   misaligned plane, cus or per-LCU array, a bad size or stride, kvz_hip_sao_frames' dst == rec, start_qp outside 0..51, chain_rows
+ *   other than 0 and 1), an invalid grid, deblock.chroma != chroma, src.width / src.height that differ from width / height, shared
+ *   outputs, and a record whose grid no longer fits the pool of KVZ_HIP_CHAIN_TILE_BOUNDS boundaries that the grids of a call share
+ *   (cols + rows + 2 values per record with a grid).  Every record is checked before anything is launched: a refusal writes nothing
+ *   for any picture, and kvz_hip_last_error() names the record's index ("picture 2") -- for the pool, the record at which it
+ *   overflowed.
+ * Execution: asynchronous on s; no host synchronisation, no allocation, no workspace, no atomics on memory -- the call owns no device
+ *   buffer.  The records (64 / 120 / 96 / 120 bytes per picture for the four entries) and the pool travel in the kernel arguments,
+ *   below 4 KB, and are read with scalar loads.  Usable between kvz_hip_graph_begin / _end.  The launch shapes depend only on the
+ *   sizes, the chroma flags, the grids, chain_rows and the presence of cands: a captured call may be replayed after the CONTENTS of
+ *   every device array changed.
+ * Launches: the single entries' own, each covering all pictures -- 3 for kvz_hip_cu_qp_frames, 2 for kvz_hip_deblock_frames, 1 for
+ *   kvz_hip_sao_stats_frames, 1 for kvz_hip_sao_frames.  A launch is sized for the largest picture of the call; the surplus
+ *   workgroups of a smaller picture leave at once.
+ * LEFT OUT ON PURPOSE: prediction of several pictures (kvz_hip_inter_recon_frame: each picture brings a table of up to sixteen
+ *   40-byte reference pictures, and sixteen such tables do not fit the 4 KB of kernel arguments; a reference pool that the records
+ *   share is a design of its own); pictures coded with --lossless, whose chain ends before deblocking; the SAO mode / merge decision
+ *   and RDOQ, which stay with the host.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_cu_qp_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_sao_stats_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_sao_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */

@@ -107,6 +107,23 @@ class ChainPictureTs(C.Structure):
                 ("tr_skip_out", C.c_void_p)]
 
 
+class DeblockParams(C.Structure):
+    """kvz_hip_deblock_params"""
+    _fields_ = [("beta_offset_div2", C.c_int32), ("tc_offset_div2", C.c_int32), ("qp", C.c_int32), ("frame_qp", C.c_int32),
+                ("per_cu_qp", C.c_int32), ("slice_is_b", C.c_int32), ("chroma", C.c_int32), ("reserved", C.c_int32),
+                ("ref_LX", (C.c_uint8 * 16) * 2)]
+
+
+class FilterPicture(C.Structure):
+    """kvz_hip_filter_picture"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("chroma", C.c_int32), ("reserved", C.c_int32), ("src", RefPicture),
+                ("rec_y", C.c_void_p), ("rec_u", C.c_void_p), ("rec_v", C.c_void_p), ("stride_y", C.c_uint32), ("stride_c", C.c_uint32),
+                ("dst_y", C.c_void_p), ("dst_u", C.c_void_p), ("dst_v", C.c_void_p), ("dst_stride_y", C.c_uint32), ("dst_stride_c", C.c_uint32),
+                ("cus", C.c_void_p), ("cbf", C.c_void_p), ("lcu_qp", C.c_void_p), ("lcu_last_qp", C.c_void_p), ("stats", C.c_void_p),
+                ("cands", C.c_void_p), ("sao_luma", C.c_void_p), ("sao_chroma", C.c_void_p), ("grid", C.POINTER(TileGrid)),
+                ("deblock", DeblockParams), ("cu_qp", CuQpTilesParams)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -219,6 +236,10 @@ SIGNATURES = {
     "kvz_hip_intra_recon_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
     "kvz_hip_inter_residual_frames_ts": (_I, [C.POINTER(ChainPictureTs), _I, _P]),
     "kvz_hip_intra_recon_frames_ts": (_I, [C.POINTER(ChainPictureTs), _I, _P]),
+    "kvz_hip_cu_qp_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
+    "kvz_hip_deblock_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
+    "kvz_hip_sao_stats_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
+    "kvz_hip_sao_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

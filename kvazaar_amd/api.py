@@ -1137,6 +1137,142 @@ def sao_frame(rec, sao_luma, sao_chroma=None, chroma=1, dst=None, tiles=None):
     return tuple(out + [None] * (3 - len(out)))
 
 
+# ---- several independent pictures through the QP map, deblocking and SAO in one call each ----
+def cu_qp_frames(pictures):
+    """kvz_hip_cu_qp_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of cu_qp_frame_tiles by name
+    (cus, cbf, lcu_qp, start_qp; optional tiles, chain_rows).  Returns the list of cu_qp_frame_tiles' results, one per picture."""
+    return _filter_frames("kvz_hip_cu_qp_frames", [_FilterPicture.cu_qp(**p) for p in pictures])
+
+
+def deblock_frames(pictures):
+    """kvz_hip_deblock_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of deblock_frame by name
+    (y, u, v, cus, prm; optional tiles).  Returns the list of deblock_frame's results, one per picture."""
+    return _filter_frames("kvz_hip_deblock_frames", [_FilterPicture.deblock(**p) for p in pictures])
+
+
+def sao_stats_frames(pictures):
+    """kvz_hip_sao_stats_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of sao_stats_frame by name
+    (src, rec; optional chroma, with_cands).  Returns the list of sao_stats_frame's results, one per picture."""
+    return _filter_frames("kvz_hip_sao_stats_frames", [_FilterPicture.sao_stats(**p) for p in pictures])
+
+
+def sao_frames(pictures):
+    """kvz_hip_sao_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of sao_frame by name (rec,
+    sao_luma; optional sao_chroma, chroma, dst, tiles).  Returns the list of sao_frame's results, one per picture."""
+    return _filter_frames("kvz_hip_sao_frames", [_FilterPicture.sao(**p) for p in pictures])
+
+
+class _FilterPicture:
+    """the arrays of one picture of kvz_hip_cu_qp_frames / _deblock_frames / _sao_stats_frames / _sao_frames on the device, the record
+    with the fields its entry reads, and how the entry's outputs come back"""
+
+    def __init__(self, width, height, chroma, tiles=None):
+        self.keep = []
+        self.record = rec = _lib.FilterPicture()
+        rec.width, rec.height, rec.chroma = width, height, int(chroma)
+        rec.deblock.chroma = int(chroma)
+        if tiles is not None:
+            self.grid = _lib.TileGrid.from_buffer_copy(_grid(tiles).tobytes())
+            rec.grid = C.pointer(self.grid)
+
+    def _rec_planes(self, planes, chroma):
+        r = _stage_planes(planes, chroma)
+        rec = self.record
+        rec.rec_y, rec.stride_y = r[0].ptr, r[0].stride
+        if chroma:
+            rec.rec_u, rec.rec_v, rec.stride_c = r[1].ptr, r[2].ptr, r[1].stride
+        return r
+
+    def _cus(self, cus):
+        cus = np.ascontiguousarray(cus)
+        assert cus.dtype.itemsize == 20 and cus.ndim == 2
+        dcu = DeviceBuffer.from_numpy(cus.view(np.uint8))
+        self.record.cus = dcu.ptr
+        return cus, dcu
+
+    @classmethod
+    def cu_qp(cls, cus, cbf, lcu_qp, start_qp, tiles=None, chain_rows=0):
+        cus = np.ascontiguousarray(cus)
+        height, width = 4 * cus.shape[0], 4 * cus.shape[1]
+        self = cls(width, height, 1, tiles)
+        cus, dcu = self._cus(cus)
+        n = lcu_count(width, height)
+        dcb = DeviceBuffer.from_numpy(np.ascontiguousarray(cbf, dtype=np.uint8).reshape(cus.shape))
+        dq, dl = DeviceBuffer.from_numpy(np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(n)), DeviceBuffer(n)
+        rec = self.record
+        rec.cbf, rec.lcu_qp, rec.lcu_last_qp = dcb.ptr, dq.ptr, dl.ptr
+        rec.cu_qp = _lib.CuQpTilesParams(int(start_qp), int(chain_rows))
+        self.keep += [dcb, dq]
+        self.result = lambda: (dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape), dl.to_numpy(np.int8, (n,)))
+        return self
+
+    @classmethod
+    def deblock(cls, y, u, v, cus, prm, tiles=None):
+        prm = np.ascontiguousarray(prm)
+        assert prm.nbytes == 64
+        params = _lib.DeblockParams.from_buffer_copy(prm.tobytes())
+        chroma = 1 if params.chroma else 0
+        h, w = (y.height, y.width) if isinstance(y, PlaneView) else np.asarray(y).shape
+        self = cls(w, h, params.chroma, tiles)
+        planes = self._rec_planes((y, u, v), chroma)
+        self.record.deblock = params
+        self.keep.append(self._cus(cus)[1])
+        self.result = lambda: tuple([p.download() for p in planes] + [None] * (3 - len(planes)))
+        return self
+
+    @classmethod
+    def sao_stats(cls, src, rec, chroma=1, with_cands=True):
+        chroma = int(chroma)
+        s = _stage_planes(src, chroma)
+        w, h = s[0].w, s[0].h
+        self = cls(w, h, chroma)
+        r = self._rec_planes(rec, chroma)
+        assert (r[0].w, r[0].h) == (w, h)
+        self.record.src = _lib.RefPicture(s[0].ptr, s[1].ptr if chroma else None, s[2].ptr if chroma else None, s[0].stride,
+                                          s[1].stride if chroma else 0, w, h)
+        planes = 3 if chroma else 1
+        n = planes * lcu_count(w, h)
+        ds = DeviceBuffer(n * SAO_LCU_STATS.itemsize)
+        dc = DeviceBuffer(n * SAO_LCU_CAND.itemsize) if with_cands else None
+        self.record.stats, self.record.cands = ds.ptr, dc.ptr if dc else None
+        self.keep += [s, r]
+        shape = (planes, n // planes)
+        self.result = lambda: (ds.to_numpy(np.uint8, (n * SAO_LCU_STATS.itemsize,)).view(SAO_LCU_STATS).reshape(shape),
+                               dc.to_numpy(np.uint8, (n * SAO_LCU_CAND.itemsize,)).view(SAO_LCU_CAND).reshape(shape) if dc else None)
+        return self
+
+    @classmethod
+    def sao(cls, rec, sao_luma, sao_chroma=None, chroma=1, dst=None, tiles=None):
+        chroma = int(chroma)
+        first = rec[0]
+        h, w = (first.height, first.width) if isinstance(first, PlaneView) else np.asarray(first).shape
+        self = cls(w, h, chroma, tiles)
+        self.keep.append(self._rec_planes(rec, chroma))
+        if dst is None:
+            dst = [np.zeros((h >> (1 if k else 0), w >> (1 if k else 0)), np.uint8) for k in range(3)]
+        d = _stage_planes(dst, chroma)
+        assert (d[0].w, d[0].h) == (w, h)
+        n = lcu_count(w, h)
+        infos = [np.ascontiguousarray(a).view(np.int32).reshape(n, 14) if a is not None and np.asarray(a).dtype == SAO_INFO
+                 else (np.ascontiguousarray(a, dtype=np.int32).reshape(n, 14) if a is not None else None) for a in (sao_luma, sao_chroma)]
+        di = [DeviceBuffer.from_numpy(a) if a is not None else None for a in infos]
+        rc = self.record
+        rc.dst_y, rc.dst_stride_y = d[0].ptr, d[0].stride
+        if chroma:
+            rc.dst_u, rc.dst_v, rc.dst_stride_c = d[1].ptr, d[2].ptr, d[1].stride
+        rc.sao_luma, rc.sao_chroma = di[0].ptr, di[1].ptr if di[1] else None
+        self.keep += [di]
+        self.result = lambda: tuple([p.download() for p in d] + [None] * (3 - len(d)))
+        return self
+
+
+def _filter_frames(entry, staged):
+    L = _lib.init()
+    records = (_lib.FilterPicture * max(len(staged), 1))(*[st.record for st in staged])
+    check(getattr(L, entry)(records, len(staged), None), entry[len("kvz_hip_"):])
+    return [st.result() for st in staged]
+
+
 # ---- tile halo exchange: batched rectangle copies on device pointers ----
 def copy_rects(rects, stream=None):
     """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most

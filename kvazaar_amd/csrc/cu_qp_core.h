@@ -60,10 +60,9 @@ __device__ __forceinline__ int cu_of_scu(const cu_qp_args &a, int X0, int Y0, bo
   return key;
 }
 
-__global__ __launch_bounds__(256) void cu_qp_first_kernel(cu_qp_args a)
+// launch 1 for the LCU (lcu_x, lcu_y) of the picture a; s_min: four ints of LDS
+__device__ __forceinline__ void cu_qp_first(const cu_qp_args &a, int lcu_x, int lcu_y, int *s_min)
 {
-  __shared__ int s_min[4];
-  const int lcu_x = blockIdx.x, lcu_y = blockIdx.y;
   bool inside;
   int first;
   cu_of_scu(a, 64 * lcu_x, 64 * lcu_y, inside, first, s_min);
@@ -71,6 +70,12 @@ __global__ __launch_bounds__(256) void cu_qp_first_kernel(cu_qp_args a)
     const size_t lcu = (size_t)lcu_y * a.lcus_x + lcu_x;
     a.lcu_last_qp[lcu] = (int8_t)(first < 256 ? clip_lcu_qp(a.lcu_qp[lcu]) : -1);
   }
+}
+
+__global__ __launch_bounds__(256) void cu_qp_first_kernel(cu_qp_args a)
+{
+  __shared__ int s_min[4];
+  cu_qp_first(a, blockIdx.x, blockIdx.y, s_min);
 }
 
 // v[i] on entry: the QP that LCU i leaves as last_qp, or -1 if it leaves last_qp as it found it.  On return: last_qp on entry to
@@ -81,6 +86,16 @@ __global__ __launch_bounds__(256) void cu_qp_first_kernel(cu_qp_args a)
 // Without it the instantiation is the kernel as it was.
 struct tile_chains { kvz_hip_tile_grid grid; int lcus_x, chain_rows; };
 __device__ __forceinline__ const tile_chains &only(const tile_chains &c) { return c; }
+// Or the table of the pictures of a multi-picture call (kvz_hip_cu_qp_frames, cu_qp_multi.hip), the picture being the grid's third
+// dimension: a picture's record is the argument of the kernels above with its chains, 64 bytes, and its grid is its part of the pool
+// of boundaries that the pictures share (tile_grid.h); v and start_qp are the record's and the kernel's own are not read.  A
+// workgroup reads its record from the kernel arguments with scalar loads; one beyond its picture's chains leaves at once.
+struct cu_qp_pic { cu_qp_args a; pic_tiles tiles; u8 chain_rows, start_qp, pad[2]; };
+struct cu_qp_batch { cu_qp_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; tile_pool pool; };
+static_assert(sizeof(cu_qp_pic) == 64 && sizeof(cu_qp_batch) <= 4096, "the records and the pool travel in the kernel arguments");
+__device__ __forceinline__ const cu_qp_batch &only(const cu_qp_batch &b) { return b; }
+template <typename... T> struct cu_qp_takes_batch { static constexpr bool value = false; };
+template <> struct cu_qp_takes_batch<cu_qp_batch> { static constexpr bool value = true; };
 template <typename... TILES>
 __global__ __launch_bounds__(256) void cu_qp_chain_kernel(int8_t *v, int n_lcu, int chain_lcus, int start_qp, TILES... tiles)
 {
@@ -89,7 +104,20 @@ __global__ __launch_bounds__(256) void cu_qp_chain_kernel(int8_t *v, int n_lcu, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int begin = blockIdx.x * chain_lcus, end = min(n_lcu, begin + chain_lcus);
   int x0 = 0, x1 = 0, y0 = 0, y1 = 0, lcus_x = 0;
-  if constexpr (TILED) {
+  if constexpr (cu_qp_takes_batch<TILES...>::value) {
+    const cu_qp_batch &b = only(tiles...);
+    const cu_qp_pic &p = b.p[blockIdx.z];
+    if ((int)blockIdx.x >= p.tiles.cols || (int)blockIdx.y >= (p.chain_rows ? p.tiles.lcus_y : p.tiles.rows)) return;
+    const pool_grid g = { b.pool, p.tiles };
+    tile_col_span_at(g, (int)blockIdx.x, x0, x1);
+    if (p.chain_rows) { y0 = (int)blockIdx.y; y1 = y0 + 1; }
+    else tile_row_span_at(g, (int)blockIdx.y, y0, y1);
+    v = p.a.lcu_last_qp;
+    start_qp = p.start_qp;
+    lcus_x = p.a.lcus_x;
+    begin = 0;
+    end = (x1 - x0) * (y1 - y0);
+  } else if constexpr (TILED) {
     const tile_chains &c = only(tiles...);
     tile_span_at(c.grid.col_bd, (int)blockIdx.x, x0, x1);
     if (c.chain_rows) { y0 = (int)blockIdx.y; y1 = y0 + 1; }
@@ -131,10 +159,10 @@ __global__ __launch_bounds__(256) void cu_qp_chain_kernel(int8_t *v, int n_lcu, 
   }
 }
 
-__global__ __launch_bounds__(256) void cu_qp_write_kernel(cu_qp_args a)
+// launch 3 for the LCU (lcu_x, lcu_y) of the picture a
+__device__ __forceinline__ void cu_qp_write(const cu_qp_args &a, int lcu_x, int lcu_y, int *s_min)
 {
-  __shared__ int s_min[4];
-  const int lcu_x = blockIdx.x, lcu_y = blockIdx.y, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   bool inside;
   int first;
   const int key = cu_of_scu(a, 64 * lcu_x, 64 * lcu_y, inside, first, s_min);
@@ -143,6 +171,12 @@ __global__ __launch_bounds__(256) void cu_qp_write_kernel(cu_qp_args a)
   const int qp = key < first ? (int)a.lcu_last_qp[lcu] : clip_lcu_qp(a.lcu_qp[lcu]);
   const size_t scu = (size_t)(16 * lcu_y + (tid >> 4)) * a.cus_stride + 16 * lcu_x + (tid & 15);
   ((u8 *)a.cus)[scu * 20 + 6] = (u8)qp;
+}
+
+__global__ __launch_bounds__(256) void cu_qp_write_kernel(cu_qp_args a)
+{
+  __shared__ int s_min[4];
+  cu_qp_write(a, blockIdx.x, blockIdx.y, s_min);
 }
 
 }  // namespace

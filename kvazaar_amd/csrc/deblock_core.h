@@ -147,20 +147,53 @@ __device__ __forceinline__ u32 pack4(const int *m) { return (u32)m[0] | ((u32)m[
 // the sub-picture state->tile->frame, x == 0 or y == 0 of filter_deblock_unit -- and the right edge of a tile ends the horizontal
 // edges as the right edge of the picture does.  Without it the instantiation is the kernel as it was; each of the two has a
 // translation unit of its own (deblock.hip, deblock_tiles.hip).
+// Or the table of the pictures of a multi-picture call (kvz_hip_deblock_frames, deblock_multi.hip), the picture being the grid's
+// second dimension: the planes, the map and the parameters are the record's -- the kernel's own are not read -- and the grid is the
+// picture's part of the pool of boundaries that the pictures share (tile_grid.h).  A workgroup reads its record from the kernel
+// arguments with scalar loads; a thread beyond its picture's segments leaves at once, as in the single-picture kernels.
 __device__ __forceinline__ const kvz_hip_tile_grid &only(const kvz_hip_tile_grid &g) { return g; }
+struct deblock_pic {                     // 120 bytes
+  const u32 *cus;
+  u8 *rec_y, *rec_u, *rec_v;
+  u32 stride_y, stride_c;
+  kvz_hip_deblock_params prm;
+  pic_tiles tiles;
+  uint16_t width, height;
+};
+struct deblock_batch { deblock_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; tile_pool pool; };
+static_assert(sizeof(deblock_pic) == 120 && sizeof(deblock_batch) <= 4096, "the records and the pool travel in the kernel arguments");
+__device__ __forceinline__ const deblock_batch &only(const deblock_batch &b) { return b; }
+template <typename... T> struct deblock_takes_batch { static constexpr bool value = false; };
+template <> struct deblock_takes_batch<deblock_batch> { static constexpr bool value = true; };
+// the parameters of the thread's picture: the kernel's own, or the record's where they stand in the kernel arguments
+template <typename... TILES>
+__device__ __forceinline__ const kvz_hip_deblock_params &deblock_params_of(const kvz_hip_deblock_params &own, const TILES &... tiles)
+{
+  if constexpr (deblock_takes_batch<TILES...>::value) return only(tiles...).p[blockIdx.y].prm;
+  else return own;
+}
+__device__ __forceinline__ bool tile_col_starts(const deblock_batch &b, int l) { return tile_col_starts(pool_grid{ b.pool, b.p[blockIdx.y].tiles }, l); }
+__device__ __forceinline__ bool tile_row_starts(const deblock_batch &b, int l) { return tile_row_starts(pool_grid{ b.pool, b.p[blockIdx.y].tiles }, l); }
 template <int DIR, typename... TILES>
 __global__ __launch_bounds__(256) void deblock_pass_kernel(u8 *__restrict__ rec_y, u32 stride_y, u8 *__restrict__ rec_u, u8 *__restrict__ rec_v,
-                                                          u32 stride_c, frame_t f, kvz_hip_deblock_params prm, TILES... tiles)
+                                                          u32 stride_c, frame_t f, kvz_hip_deblock_params own, TILES... tiles)
 {
   constexpr bool TILED = sizeof...(TILES) != 0;
+  const kvz_hip_deblock_params &prm = deblock_params_of(own, tiles...);
+  if constexpr (deblock_takes_batch<TILES...>::value) {
+    const deblock_pic &p = only(tiles...).p[blockIdx.y];
+    rec_y = p.rec_y; rec_u = p.rec_u; rec_v = p.rec_v;
+    stride_y = p.stride_y; stride_c = p.stride_c;
+    f = frame_t{ p.cus, (p.width + 3) >> 2, p.width, p.height };
+  }
   const int uw = f.width >> 3, rows = (f.height >> 3) * 2;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)uw * rows) return;
   const int row = (int)(t / uw), ux = (int)(t - (size_t)row * uw) * 8, uy = (row >> 1) * 8, s = row & 1;
   if ((DIR == 0 && ux == 0) || (DIR == 1 && uy == 0)) return;            // filter_deblock_unit, :635-636
   if constexpr (TILED) {
-    const kvz_hip_tile_grid &g = only(tiles...);
-    if (DIR == 0 ? ((ux & 63) == 0 && tile_starts_at(g.col_bd, g.cols, ux >> 6)) : ((uy & 63) == 0 && tile_starts_at(g.row_bd, g.rows, uy >> 6))) return;
+    const auto &g = only(tiles...);
+    if (DIR == 0 ? ((ux & 63) == 0 && tile_col_starts(g, ux >> 6)) : ((uy & 63) == 0 && tile_row_starts(g, uy >> 6))) return;
   }
 
   // ---- luma segment s of the unit ----
@@ -169,8 +202,8 @@ __global__ __launch_bounds__(256) void deblock_pass_kernel(u8 *__restrict__ rec_
     // (filter_deblock_lcu_rightmost, :711-731): its boundary flags and QP are taken at that half's own SCU
     bool deferred = DIR == 1 && ((ux + 8) & 63) == 0 && ux + 8 != f.width;
     if constexpr (TILED && DIR == 1) {
-      const kvz_hip_tile_grid &g = only(tiles...);
-      deferred = deferred && !tile_starts_at(g.col_bd, g.cols, (ux + 8) >> 6);     // rightmost_4px_of_frame of the tile's frame
+      const auto &g = only(tiles...);
+      deferred = deferred && !tile_col_starts(g, (ux + 8) >> 6);     // rightmost_4px_of_frame of the tile's frame
     }
     const int fx = (deferred && s == 1) ? ux + 4 : ux;
     bool tu_b;

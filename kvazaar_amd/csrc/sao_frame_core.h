@@ -66,11 +66,25 @@ __device__ __forceinline__ u32 edge_dword(const u32 *s, int pitch, int at, int g
 // TILES: nothing (kvz_hip_sao_frame), or the grid of a tiled picture as an optional trailing argument (kvz_hip_sao_frame_tiles).  A
 // workgroup's tile lies inside one LCU, so the rectangle is workgroup-uniform.  Without it the instantiation is the kernel as it
 // was; each of the two has a translation unit of its own (sao_frame.hip, sao_frame_tiles.hip).
+// Or the table of the pictures of a multi-picture call (kvz_hip_sao_frames, sao_frame_multi.hip), the picture being the grid's
+// second dimension: `a` is the record's -- the kernel's own is not read -- and the grid is the picture's part of the pool of
+// boundaries that the pictures share (tile_grid.h).  A workgroup reads its record from the kernel arguments with scalar loads; one
+// beyond its picture's tiles leaves at once.
 __device__ __forceinline__ const kvz_hip_tile_grid &only(const kvz_hip_tile_grid &g) { return g; }
+struct frame_pic { frame_args a; pic_tiles tiles; int pad; };       // 120 bytes
+struct frame_batch { frame_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; tile_pool pool; };
+static_assert(sizeof(frame_pic) == 120 && sizeof(frame_batch) <= 4096, "the records and the pool travel in the kernel arguments");
+__device__ __forceinline__ const frame_batch &only(const frame_batch &b) { return b; }
+template <typename... T> struct sao_takes_batch { static constexpr bool value = false; };
+template <> struct sao_takes_batch<frame_batch> { static constexpr bool value = true; };
 template <typename... TILES>
 __global__ __launch_bounds__(256) void sao_frame_kernel(frame_args a, TILES... tiles)
 {
   __shared__ u32 s_t[10 * 34];              // the larger of 18 x 18 (luma) and 10 x 34 (chroma) dwords
+  if constexpr (sao_takes_batch<TILES...>::value) {
+    a = only(tiles...).p[blockIdx.y].a;     // every field is read at a constant index: scalar loads, no copy in memory
+    if ((int)blockIdx.x >= a.tiles_y + 2 * a.tiles_c) return;
+  }
   const int tid = threadIdx.x;
   int b = (int)blockIdx.x, plane = 0;
   if (b >= a.tiles_y) { b -= a.tiles_y; plane = 1; if (b >= a.tiles_c) { b -= a.tiles_c; plane = 2; } }
@@ -84,6 +98,14 @@ __global__ __launch_bounds__(256) void sao_frame_kernel(frame_args a, TILES... t
     int cx0, cx1, ry0, ry1;
     tile_span_of(g.col_bd, g.cols, lx, cx0, cx1);
     tile_span_of(g.row_bd, g.rows, plane ? tr : (ty0 >> 6), ry0, ry1);
+    const int u = 64 >> sh;
+    return px_rect{ u * cx0, u * ry0, min(u * cx1, pw), min(u * ry1, ph) };
+  };
+  const auto rect_of_picture = [&](const frame_batch &t) {
+    const pool_grid g = { t.pool, t.p[blockIdx.y].tiles };
+    int cx0, cx1, ry0, ry1;
+    tile_col_span_of(g, lx, cx0, cx1);
+    tile_row_span_of(g, plane ? tr : (ty0 >> 6), ry0, ry1);
     const int u = 64 >> sh;
     return px_rect{ u * cx0, u * ry0, min(u * cx1, pw), min(u * ry1, ph) };
   };
@@ -113,7 +135,9 @@ __global__ __launch_bounds__(256) void sao_frame_kernel(frame_args a, TILES... t
     if (!inside) return;
     const int at = (r + 1) * pitch + c + 1;
     if constexpr (sizeof...(TILES) != 0) {
-      const px_rect q = rect_of(tiles...);                      // once per workgroup, by the edge workgroups only
+      px_rect q;                                                // once per workgroup, by the edge workgroups only
+      if constexpr (sao_takes_batch<TILES...>::value) q = rect_of_picture(tiles...);
+      else q = rect_of(tiles...);
       switch (cls) {
         case 0: out = edge_dword<0>(s_t, pitch, at, gx, gy, pw, ph, s_off, q); break;
         case 1: out = edge_dword<1>(s_t, pitch, at, gx, gy, pw, ph, s_off, q); break;

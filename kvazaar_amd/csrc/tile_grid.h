@@ -1,5 +1,6 @@
 // tile_grid.h -- kvz_hip_tile_grid on the host and on the device, for the four *_tiles entries of the picture chain
-// (intra_recon_tiles.hip, cu_qp_tiles.hip, deblock_tiles.hip, sao_frame_tiles.hip).
+// (intra_recon_tiles.hip, cu_qp_tiles.hip, deblock_tiles.hip, sao_frame_tiles.hip).  At the end: the grids of the pictures of a multi-picture
+// call, which share one pool of boundaries (cu_qp_multi.hip, deblock_multi.hip, sao_frame_multi.hip).
 //
 // The grid travels to every kernel by value (392 bytes of kernel arguments).  The lookups below index it with constants only --
 // the loops are fully unrolled and select -- because a dynamically indexed kernel argument array is copied to scratch; with a
@@ -109,5 +110,76 @@ __device__ __forceinline__ bool tile_starts_at(const int32_t (&bd)[KVZ_HIP_MAX_T
   if (n > TILE_NEAR) hit = hit || tile_starts_part<TILE_NEAR + 1, TILE_MAX>(bd, n, l);
   return hit;
 }
+
+// ---- the grids of the pictures of a multi-picture call (cu_qp_multi.hip, deblock_multi.hip, sao_frame_multi.hip) ----
+// Sixteen kvz_hip_tile_grid do not fit the kernel arguments; the boundaries that a call uses do, as in kvz_hip_*_frames_ts: one pool of
+// KVZ_HIP_CHAIN_TILE_BOUNDS 16-bit values (an LCU index is at most 256) that the records share, two to a dword.  A picture's record
+// says where its cols + 1 column and rows + 1 row boundaries stand.  A picture without a grid is one tile and takes nothing from the
+// pool: the first boundary is 0 and the last is the picture's LCU count, so only the boundaries between them are ever read.
+struct tile_pool {
+  u32 bd[KVZ_HIP_CHAIN_TILE_BOUNDS / 2];
+  __device__ __forceinline__ int bound(int i) const { return (int)((bd[i >> 1] >> (16 * (i & 1))) & 0xffffu); }
+};
+struct pic_tiles { uint16_t col_at, row_at, lcus_x, lcus_y; u8 cols, rows, pad[2]; };
+static_assert(sizeof(tile_pool) == 2 * KVZ_HIP_CHAIN_TILE_BOUNDS && sizeof(pic_tiles) == 12, "kernel arguments");
+// what a kernel hands to the lookups: both live in the kernel arguments, so every read is a scalar load
+struct pool_grid { const tile_pool &pool; const pic_tiles &t; };
+
+// -> false where the pool is full.  g: what tile_grid_make made of grid
+inline bool tile_pool_add(const kvz_hip_tile_grid *grid, const kvz_hip_tile_grid &g, uint16_t *bounds, int &used, pic_tiles *t)
+{
+  __builtin_memset(t, 0, sizeof *t);
+  t->cols = (u8)g.cols; t->rows = (u8)g.rows;
+  t->lcus_x = (uint16_t)g.col_bd[g.cols]; t->lcus_y = (uint16_t)g.row_bd[g.rows];
+  if (!grid) return true;
+  if (used + g.cols + g.rows + 2 > KVZ_HIP_CHAIN_TILE_BOUNDS) return false;
+  t->col_at = (uint16_t)used;
+  for (int j = 0; j <= g.cols; ++j) bounds[used++] = (uint16_t)g.col_bd[j];
+  t->row_at = (uint16_t)used;
+  for (int j = 0; j <= g.rows; ++j) bounds[used++] = (uint16_t)g.row_bd[j];
+  return true;
+}
+inline void tile_pool_pack(const uint16_t *bounds, int used, tile_pool *pool)
+{
+  __builtin_memset(pool, 0, sizeof *pool);
+  for (int j = 0; j < used; ++j) pool->bd[j >> 1] |= (u32)bounds[j] << (16 * (j & 1));
+}
+
+// The lookups that the shared cores use, for a kvz_hip_tile_grid (the single-picture kernels: the functions above) and for a picture's
+// part of the pool (a loop over the boundaries between the first and the last; wave-uniform where the LCU position is).
+__device__ __forceinline__ bool tile_col_starts(const kvz_hip_tile_grid &g, int l) { return tile_starts_at(g.col_bd, g.cols, l); }
+__device__ __forceinline__ bool tile_row_starts(const kvz_hip_tile_grid &g, int l) { return tile_starts_at(g.row_bd, g.rows, l); }
+__device__ __forceinline__ void tile_col_span_of(const kvz_hip_tile_grid &g, int l, int &lo, int &hi) { tile_span_of(g.col_bd, g.cols, l, lo, hi); }
+__device__ __forceinline__ void tile_row_span_of(const kvz_hip_tile_grid &g, int l, int &lo, int &hi) { tile_span_of(g.row_bd, g.rows, l, lo, hi); }
+__device__ __forceinline__ void tile_col_span_at(const kvz_hip_tile_grid &g, int t, int &lo, int &hi) { tile_span_at(g.col_bd, t, lo, hi); }
+__device__ __forceinline__ void tile_row_span_at(const kvz_hip_tile_grid &g, int t, int &lo, int &hi) { tile_span_at(g.row_bd, t, lo, hi); }
+
+__device__ __forceinline__ bool pool_starts(const tile_pool &pool, int at, int n, int last, int l)
+{
+  bool hit = l == last;
+  for (int j = 1; j < n; ++j) hit = hit || pool.bound(at + j) == l;
+  return hit;
+}
+__device__ __forceinline__ void pool_span_of(const tile_pool &pool, int at, int n, int last, int l, int &lo, int &hi)
+{
+  lo = 0;
+  hi = last;
+  for (int j = 1; j < n; ++j) {
+    const int b = pool.bound(at + j);
+    if (b <= l) lo = b;
+    else hi = min(hi, b);
+  }
+}
+__device__ __forceinline__ void pool_span_at(const tile_pool &pool, int at, int n, int last, int t, int &lo, int &hi)
+{
+  lo = t > 0 ? pool.bound(at + t) : 0;
+  hi = t + 1 < n ? pool.bound(at + t + 1) : last;
+}
+__device__ __forceinline__ bool tile_col_starts(const pool_grid &g, int l) { return pool_starts(g.pool, g.t.col_at, g.t.cols, g.t.lcus_x, l); }
+__device__ __forceinline__ bool tile_row_starts(const pool_grid &g, int l) { return pool_starts(g.pool, g.t.row_at, g.t.rows, g.t.lcus_y, l); }
+__device__ __forceinline__ void tile_col_span_of(const pool_grid &g, int l, int &lo, int &hi) { pool_span_of(g.pool, g.t.col_at, g.t.cols, g.t.lcus_x, l, lo, hi); }
+__device__ __forceinline__ void tile_row_span_of(const pool_grid &g, int l, int &lo, int &hi) { pool_span_of(g.pool, g.t.row_at, g.t.rows, g.t.lcus_y, l, lo, hi); }
+__device__ __forceinline__ void tile_col_span_at(const pool_grid &g, int t, int &lo, int &hi) { pool_span_at(g.pool, g.t.col_at, g.t.cols, g.t.lcus_x, t, lo, hi); }
+__device__ __forceinline__ void tile_row_span_at(const pool_grid &g, int t, int &lo, int &hi) { pool_span_at(g.pool, g.t.row_at, g.t.rows, g.t.lcus_y, t, lo, hi); }
 
 }  // namespace

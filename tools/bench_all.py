@@ -250,6 +250,109 @@ def main():
     if not args.only or any(o in "intra_recon_frames_ts_1080p_all_tiles4x2_x4 intra_recon_frames_ts_1080p_mixed_tiles4x2_x4 intra_recon_frames_ts_1080p_all_trskip_x4 "
                             "inter_residual_frames_ts_1080p_x4" for o in args.only.split(",")):
         chain_multi_ts_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "cu_qp_frames_1080p_x4 deblock_frames_1080p_x4 sao_stats_frames_1080p_x4 sao_frames_1080p_x4 deblock_frames_1080p_tiles4x2_x4 "
+                            "sao_frames_1080p_tiles4x2_x4" for o in args.only.split(",")):
+        chain_filter_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+
+
+def chain_filter_multi_rows(L, st, dev, rounds, only, pictures=4, iters=20):
+    """Four distinct 1080p 4:2:0 pictures of the kind the cu_qp_frame_1080p, deblock_frame_1080p, sao_stats_frame_1080p and sao_frame_1080p
+    rows use (the same generators, seeds of their own) through ONE call of kvz_hip_cu_qp_frames / kvz_hip_deblock_frames /
+    kvz_hip_sao_stats_frames / kvz_hip_sao_frames and, in the same rounds, interleaved, through four back-to-back calls of the
+    single-picture entry that takes the same options: the untiled entries, and for *_tiles4x2_x4 the *_tiles entries with 4 x 2 uniform
+    tiles in every picture.  ms per batch of four pictures: median and min..max over the rounds, and the ratio of the medians; `launches`
+    counts dependent launches (one call / four calls).  Deblocking works in place on planes that earlier iterations have filtered, as in the
+    deblock_frame_1080p row: both sides of a row see the same sequence of contents."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import intra_recon_cases as XC
+    from patterns import deblock_case, deblock_params, sao_records
+    from kvazaar_amd import api
+    W, H, DH = 1920, 1080, 1088
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+    grid = api.uniform_tile_grid(W, H, 4, 2)                     # 1080 and the 1088 coded rows are the same 17 LCU rows
+    grid_p = C.cast(grid.ctypes.data, C.POINTER(_lib.TileGrid))
+    n_lcu = api.lcu_count(W, H)
+    g = torch.Generator(device=dev); g.manual_seed(23)
+    dbp = deblock_params(qp=36)
+    qprm, tprm = np.zeros(1, dtype=api.CU_QP_PARAMS), np.zeros(1, dtype=api.CU_QP_TILES_PARAMS)
+    qprm["start_qp"] = tprm["start_qp"] = 27
+    luma_d, chro_d = torch.from_numpy(sao_records(n_lcu, 7)).to(dev), torch.from_numpy(sao_records(n_lcu, 8)).to(dev)
+    keep, plain, tiled = [], (_lib.FilterPicture * pictures)(), (_lib.FilterPicture * pictures)()
+    single = {k: [] for k in ("cu_qp", "deblock", "deblock_tiles", "sao_stats", "sao", "sao_tiles")}
+    for i in range(pictures):
+        # the QP map: a quadtree with about 10 % intra CUs, random coded flags, a QP per LCU
+        cus, _, _ = XC.make_map(W, H, 171 + 10 * i, intra_share=0.1, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+        cus_d = up(cus)
+        cbf_d = (torch.rand(cus.shape, device=dev, generator=g) < 0.5).to(torch.uint8)
+        qp_d = up(np.random.default_rng(172 + 10 * i).integers(22, 43, n_lcu).astype(np.int8))
+        last_d = torch.empty(n_lcu, dtype=torch.int8, device=dev)
+        # deblocking: the picture of the deblock_frame_1080p row from another seed (1088 coded rows)
+        ty, tu, tv, tcus = deblock_case(256, 128, 21 + i, qp=36)
+        reps = (DH // 128 + 1, W // 256 + 1)
+        dby, dbu, dbv = (up(np.tile(p, reps)[:DH >> c, :W >> c]) for p, c in ((ty, 0), (tu, 1), (tv, 1)))
+        dbc = up(np.tile(tcus, reps)[:DH // 4, :W // 4])
+        # SAO: a random source and a reconstruction near it, records as after a decision
+        src = [torch.randint(0, 256, (H >> c, W >> c), dtype=torch.uint8, device=dev, generator=g) for c in (0, 1, 1)]
+        rec = [(p.to(torch.int16) + torch.randint(-8, 9, p.shape, dtype=torch.int16, device=dev, generator=g)).clamp_(0, 255).to(torch.uint8) for p in src]
+        dst = [torch.empty_like(p) for p in rec]
+        stats = torch.empty(3 * n_lcu * 104, dtype=torch.int32, device=dev)
+        cands = torch.empty(3 * n_lcu * 30, dtype=torch.int32, device=dev)
+        table = api.ref_picture_table([(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), W, W // 2)], W, H)
+        keep.append((cus_d, cbf_d, qp_d, last_d, dby, dbu, dbv, dbc, src, rec, dst, stats, cands, table))
+        # one record per stage and picture would do; the rows share one with the fields of the stage they time, so the QP map and the
+        # SAO stages (1080 rows) and deblocking (1088 rows) get records of their own
+        for recs, gp in ((plain, None), (tiled, grid_p)):
+            r = recs[i]
+            r.width, r.height, r.chroma, r.deblock, r.grid = W, H, 1, _lib.DeblockParams.from_buffer_copy(dbp.tobytes()), gp
+            r.src = _lib.RefPicture(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), W, W // 2, W, H)
+            r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), W, W // 2
+            r.dst_y, r.dst_u, r.dst_v, r.dst_stride_y, r.dst_stride_c = dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), W, W // 2
+            r.cus, r.cbf, r.lcu_qp, r.lcu_last_qp = cus_d.data_ptr(), cbf_d.data_ptr(), qp_d.data_ptr(), last_d.data_ptr()
+            r.stats, r.cands, r.sao_luma, r.sao_chroma = stats.data_ptr(), cands.data_ptr(), luma_d.data_ptr(), chro_d.data_ptr()
+            r.cu_qp = _lib.CuQpTilesParams(27, 0)
+        planes = (rec[0].data_ptr(), W, rec[1].data_ptr(), rec[2].data_ptr(), W // 2)
+        dplanes = (dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2)
+        sao_args = planes + (dst[0].data_ptr(), W, dst[1].data_ptr(), dst[2].data_ptr(), W // 2, W, H, luma_d.data_ptr(), chro_d.data_ptr(), 1)
+        single["cu_qp"].append((L.kvz_hip_cu_qp_frame, (cus_d.data_ptr(), cbf_d.data_ptr(), W, H, qp_d.data_ptr(), last_d.data_ptr(), qprm.ctypes.data, st)))
+        single["deblock"].append((L.kvz_hip_deblock_frame, dplanes + (W, DH, dbc.data_ptr(), dbp.ctypes.data, st)))
+        single["deblock_tiles"].append((L.kvz_hip_deblock_frame_tiles, dplanes + (W, DH, dbc.data_ptr(), grid.ctypes.data, dbp.ctypes.data, st)))
+        single["sao_stats"].append((L.kvz_hip_sao_stats_frame, (table.ctypes.data,) + planes + (1, stats.data_ptr(), cands.data_ptr(), st)))
+        single["sao"].append((L.kvz_hip_sao_frame, sao_args + (st,)))
+        single["sao_tiles"].append((L.kvz_hip_sao_frame_tiles, sao_args + (grid.ctypes.data, st)))
+    # deblocking: the records of the 1088-row pictures
+    deb, deb_tiled = (_lib.FilterPicture * pictures)(), (_lib.FilterPicture * pictures)()
+    for recs, gp in ((deb, None), (deb_tiled, grid_p)):
+        for i, k in enumerate(keep):
+            r = recs[i]
+            r.width, r.height, r.chroma, r.deblock, r.grid = W, DH, 1, _lib.DeblockParams.from_buffer_copy(dbp.tobytes()), gp
+            r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c, r.cus = k[4].data_ptr(), k[5].data_ptr(), k[6].data_ptr(), W, W // 2, k[7].data_ptr()
+    rows = (("cu_qp_frames_1080p_x4", 3, L.kvz_hip_cu_qp_frames, plain, "cu_qp"), ("deblock_frames_1080p_x4", 2, L.kvz_hip_deblock_frames, deb, "deblock"),
+            ("sao_stats_frames_1080p_x4", 1, L.kvz_hip_sao_stats_frames, plain, "sao_stats"), ("sao_frames_1080p_x4", 1, L.kvz_hip_sao_frames, plain, "sao"),
+            ("deblock_frames_1080p_tiles4x2_x4", 2, L.kvz_hip_deblock_frames, deb_tiled, "deblock_tiles"),
+            ("sao_frames_1080p_tiles4x2_x4", 1, L.kvz_hip_sao_frames, tiled, "sao_tiles"))
+    print("%-36s %9s %10s %18s %10s %18s %7s" % ("kernel", "launches", "ms", "min..max ms", "4 calls ms", "min..max ms", "ratio"))
+    torch.cuda.synchronize()
+    for name, launches, entry, recs, key in rows:
+        if not any(o in name for o in only):
+            continue
+
+        def multi():
+            return entry(recs, pictures, st)
+
+        def four():
+            for fn, a in single[key]:
+                rc = fn(*a)
+                if rc:
+                    return rc
+            return 0
+        t = {"multi": [], "single": []}
+        for _ in range(rounds):                          # interleaved round by round
+            t["multi"].append(timed(L, st, lambda: _lib.check(multi(), name), iters=iters, warm=3))
+            t["single"].append(timed(L, st, lambda: _lib.check(four(), name + " (4 calls)"), iters=iters, warm=3))
+        ms, ms4 = float(np.median(t["multi"])), float(np.median(t["single"]))
+        print("%-36s %9s %10.4f %18s %10.4f %18s %7.2f" % (name, "%d/%d" % (launches, pictures * launches), ms, "%.4f..%.4f" % (min(t["multi"]), max(t["multi"])),
+                                                           ms4, "%.4f..%.4f" % (min(t["single"]), max(t["single"])), ms4 / ms))
 
 
 def chain_multi_ts_rows(L, st, dev, rounds, only, pictures=4):

@@ -37,8 +37,11 @@ are left out: encoder.c:623-628 switches sign hiding, transform skip, deblocking
 --pictures N (1..16): N independent pictures in flight.  Each is predicted by a kvz_hip_inter_recon_frame call of its own; then the two
 residual stages of all N go through ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames call (one QP per picture).
 Combines with --tiles, --scaling-list and --transform-skip: the two calls are then kvz_hip_inter_residual_frames_ts and
-kvz_hip_intra_recon_frames_ts, every picture with the same grid, the same tables and the same bit cost.  --lcu-qp (the QP map of
-several pictures is a follow-up) and --lossless (one launch per picture already) stay single-picture and are refused with --pictures.
+kvz_hip_intra_recon_frames_ts, every picture with the same grid, the same tables and the same bit cost.  The stages behind them take
+all N pictures in one call each as well: kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames, and with --lcu-qp
+kvz_hip_cu_qp_frames after the intra stage.  Prediction stays a call per picture: each picture brings a table of up to sixteen reference
+pictures, and sixteen such tables do not fit a kernel's arguments.  --lossless (one launch per picture already) stays single-picture and is
+refused with --pictures.
 """
 import argparse
 import ctypes as C
@@ -159,7 +162,7 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
         del stages["sao"]                                            # no deblocking, no SAO (encoder.c:623-628)
         return stages, keep
     if pictures:
-        # N independent pictures in flight: each is predicted by a call of its own (prediction of several pictures is a follow-up),
+        # N independent pictures in flight: each is predicted by a call of its own (sixteen tables of references do not fit one launch),
         # then ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames take all of them.  Picture 0 is the frame's own;
         # the others have planes, coefficients and intra maps of their own (the inter map and the references are shared inputs).
         # With --tiles, --scaling-list or --transform-skip the two calls are kvz_hip_inter_residual_frames_ts / kvz_hip_intra_recon_frames_ts:
@@ -174,7 +177,8 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
             keep += [sl_q, sl_d, sl]
         ts = _lib.TrSkip(18, 0, None) if trskip else None                # (int)(lambda + 0.5) at QP 27
         grid_p = C.cast(grid.ctypes.data, C.POINTER(_lib.TileGrid)) if tiles else None
-        keep += [ts, grid_p]
+        qp_recs = (_lib.FilterPicture * pictures)()                      # --lcu-qp: the QP map of all pictures in one kvz_hip_cu_qp_frames
+        keep += [ts, grid_p, qp_recs]
         rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
         inter, intra = (Record * pictures)(), (Record * pictures)()
         keep += [rc_src, inter, intra]
@@ -198,6 +202,8 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
                 r.cus, r.intra_modes = cus_d.data_ptr(), modes_d.data_ptr() if modes_d is not None else None
                 r.coeff_y, r.coeff_u, r.coeff_v = c[0].data_ptr(), c[1].data_ptr(), c[2].data_ptr()
                 r.params = _lib.InterResidualParams(27, 0, 0, 1 if sl is not None else 0, 1, 0)
+                if lcu_qp:
+                    r.lcu_qp = ir_qp.data_ptr()
                 if options:
                     full.grid = grid_p
                     if sl is not None:
@@ -206,12 +212,23 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
                         skip = torch.zeros(ir_cus.shape, dtype=torch.uint8, device=dev)
                         keep.append(skip)
                         full.ts, full.tr_skip_out = C.pointer(ts), skip.data_ptr()
+            if lcu_qp:
+                # the flags of the intra stage go to an array per picture (cleared once); the QP array is a shared input
+                cbf_i, last_i = (ir_cbf, ir_last) if i == 0 else (torch.zeros_like(ir_cbf), torch.empty_like(ir_last))
+                keep += [cbf_i, last_i]
+                (intra[i].pic if options else intra[i]).cbf_out = cbf_i.data_ptr()
+                q = qp_recs[i]
+                q.width, q.height, q.chroma, q.deblock.chroma = W, H, 1, 1
+                q.cus, q.cbf, q.lcu_qp, q.lcu_last_qp = x_cus.data_ptr(), cbf_i.data_ptr(), ir_qp.data_ptr(), last_i.data_ptr()
+                q.grid, q.cu_qp = grid_p, _lib.CuQpTilesParams(27, 0)
         if options:
             stages["tu"].append(("inter_residual_frames_ts", pictures, lambda s: L.kvz_hip_inter_residual_frames_ts(inter, pictures, s)))
             stages["tu"].append(("intra_recon_frames_ts", pictures, lambda s: L.kvz_hip_intra_recon_frames_ts(intra, pictures, s)))
         else:
             stages["tu"].append(("inter_residual_frames", pictures, lambda s: L.kvz_hip_inter_residual_frames(inter, pictures, s)))
             stages["tu"].append(("intra_recon_frames", pictures, lambda s: L.kvz_hip_intra_recon_frames(intra, pictures, s)))
+        if lcu_qp:
+            stages["tu"].append(("cu_qp_frames", pictures, lambda s: L.kvz_hip_cu_qp_frames(qp_recs, pictures, s)))
     elif lists or trskip:
         # the packed tables on the device; `none`: no tables, and params->scaling_list stays 0
         sl = None
@@ -319,7 +336,9 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
     dbc = torch.from_numpy(np.tile(tcus, reps)[:DH // 4, :W // 4].copy().view(np.uint8)).to(dev)
     dbp = deblock_params(qp=36, per_cu_qp=1 if lcu_qp else 0)          # per_cu_qp: the filter reads the qp field of the records
     keep += [dby, dbu, dbv, dbc, dbp]
-    if tiles:
+    if pictures:
+        pass                                                             # deblocking of all pictures in one call: below, with the SAO stages
+    elif tiles:
         stages["sao"].insert(0, ("deblock_frame_tiles", 1, lambda s: L.kvz_hip_deblock_frame_tiles(
             dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, W, DH, dbc.data_ptr(), grid.ctypes.data, dbp.ctypes.data, s)))
     else:
@@ -338,6 +357,30 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
     so_chroma = torch.from_numpy(sao_records(n_lcu, 4)).to(dev)
     so_dst = [torch.empty_like(p) for p in (dby, dbu, dbv)]
     keep += [so_src, so_tab, so_stats, so_cands, so_luma, so_chroma, so_dst]
+    if pictures:
+        # the stages behind the residual stages, all pictures in one call each: deblocking in place, the statistics and the SAO
+        # reconstruction.  Picture 0 is the frame's own; the others have planes, statistics and destinations of their own (the map,
+        # the source and the SAO records are shared inputs)
+        f_recs = (_lib.FilterPicture * pictures)()
+        keep.append(f_recs)
+        for i in range(pictures):
+            rec = [dby, dbu, dbv] if i == 0 else [p.clone() for p in (dby, dbu, dbv)]
+            dst = so_dst if i == 0 else [torch.empty_like(p) for p in so_dst]
+            st, cd = (so_stats, so_cands) if i == 0 else (torch.empty_like(so_stats), torch.empty_like(so_cands))
+            keep += [rec, dst, st, cd]
+            r = f_recs[i]
+            r.width, r.height, r.chroma = W, DH, 1
+            r.src = _lib.RefPicture(so_src[0].data_ptr(), so_src[1].data_ptr(), so_src[2].data_ptr(), W, W // 2, W, DH)
+            r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), W, W // 2
+            r.dst_y, r.dst_u, r.dst_v, r.dst_stride_y, r.dst_stride_c = dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), W, W // 2
+            r.cus, r.stats, r.cands = dbc.data_ptr(), st.data_ptr(), cd.data_ptr()
+            r.sao_luma, r.sao_chroma = so_luma.data_ptr(), so_chroma.data_ptr()
+            r.grid = C.cast(grid.ctypes.data, C.POINTER(_lib.TileGrid)) if tiles else None
+            r.deblock = _lib.DeblockParams.from_buffer_copy(dbp.tobytes())
+        stages["sao"].insert(0, ("deblock_frames", pictures, lambda s: L.kvz_hip_deblock_frames(f_recs, pictures, s)))
+        stages["sao"].insert(1, ("sao_stats_frames", pictures * 3 * n_lcu, lambda s: L.kvz_hip_sao_stats_frames(f_recs, pictures, s)))
+        stages["sao"].insert(2, ("sao_frames", pictures, lambda s: L.kvz_hip_sao_frames(f_recs, pictures, s)))
+        return stages, keep
     stages["sao"].insert(1, ("sao_stats_frame", 3 * n_lcu, lambda s: L.kvz_hip_sao_stats_frame(
         so_tab.ctypes.data, dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, 1, so_stats.data_ptr(), so_cands.data_ptr(), s)))
     if tiles:
@@ -411,11 +454,12 @@ def main():
                          "encoder.c:623-628 switches off with sign hiding and transform skip")
     ap.add_argument("--pictures", type=int, default=0, metavar="N",
                     help="N independent pictures (1..16): their two residual stages through kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames, or "
-                         "through the *_frames_ts entries with --tiles, --scaling-list or --transform-skip")
+                         "through the *_frames_ts entries with --tiles, --scaling-list or --transform-skip; the QP map (--lcu-qp), deblocking and SAO "
+                         "through kvz_hip_cu_qp_frames, kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames")
     args = ap.parse_args()
-    if args.pictures and (args.lossless or args.lcu_qp or not 1 <= args.pictures <= 16):
-        ap.error("--pictures N: 1..16, and without --lcu-qp (the QP map of several pictures is not built) and --lossless (one launch per "
-                 "picture already), which stay with the single-picture entries; --tiles, --scaling-list and --transform-skip combine with it")
+    if args.pictures and (args.lossless or not 1 <= args.pictures <= 16):
+        ap.error("--pictures N: 1..16, and without --lossless (one launch per picture already), which stays with the single-picture entries; "
+                 "--lcu-qp, --tiles, --scaling-list and --transform-skip combine with it")
     if args.lossless and (args.lcu_qp or args.scaling_list or args.transform_skip):
         ap.error("--lossless: nothing is quantised, so --lcu-qp, --scaling-list and --transform-skip do not combine with it")
     tiles = tuple(int(v) for v in args.tiles.lower().split("x")) if args.tiles else None
