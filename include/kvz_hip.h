@@ -893,7 +893,9 @@ typedef struct {
  * The records of all SCUs of one PU must agree about the CU's depth and type (cu_array_t holds copies of one
  * cu_info_t, cu.c:167-190); a map that disagrees inside a PU is a caller error: the output inside that CU is
  * unspecified, but no access leaves the planes.  refs, params: HOST, copied at the call.  width, height: multiples of 8
- * and the size of every reference picture.  Coordinates are picture-wide, as for kvz_hip_inter_recon_batch. */
+ * and the size of every reference picture.  Coordinates are picture-wide, as for kvz_hip_inter_recon_batch.
+ * Several independent pictures in one call: kvz_hip_inter_recon_frames, near the end of this header, whose records index one shared
+ * pool of reference pictures. */
 KVZ_HIP_API int kvz_hip_inter_recon_frame(kvz_hip_pixel *pred_y, uint32_t stride_y, kvz_hip_pixel *pred_u, kvz_hip_pixel *pred_v,
                                           uint32_t stride_c, int width, int height, const kvz_hip_cu_info *cus,
                                           const kvz_hip_ref_picture *refs, const kvz_hip_inter_recon_params *params,
@@ -1473,7 +1475,8 @@ typedef struct {
  *   below, which take them.  Behind these two stages, the QP map, deblocking and SAO of several pictures are kvz_hip_cu_qp_frames,
  *   kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames further below.  Prediction of several pictures
  *   (kvz_hip_inter_recon_frame) is
- *   not built: sixteen tables of reference pictures do not fit the kernel arguments (see there).  The ABI version stays 4. */
+ *   kvz_hip_inter_recon_frames at the end of these sections: sixteen tables of reference pictures do not fit the kernel arguments,
+ *   so its records index one shared pool of reference pictures (see there).  The ABI version stays 4. */
 KVZ_HIP_API int kvz_hip_inter_residual_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s);
 
@@ -1530,7 +1533,8 @@ typedef struct {
  * LEFT OUT ON PURPOSE: a call that mixes pictures with and without tables, or with and without ts (a kernel that takes both paths at
  *   run time would carry the code of both); pictures coded with --lossless (one launch each already); prediction of several
  *   pictures (the QP map, deblocking and SAO of several pictures are kvz_hip_cu_qp_frames, kvz_hip_deblock_frames,
- *   kvz_hip_sao_stats_frames and kvz_hip_sao_frames below); RDOQ.  The ABI version stays 4. */
+ *   kvz_hip_sao_stats_frames and kvz_hip_sao_frames below) in these entries -- it is an entry of its own,
+ *   kvz_hip_inter_recon_frames further below; RDOQ.  The ABI version stays 4. */
 KVZ_HIP_API int kvz_hip_inter_residual_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 
@@ -1597,12 +1601,66 @@ typedef struct {
  *   workgroups of a smaller picture leave at once.
  * LEFT OUT ON PURPOSE: prediction of several pictures (kvz_hip_inter_recon_frame: each picture brings a table of up to sixteen
  *   40-byte reference pictures, and sixteen such tables do not fit the 4 KB of kernel arguments; a reference pool that the records
- *   share is a design of its own); pictures coded with --lossless, whose chain ends before deblocking; the SAO mode / merge decision
+ *   share is a design of its own: kvz_hip_inter_recon_frames below); pictures coded with --lossless, whose chain ends before
+ *   deblocking; the SAO mode / merge decision
  *   and RDOQ, which stay with the host.  The ABI version stays 4. */
 KVZ_HIP_API int kvz_hip_cu_qp_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_sao_stats_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_sao_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Several independent pictures through motion compensation at once:   */
+/*   the stage in front of kvz_hip_*_frames(_ts), over one shared      */
+/*   pool of reference pictures                                        */
+/*   reference: kvz_inter_recon_cu (inter.c:492-540) of the pictures   */
+/*   in flight (--owf), which share most of their references           */
+/* ------------------------------------------------------------------ */
+/* The reference pictures of all records of one call: the pictures in flight of a GOP name few distinct pictures, so the records index
+ * ONE pool instead of bringing a table each -- sixteen tables of sixteen 40-byte pictures would not fit a kernel's arguments. */
+#define KVZ_HIP_RECON_POOL_PICTURES 48
+/* One picture of kvz_hip_inter_recon_frames: the arguments of kvz_hip_inter_recon_frame as a record, its table of reference pictures
+ * as indices into the pool.  The record is HOST memory, copied at the call.  Offsets in front of the fields; no implicit padding. */
+typedef struct {
+  kvz_hip_pixel *pred_y, *pred_u, *pred_v;  /*  0,  8, 16: DEVICE destination planes */
+  uint32_t stride_y, stride_c;              /* 24, 28 */
+  int32_t width, height;                    /* 32, 36 */
+  const kvz_hip_cu_info *cus;               /* 40: DEVICE */
+  uint8_t refs[16];                         /* 48: pool index of this picture's reference picture i */
+  kvz_hip_inter_recon_params params;        /* 64: chroma, n_refs, ref_LX -- as for the single entry */
+} kvz_hip_recon_picture;                    /* 104 bytes, no implicit padding */
+/* kvz_hip_inter_recon_frame for n_pictures (0..KVZ_HIP_MAX_CHAIN_PICTURES) pictures that do not depend on each other, in one
+ * asynchronous call and one launch: a batch of P or B pictures goes from the CU map to SAO in one call per stage.
+ * THE RULE: for every picture i, the three destination planes are byte for byte what kvz_hip_inter_recon_frame leaves when called
+ *   with the record's fields and a table refs[k] = pool[pictures[i].refs[k]] for k < params.n_refs.  Everything the single entry
+ *   defines holds per picture: which CUs and PUs are predicted or skipped, "pixels of anything else are left untouched",
+ *   picture-wide coordinates, and unspecified output inside a CU whose records disagree.  Pictures of one call may differ in size,
+ *   chroma format (4:0:0 beside 4:2:0), n_refs and ref_LX, and two records may name the same pool pictures in a different order.
+ * Pool: pool is HOST memory, copied at the call, n_pool in 1..KVZ_HIP_RECON_POOL_PICTURES.  A pool picture that no record names is
+ *   ignored entirely: its fields are not looked at.  A pool picture named by a record must have the record's width and height and
+ *   a valid y / stride_y; if the record is 4:2:0 it must also have valid u, v and stride_c.  The same pool picture may serve a
+ *   4:0:0 record without chroma planes.  refs[k] for k >= n_refs is not read.
+ * Independence is the caller's promise: no destination plane may be a pool plane or a plane of another record.  Records whose
+ *   pred_y bases coincide are refused, and so is a record whose pred_y / pred_u / pred_v base equals the y / u / v base of a pool
+ *   picture named by any record.  Any other overlap is a caller error with unspecified output, but no access leaves a record's
+ *   own arrays.
+ * Errors: n_pictures == 0 is a no-op that returns KVZ_HIP_OK (pictures and pool may then be NULL).  KVZ_HIP_ERR_INVALID: n_pictures
+ *   outside 0..KVZ_HIP_MAX_CHAIN_PICTURES; n_pool outside 1..KVZ_HIP_RECON_POOL_PICTURES when n_pictures > 0; a NULL table; any
+ *   record the single entry would refuse (a missing pointer, a misaligned cus, a bad size or stride, n_refs outside 1..16);
+ *   refs[k] >= n_pool for a k < n_refs; a named pool picture of another size or with missing planes; the aliasing cases above.
+ *   Every record is checked before anything is launched: on refusal nothing is written for any picture, and kvz_hip_last_error()
+ *   names the index of the offending record ("picture 2").  Without a device the entry returns KVZ_HIP_ERR_NO_DEVICE before it
+ *   looks at anything.
+ * Execution: one launch covers all pictures -- the sum over the pictures of ceil(tiles / 4) workgroups, a tile being a 16x16 luma
+ *   block of its picture; a workgroup never spans two pictures.
+ *   Asynchronous on s; no host synchronisation, no allocation, no workspace -- the call owns no device buffer.  Records and pool
+ *   travel in the kernel arguments (88 bytes per picture with its reference lists resolved to pool indices, 40 per pool picture:
+ *   3336 bytes, below 4 KB) and are read with scalar loads; no atomics, no barriers.  Usable between kvz_hip_graph_begin / _end.  The launch shape depends only on the sizes: a captured call
+ *   may be replayed after the CONTENTS of the CU arrays and of every plane changed.
+ * LEFT OUT ON PURPOSE: a per-PU entry over the pool (kvz_hip_inter_recon_batch stays single-picture); more than
+ *   KVZ_HIP_RECON_POOL_PICTURES distinct references in one call (split the call).  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_recon_frames(const kvz_hip_recon_picture *pictures, int n_pictures,
+                                           const kvz_hip_ref_picture *pool, int n_pool, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */

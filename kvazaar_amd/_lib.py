@@ -124,6 +124,20 @@ class FilterPicture(C.Structure):
                 ("deblock", DeblockParams), ("cu_qp", CuQpTilesParams)]
 
 
+RECON_POOL_PICTURES = 48     # KVZ_HIP_RECON_POOL_PICTURES
+
+
+class InterReconParams(C.Structure):
+    """kvz_hip_inter_recon_params"""
+    _fields_ = [("chroma", C.c_int32), ("n_refs", C.c_int32), ("ref_LX", (C.c_uint8 * 16) * 2)]
+
+
+class ReconPicture(C.Structure):
+    """kvz_hip_recon_picture"""
+    _fields_ = [("pred_y", C.c_void_p), ("pred_u", C.c_void_p), ("pred_v", C.c_void_p), ("stride_y", C.c_uint32), ("stride_c", C.c_uint32),
+                ("width", C.c_int32), ("height", C.c_int32), ("cus", C.c_void_p), ("refs", C.c_uint8 * 16), ("params", InterReconParams)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -240,6 +254,7 @@ SIGNATURES = {
     "kvz_hip_deblock_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_sao_stats_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_sao_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
+    "kvz_hip_inter_recon_frames": (_I, [C.POINTER(ReconPicture), _I, C.POINTER(RefPicture), _I, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -658,6 +658,79 @@ def inter_recon_frame(refs, cus, ref_LX, width, height, chroma=1, dest=None):
     return st.result()
 
 
+class _OnDevice:
+    """a 2-D uint8 device tensor used where it lies: the same face as _Staged; download() hands the tensor back"""
+
+    def __init__(self, t):
+        assert t.dim() == 2 and t.element_size() == 1 and t.stride(1) == 1 and t.is_cuda
+        self.t, self.ptr, self.stride, self.w, self.h, self.shape = t, t.data_ptr(), t.stride(0), t.shape[1], t.shape[0], tuple(t.shape)
+
+    def download(self):
+        return self.t
+
+
+def _plane(p):
+    return _OnDevice(p) if hasattr(p, "data_ptr") else _Staged(p)
+
+
+def inter_recon_frames(pictures, pool):
+    """kvz_hip_inter_recon_frames: the prediction of up to 16 pictures over one pool of reference pictures, in one call.
+    pictures: a list of dicts with
+      cus      kvz_hip_cu_info records [height / 4, width / 4] (20 bytes each)
+      refs     the picture's table of reference pictures as indices into pool (1..16 of them)
+      ref_LX   uint8 [2, 16], indices into refs
+      width, height
+      chroma   optional, 1 (4:2:0, the default) or 0
+      dest     optional initial (y, u, v) destination planes (default zeros of the picture size)
+    pool: a list of (y, u, v) planes (u, v None where only 4:0:0 pictures name the entry; an entry may be None and is then left zero,
+    for a slot that no picture names).  A pool picture has the size of the first picture that names it, or else of its y plane.
+    A plane is a uint8 array or PlaneView, staged to the device (a wider array gives a stride), or a 2-D uint8 device tensor, used
+    where it lies; cus likewise an array or a device tensor.  Returns [(y, u, v)] per picture: what the destination planes hold
+    (arrays for staged planes -- the WHOLE buffer for a PlaneView -- and the tensors themselves for device tensors; None for the
+    chroma planes of a 4:0:0 picture)."""
+    L = _lib.init()
+    size_of, keep = {}, []
+    for p in pictures:
+        for k in p["refs"]:
+            size_of.setdefault(int(k), (int(p["width"]), int(p["height"])))
+    table = (_lib.RefPicture * max(len(pool), 1))()
+    for r, planes in enumerate(pool):
+        if planes is None:
+            continue
+        st = [_plane(q) if q is not None else None for q in (tuple(planes) + (None, None))[:3]]
+        keep.append(st)
+        w, h = size_of.get(r, (st[0].w, st[0].h))
+        table[r] = _lib.RefPicture(st[0].ptr, st[1].ptr if st[1] else None, st[2].ptr if st[2] else None, st[0].stride,
+                                   st[1].stride if st[1] else 0, w, h)
+    records, dests = (_lib.ReconPicture * max(len(pictures), 1))(), []
+    for i, p in enumerate(pictures):
+        w, h, chroma = int(p["width"]), int(p["height"]), int(p.get("chroma", 1))
+        cus = p["cus"]
+        if hasattr(cus, "data_ptr"):
+            cus_ptr = cus.data_ptr()
+        else:
+            cus = np.ascontiguousarray(cus)
+            assert cus.dtype.itemsize == 20 and cus.shape == (h // 4, w // 4)
+            cus = DeviceBuffer.from_numpy(cus.view(np.uint8))
+            cus_ptr = cus.ptr
+        dest = p.get("dest")
+        if dest is None:
+            dest = (np.zeros((h, w), np.uint8), np.zeros((h // 2, w // 2), np.uint8), np.zeros((h // 2, w // 2), np.uint8))
+        d = [_plane(q) if q is not None and (k == 0 or chroma) else None for k, q in enumerate((tuple(dest) + (None, None))[:3])]
+        keep += [cus, d]
+        dests.append(d)
+        r = records[i]
+        r.pred_y, r.pred_u, r.pred_v = d[0].ptr, d[1].ptr if d[1] else None, d[2].ptr if d[2] else None
+        r.stride_y, r.stride_c, r.width, r.height, r.cus = d[0].stride, d[1].stride if d[1] else 0, w, h, cus_ptr
+        refs = [int(k) for k in p["refs"]]
+        r.refs[:len(refs)] = refs
+        r.params.chroma, r.params.n_refs = chroma, len(refs)
+        C.memmove(r.params.ref_LX, np.ascontiguousarray(p["ref_LX"], dtype=np.uint8).reshape(2, 16).ctypes.data, 32)
+    check(L.kvz_hip_inter_recon_frames(records, len(pictures), table, len(pool), None), "inter_recon frames")
+    check(L.kvz_hip_stream_sync(None), "stream_sync")
+    return [tuple(q.download() if q else None for q in d) for d in dests]
+
+
 # ---- residual coding of a picture's inter CUs ----
 INTER_RESIDUAL_PARAMS = np.dtype([("qp", "<i4"), ("slice_is_intra", "<i4"), ("signhide", "<i4"), ("scaling_list", "<i4"),
                                   ("chroma", "<i4"), ("reserved", "<i4")])                      # kvz_hip_inter_residual_params

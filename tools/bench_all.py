@@ -253,6 +253,67 @@ def main():
     if not args.only or any(o in "cu_qp_frames_1080p_x4 deblock_frames_1080p_x4 sao_stats_frames_1080p_x4 sao_frames_1080p_x4 deblock_frames_1080p_tiles4x2_x4 "
                             "sao_frames_1080p_tiles4x2_x4" for o in args.only.split(",")):
         chain_filter_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "inter_recon_frames_1080p_p_x4 inter_recon_frames_1080p_b_x4" for o in args.only.split(",")):
+        inter_recon_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+
+
+def inter_recon_multi_rows(L, st, dev, rounds, only, pictures=4, iters=20):
+    """Four distinct 1080p 4:2:0 CU maps from the generator of the inter_recon_frame rows (seeds of their own) through ONE call of
+    kvz_hip_inter_recon_frames and, in the same rounds, interleaved, through four back-to-back calls of kvz_hip_inter_recon_frame.  _p: all
+    four pictures name one shared reference; _b: every PU bi-predicted, each picture from two of three pool pictures.  ms per batch of
+    four pictures: median and min..max over the rounds, and the ratio of the medians; `launches` is one call / four calls."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inter_recon_cases as IC
+    from kvazaar_amd import api
+    W, H = 1920, 1080
+    g = torch.Generator(device=dev); g.manual_seed(29)
+    planes = [[torch.randint(0, 256, (H >> c, W >> c), dtype=torch.uint8, device=dev, generator=g) for c in (0, 1, 1)] for _ in range(3)]
+    pool = (_lib.RefPicture * 3)(*[_lib.RefPicture(p[0].data_ptr(), p[1].data_ptr(), p[2].data_ptr(), W, W // 2, W, H) for p in planes])
+    dest = [[torch.empty((H >> c, W >> c), dtype=torch.uint8, device=dev) for c in (0, 1, 1)] for _ in range(pictures)]
+    print("%-36s %9s %10s %18s %10s %18s %7s" % ("kernel", "launches", "ms", "min..max ms", "4 calls ms", "min..max ms", "ratio"))
+    for name, n_refs in (("inter_recon_frames_1080p_p_x4", 1), ("inter_recon_frames_1080p_b_x4", 2)):
+        if not any(o in name for o in only):
+            continue
+        recs, keep, single = (_lib.ReconPicture * pictures)(), [], []
+        for i in range(pictures):
+            cus, ref_LX = IC.random_cu_map(W, H, 331 + 10 * i, 1, False, intra_share=0.0, blank_share=0.0, bad_share=0.0, far=0.0)
+            refs = (0,)
+            if n_refs == 2:                                               # the same kind of map, every PU from both lists
+                rs = np.random.default_rng(332 + 10 * i)
+                cus["mv_dir"][cus["type"] == IC.CU_INTER] = 3
+                cus["mv"][:, :, 1, :] = rs.integers(-160, 161, cus["mv"][:, :, 1, :].shape)
+                ref_LX[1, 0] = 1
+                refs = ((0, 1), (1, 2), (2, 0), (0, 2))[i % 4]
+            cus_d = torch.from_numpy(cus.view(np.uint8).copy()).to(dev)
+            prm = np.zeros(1, dtype=api.INTER_RECON_PARAMS)
+            prm["chroma"], prm["n_refs"], prm["ref_LX"] = 1, n_refs, ref_LX
+            table = (_lib.RefPicture * n_refs)(*[pool[k] for k in refs])
+            d, r = dest[i], recs[i]
+            r.pred_y, r.pred_u, r.pred_v, r.stride_y, r.stride_c = d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), W, W // 2
+            r.width, r.height, r.cus = W, H, cus_d.data_ptr()
+            r.refs[:n_refs] = refs
+            r.params = _lib.InterReconParams.from_buffer_copy(prm.tobytes())
+            keep.append((cus_d, prm, table))
+            single.append((d[0].data_ptr(), W, d[1].data_ptr(), d[2].data_ptr(), W // 2, W, H, cus_d.data_ptr(), table, prm.ctypes.data, st))
+        torch.cuda.synchronize()
+
+        def multi():
+            return L.kvz_hip_inter_recon_frames(recs, pictures, pool, 3, st)
+
+        def four():
+            for a in single:
+                rc = L.kvz_hip_inter_recon_frame(*a)
+                if rc:
+                    return rc
+            return 0
+        t = {"multi": [], "single": []}
+        for _ in range(rounds):                          # interleaved round by round
+            t["multi"].append(timed(L, st, lambda: _lib.check(multi(), name), iters=iters, warm=3))
+            t["single"].append(timed(L, st, lambda: _lib.check(four(), name + " (4 calls)"), iters=iters, warm=3))
+        ms, ms4 = float(np.median(t["multi"])), float(np.median(t["single"]))
+        print("%-36s %9s %10.4f %18s %10.4f %18s %7.2f" % (name, "%d/%d" % (1, pictures), ms, "%.4f..%.4f" % (min(t["multi"]), max(t["multi"])),
+                                                           ms4, "%.4f..%.4f" % (min(t["single"]), max(t["single"])), ms4 / ms))
 
 
 def chain_filter_multi_rows(L, st, dev, rounds, only, pictures=4, iters=20):

@@ -34,14 +34,14 @@ luma TU is coded transformed and transform-skipped and the cheaper trial is kept
 kvz_hip_intra_recon_frame_lossless (implicit_rdpcm on), one kernel launch each.  The quantising batches, the QP map, deblocking and SAO
 are left out: encoder.c:623-628 switches sign hiding, transform skip, deblocking and SAO off under --lossless.  Combines with --tiles
 (the grid goes to the intra entry); --lcu-qp, --scaling-list and --transform-skip have no meaning without quantisation and are refused.
---pictures N (1..16): N independent pictures in flight.  Each is predicted by a kvz_hip_inter_recon_frame call of its own; then the two
-residual stages of all N go through ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames call (one QP per picture).
+--pictures N (1..16): N independent pictures in flight.  All N are predicted by ONE kvz_hip_inter_recon_frames call over the pool of their
+distinct reference pictures; then the two residual stages of all N go through ONE kvz_hip_inter_residual_frames and ONE
+kvz_hip_intra_recon_frames call (one QP per picture).
 Combines with --tiles, --scaling-list and --transform-skip: the two calls are then kvz_hip_inter_residual_frames_ts and
 kvz_hip_intra_recon_frames_ts, every picture with the same grid, the same tables and the same bit cost.  The stages behind them take
 all N pictures in one call each as well: kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames, and with --lcu-qp
-kvz_hip_cu_qp_frames after the intra stage.  Prediction stays a call per picture: each picture brings a table of up to sixteen reference
-pictures, and sixteen such tables do not fit a kernel's arguments.  --lossless (one launch per picture already) stays single-picture and is
-refused with --pictures.
+kvz_hip_cu_qp_frames after the intra stage.  --lossless (one launch per picture already) stays single-picture and is refused with
+--pictures.
 """
 import argparse
 import ctypes as C
@@ -121,9 +121,10 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
     rc_prm = np.zeros(1, dtype=api.INTER_RECON_PARAMS)
     rc_prm["chroma"], rc_prm["n_refs"], rc_prm["ref_LX"] = 1, 1, rc_LX
     keep += [rc_cus_d, rc_ref, rc_dst, rc_tab, rc_prm]
-    stages["tu"].append(("inter_recon_frame", 1, lambda s: L.kvz_hip_inter_recon_frame(
-        rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data,
-        rc_prm.ctypes.data, s)))
+    if not pictures:                                                    # with --pictures all of them are predicted by one call, below
+        stages["tu"].append(("inter_recon_frame", 1, lambda s: L.kvz_hip_inter_recon_frame(
+            rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data,
+            rc_prm.ctypes.data, s)))
     # the intra CUs of a picture (a tenth of it; tr_depth and modes as tests/intra_recon_cases.py sets them), in coding order on a map
     # and planes of its own: an init launch and one launch per wavefront of LCUs, 63 kernel launches at 1080p for the one call
     import intra_recon_cases as XC
@@ -162,8 +163,8 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
         del stages["sao"]                                            # no deblocking, no SAO (encoder.c:623-628)
         return stages, keep
     if pictures:
-        # N independent pictures in flight: each is predicted by a call of its own (sixteen tables of references do not fit one launch),
-        # then ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames take all of them.  Picture 0 is the frame's own;
+        # N independent pictures in flight: ONE kvz_hip_inter_recon_frames predicts all of them -- the pool is their distinct references,
+        # here the one picture they share -- then ONE kvz_hip_inter_residual_frames and ONE kvz_hip_intra_recon_frames take all of them.  Picture 0 is the frame's own;
         # the others have planes, coefficients and intra maps of their own (the inter map and the references are shared inputs).
         # With --tiles, --scaling-list or --transform-skip the two calls are kvz_hip_inter_residual_frames_ts / kvz_hip_intra_recon_frames_ts:
         # every picture carries the grid, the tables (one set, shared) and a bit cost with an array of choices of its own per stage
@@ -181,19 +182,22 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
         keep += [ts, grid_p, qp_recs]
         rc_src = [cur] + [torch.randint(0, 256, (H // 2, W // 2), dtype=torch.uint8, device=dev, generator=g) for _ in range(2)]
         inter, intra = (Record * pictures)(), (Record * pictures)()
-        keep += [rc_src, inter, intra]
+        recon, rc_pool = (_lib.ReconPicture * pictures)(), (_lib.RefPicture * 1).from_buffer_copy(rc_tab.tobytes())
+        keep += [rc_src, inter, intra, recon, rc_pool]
         for i in range(pictures):
             dst, co = rc_dst, [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
             x_src, x_rec, x_cus, x_modes, x_co = ir_src, ir_rec, ir_cus_d, ir_modes_d, ir_co
             if i:
                 dst = [torch.empty_like(p) for p in rc_dst]
-                stages["tu"].append(("inter_recon_frame", 1, lambda s, dst=dst: L.kvz_hip_inter_recon_frame(
-                    dst[0].data_ptr(), W, dst[1].data_ptr(), dst[2].data_ptr(), W // 2, W, H, rc_cus_d.data_ptr(), rc_tab.ctypes.data, rc_prm.ctypes.data, s)))
                 cus_h, _, modes_h = XC.make_map(W, H, 33 + 10 * i, intra_share=0.1, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
                 src_h, rec_h = XC.make_planes(cus_h, 34 + 10 * i)
                 x_src, x_rec, x_cus, x_modes = [up(p) for p in src_h], [up(p) for p in rec_h], up(cus_h), up(modes_h)
                 x_co = [torch.zeros(ir_shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
             cus_copy = rc_cus_d.clone()                                  # cbf_y is written back: a map per picture
+            p = recon[i]
+            p.pred_y, p.pred_u, p.pred_v, p.stride_y, p.stride_c = dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), W, W // 2
+            p.width, p.height, p.cus = W, H, rc_cus_d.data_ptr()
+            p.refs[0], p.params = 0, _lib.InterReconParams.from_buffer_copy(rc_prm.tobytes())
             keep += [dst, co, x_src, x_rec, x_cus, x_modes, x_co, cus_copy]
             for full, src, rec, cus_d, modes_d, c in ((inter[i], rc_src, dst, cus_copy, None, co), (intra[i], x_src, x_rec, x_cus, x_modes, x_co)):
                 r = full.pic if options else full
@@ -221,6 +225,7 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
                 q.width, q.height, q.chroma, q.deblock.chroma = W, H, 1, 1
                 q.cus, q.cbf, q.lcu_qp, q.lcu_last_qp = x_cus.data_ptr(), cbf_i.data_ptr(), ir_qp.data_ptr(), last_i.data_ptr()
                 q.grid, q.cu_qp = grid_p, _lib.CuQpTilesParams(27, 0)
+        stages["tu"].append(("inter_recon_frames", pictures, lambda s: L.kvz_hip_inter_recon_frames(recon, pictures, rc_pool, 1, s)))
         if options:
             stages["tu"].append(("inter_residual_frames_ts", pictures, lambda s: L.kvz_hip_inter_residual_frames_ts(inter, pictures, s)))
             stages["tu"].append(("intra_recon_frames_ts", pictures, lambda s: L.kvz_hip_intra_recon_frames_ts(intra, pictures, s)))
@@ -453,7 +458,7 @@ def main():
                     help="a frame coded with --lossless: prediction, then the two *_lossless entries; no QP map, deblocking or SAO, which "
                          "encoder.c:623-628 switches off with sign hiding and transform skip")
     ap.add_argument("--pictures", type=int, default=0, metavar="N",
-                    help="N independent pictures (1..16): their two residual stages through kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames, or "
+                    help="N independent pictures (1..16): their prediction through kvz_hip_inter_recon_frames, their two residual stages through kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames, or "
                          "through the *_frames_ts entries with --tiles, --scaling-list or --transform-skip; the QP map (--lcu-qp), deblocking and SAO "
                          "through kvz_hip_cu_qp_frames, kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames")
     args = ap.parse_args()
