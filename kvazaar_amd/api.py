@@ -819,37 +819,67 @@ def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_i
     return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling, trskip, tr_skip)
 
 
+class _StagedPicture:
+    """the arrays of one picture of a residual stage on the device: the source, the prediction (the inter stage) or the reconstruction
+    so far (the intra stage), the coefficients, cbf_out, costs and cus, and modes for the intra stage (None: the inter stage).  coeff,
+    cbf_out, costs: optional initial contents of the outputs, zeros by default"""
+
+    def __init__(self, modes, src, pred, cus, chroma, coeff, cbf_out, costs):
+        self.chroma = chroma = int(chroma)
+        self.height, self.width = src[0].shape
+        self.cus = np.ascontiguousarray(cus)
+        assert self.cus.dtype.itemsize == 20 and self.cus.shape == (self.height // 4, self.width // 4)
+        n = self.n = 3 if chroma else 1
+        self.s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
+        self.r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
+        self.ds, self.dr = [DeviceBuffer.from_numpy(p) for p in self.s], [DeviceBuffer.from_numpy(p) for p in self.r]
+        shapes = coeff_shapes(self.width, self.height)
+        self.co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
+                   else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
+        self.dco = [DeviceBuffer.from_numpy(c) for c in self.co]
+        self.cb = np.zeros(self.cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(self.cus.shape)
+        self.cs = (np.zeros(self.cus.shape, INTER_RESIDUAL_COST) if costs is None
+                   else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(self.cus.shape))
+        self.dcb, self.dcs = DeviceBuffer.from_numpy(self.cb), DeviceBuffer.from_numpy(self.cs.view(np.uint8))
+        self.dcu = DeviceBuffer.from_numpy(self.cus.view(np.uint8))
+        self.dm = None
+        if modes is not None:
+            m = np.ascontiguousarray(modes, dtype=np.uint8)
+            assert m.shape == self.cus.shape + (2,)
+            self.dm = DeviceBuffer.from_numpy(m)
+
+    def loose(self):
+        """the arguments of a single-picture entry: (src table, rec planes and strides, cus), (coeff planes, cbf_out, costs)"""
+        chroma, ds, dr, dco = self.chroma, self.ds, self.dr, self.dco
+        self.table = ref_picture_table([(ds[0].ptr, ds[1].ptr if chroma else 0, ds[2].ptr if chroma else 0, self.s[0].shape[1],
+                                         self.s[1].shape[1] if chroma else 0)], self.width, self.height)
+        planes = (self.table.ctypes.data, dr[0].ptr, self.r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
+                  self.r[1].shape[1] if chroma else 0, self.dcu.ptr)
+        return planes, (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, self.dcb.ptr, self.dcs.ptr)
+
+    def result(self):
+        pad = (None,) * (3 - self.n)
+        return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(self.dr, self.r)) + pad,
+                "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(self.dco, self.co)) + pad,
+                "cus": self.dcu.to_numpy(np.uint8, self.cus.shape + (20,)).view(self.cus.dtype).reshape(self.cus.shape),
+                "cbf_out": self.dcb.to_numpy(np.uint8, self.cb.shape),
+                "costs": self.dcs.to_numpy(np.uint8, self.cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(self.cs.shape)}
+
+
 def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None, scaling=None,
                     trskip=None, tr_skip=None):
     """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries; tiles given (intra only): the
     _tiles entry; scaling given: the _sl entries, the packed arrays uploaded for the call; trskip given: the _ts entries"""
     L = _lib.init()
-    chroma = int(chroma)
-    height, width = src[0].shape
-    cus = np.ascontiguousarray(cus)
-    assert cus.dtype.itemsize == 20 and cus.shape == (height // 4, width // 4)
-    n = 3 if chroma else 1
-    s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
-    r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
-    ds, dr = [DeviceBuffer.from_numpy(p) for p in s], [DeviceBuffer.from_numpy(p) for p in r]
-    table = ref_picture_table([(ds[0].ptr, ds[1].ptr if chroma else 0, ds[2].ptr if chroma else 0, s[0].shape[1],
-                                s[1].shape[1] if chroma else 0)], width, height)
-    shapes = coeff_shapes(width, height)
-    co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
-          else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
-    dco = [DeviceBuffer.from_numpy(c) for c in co]
-    cb = np.zeros(cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(cus.shape)
-    cs = np.zeros(cus.shape, INTER_RESIDUAL_COST) if costs is None else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(cus.shape)
-    dcb, dcs, dcu = DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(cs.view(np.uint8)), DeviceBuffer.from_numpy(cus.view(np.uint8))
-    prm = inter_residual_params(qp, slice_is_intra, signhide, chroma, 0 if scaling is None else 1)
+    st = _StagedPicture(modes, src, pred, cus, chroma, coeff, cbf_out, costs)
+    width, height, cus = st.width, st.height, st.cus
+    prm = inter_residual_params(qp, slice_is_intra, signhide, st.chroma, 0 if scaling is None else 1)
     sl = None
     if scaling is not None:
         tq, td = (np.ascontiguousarray(t, dtype=np.int32).reshape(SL_TABLE_LEN) for t in scaling)
         dtq, dtd = DeviceBuffer.from_numpy(tq), DeviceBuffer.from_numpy(td)
         sl = _lib.ScalingTables(dtq.ptr, dtd.ptr)
-    planes = (table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
-              r[1].shape[1] if chroma else 0, dcu.ptr)
-    outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr)
+    planes, outs = st.loose()
     tail = (prm.ctypes.data, None)
     if lcu_qp is not None:
         lq = np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(lcu_count(width, height))
@@ -872,7 +902,7 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
             check(L.kvz_hip_inter_residual_frame_ts(*planes, *outs, dqp, C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr,
                                                     prm.ctypes.data, None), "inter_residual frame_ts")
         else:
-            dm = DeviceBuffer.from_numpy(modes)
+            dm = st.dm
             check(L.kvz_hip_intra_recon_frame_ts(*planes, dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None,
                                                  C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr, prm.ctypes.data, None),
                   "intra_recon frame_ts")
@@ -884,7 +914,7 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
             entry = L.kvz_hip_inter_residual_frame if lcu_qp is None else L.kvz_hip_inter_residual_frame_qp
             check(entry(*planes, *outs, *tail), "inter_residual frame")
     else:
-        dm = DeviceBuffer.from_numpy(modes)
+        dm = st.dm
         if sl is not None:
             g = _grid(tiles) if tiles is not None else None
             check(L.kvz_hip_intra_recon_frame_sl(*planes, dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None, C.byref(sl), prm.ctypes.data,
@@ -896,12 +926,7 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
         else:
             entry = L.kvz_hip_intra_recon_frame if lcu_qp is None else L.kvz_hip_intra_recon_frame_qp
             check(entry(*planes, dm.ptr, *outs, *tail), "intra_recon frame")
-    pad = (None,) * (3 - n)
-    out = {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
-           "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
-           "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
-           "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
-           "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+    out = st.result()
     if dts is not None:
         out["tr_skip"] = dts.to_numpy(np.uint8, cus.shape)
     return out
@@ -925,55 +950,29 @@ def intra_recon_frames(pictures):
     return _chain_frames(True, pictures)
 
 
-class _ChainPicture:
+class _ChainPicture(_StagedPicture):
     """the arrays of one picture of a multi-picture call on the device, and its record"""
 
     def __init__(self, intra, src, cus, qp, pred=None, rec=None, modes=None, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None,
                  costs=None, lcu_qp=None):
-        pred = rec if intra else pred
-        chroma = int(chroma)
-        height, width = src[0].shape
-        self.cus = np.ascontiguousarray(cus)
-        assert self.cus.dtype.itemsize == 20 and self.cus.shape == (height // 4, width // 4)
-        n = self.n = 3 if chroma else 1
-        s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
-        self.r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
-        self.ds, self.dr = [DeviceBuffer.from_numpy(p) for p in s], [DeviceBuffer.from_numpy(p) for p in self.r]
-        shapes = coeff_shapes(width, height)
-        self.co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
-                   else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
-        self.dco = [DeviceBuffer.from_numpy(c) for c in self.co]
-        self.cb = np.zeros(self.cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(self.cus.shape)
-        self.cs = (np.zeros(self.cus.shape, INTER_RESIDUAL_COST) if costs is None
-                   else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(self.cus.shape))
-        self.dcb, self.dcs = DeviceBuffer.from_numpy(self.cb), DeviceBuffer.from_numpy(self.cs.view(np.uint8))
-        self.dcu = DeviceBuffer.from_numpy(self.cus.view(np.uint8))
+        assert modes is not None or not intra
+        super().__init__(modes if intra else None, src, rec if intra else pred, cus, chroma, coeff, cbf_out, costs)
+        chroma = self.chroma
         rec = _lib.ChainPicture()
-        rec.src = _lib.RefPicture(self.ds[0].ptr, self.ds[1].ptr if chroma else None, self.ds[2].ptr if chroma else None, s[0].shape[1],
-                                  s[1].shape[1] if chroma else 0, width, height)
+        rec.src = _lib.RefPicture(self.ds[0].ptr, self.ds[1].ptr if chroma else None, self.ds[2].ptr if chroma else None, self.s[0].shape[1],
+                                  self.s[1].shape[1] if chroma else 0, self.width, self.height)
         rec.rec_y, rec.stride_y = self.dr[0].ptr, self.r[0].shape[1]
         if chroma:
             rec.rec_u, rec.rec_v, rec.stride_c = self.dr[1].ptr, self.dr[2].ptr, self.r[1].shape[1]
             rec.coeff_u, rec.coeff_v = self.dco[1].ptr, self.dco[2].ptr
         rec.cus, rec.coeff_y, rec.cbf_out, rec.costs = self.dcu.ptr, self.dco[0].ptr, self.dcb.ptr, self.dcs.ptr
         if intra:
-            m = np.ascontiguousarray(modes, dtype=np.uint8)
-            assert m.shape == self.cus.shape + (2,)
-            self.dm = DeviceBuffer.from_numpy(m)
             rec.intra_modes = self.dm.ptr
         if lcu_qp is not None:
-            self.dq = DeviceBuffer.from_numpy(np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(lcu_count(width, height)))
+            self.dq = DeviceBuffer.from_numpy(np.ascontiguousarray(lcu_qp, dtype=np.int8).reshape(lcu_count(self.width, self.height)))
             rec.lcu_qp = self.dq.ptr
         rec.params = _lib.InterResidualParams(int(qp), int(slice_is_intra), int(signhide), 0, chroma, 0)
         self.record = rec
-
-    def result(self):
-        pad = (None,) * (3 - self.n)
-        return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(self.dr, self.r)) + pad,
-                "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(self.dco, self.co)) + pad,
-                "cus": self.dcu.to_numpy(np.uint8, self.cus.shape + (20,)).view(self.cus.dtype).reshape(self.cus.shape),
-                "cbf_out": self.dcb.to_numpy(np.uint8, self.cb.shape),
-                "costs": self.dcs.to_numpy(np.uint8, self.cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(self.cs.shape)}
 
 
 def _chain_frames(intra, pictures):
@@ -1067,40 +1066,17 @@ def intra_recon_frame_lossless(src, rec, cus, modes, chroma=1, implicit_rdpcm=0,
 def _lossless_frame(modes, src, pred, cus, chroma, implicit_rdpcm, tiles, coeff, cbf_out, costs):
     """the staging of the two lossless entries; modes None: the inter stage"""
     L = _lib.init()
-    chroma = int(chroma)
-    height, width = src[0].shape
-    cus = np.ascontiguousarray(cus)
-    assert cus.dtype.itemsize == 20 and cus.shape == (height // 4, width // 4)
-    n = 3 if chroma else 1
-    s = [np.ascontiguousarray(p, dtype=np.uint8) for p in src[:n]]
-    r = [np.ascontiguousarray(p, dtype=np.uint8) for p in pred[:n]]
-    ds, dr = [DeviceBuffer.from_numpy(p) for p in s], [DeviceBuffer.from_numpy(p) for p in r]
-    table = ref_picture_table([(ds[0].ptr, ds[1].ptr if chroma else 0, ds[2].ptr if chroma else 0, s[0].shape[1],
-                                s[1].shape[1] if chroma else 0)], width, height)
-    shapes = coeff_shapes(width, height)
-    co = [np.ascontiguousarray(coeff[k], dtype=np.int16).reshape(shapes[1 if k else 0]) if coeff is not None
-          else np.zeros(shapes[1 if k else 0], np.int16) for k in range(n)]
-    dco = [DeviceBuffer.from_numpy(c) for c in co]
-    cb = np.zeros(cus.shape, np.uint8) if cbf_out is None else np.ascontiguousarray(cbf_out, dtype=np.uint8).reshape(cus.shape)
-    cs = np.zeros(cus.shape, INTER_RESIDUAL_COST) if costs is None else np.ascontiguousarray(costs, dtype=INTER_RESIDUAL_COST).reshape(cus.shape)
-    dcb, dcs, dcu = DeviceBuffer.from_numpy(cb), DeviceBuffer.from_numpy(cs.view(np.uint8)), DeviceBuffer.from_numpy(cus.view(np.uint8))
-    ll = _lib.Lossless(chroma, int(implicit_rdpcm), (0, 0))
-    planes = (table.ctypes.data, dr[0].ptr, r[0].shape[1], dr[1].ptr if chroma else None, dr[2].ptr if chroma else None,
-              r[1].shape[1] if chroma else 0, dcu.ptr)
-    outs = (dco[0].ptr, dco[1].ptr if chroma else None, dco[2].ptr if chroma else None, dcb.ptr, dcs.ptr)
+    st = _StagedPicture(modes, src, pred, cus, chroma, coeff, cbf_out, costs)
+    ll = _lib.Lossless(st.chroma, int(implicit_rdpcm), (0, 0))
+    planes, outs = st.loose()
     if modes is None:
         check(L.kvz_hip_inter_residual_frame_lossless(*planes, *outs, C.byref(ll), None), "inter_residual frame_lossless")
     else:
-        dm = DeviceBuffer.from_numpy(modes)
+        dm = st.dm
         g = _grid(tiles) if tiles is not None else None
         check(L.kvz_hip_intra_recon_frame_lossless(*planes, dm.ptr, *outs, g.ctypes.data if g is not None else None, C.byref(ll), None),
               "intra_recon frame_lossless")
-    pad = (None,) * (3 - n)
-    return {"rec": tuple(b.to_numpy(np.uint8, p.shape) for b, p in zip(dr, r)) + pad,
-            "coeff": tuple(b.to_numpy(np.int16, c.shape) for b, c in zip(dco, co)) + pad,
-            "cus": dcu.to_numpy(np.uint8, cus.shape + (20,)).view(cus.dtype).reshape(cus.shape),
-            "cbf_out": dcb.to_numpy(np.uint8, cb.shape),
-            "costs": dcs.to_numpy(np.uint8, cs.shape + (24,)).view(INTER_RESIDUAL_COST).reshape(cs.shape)}
+    return st.result()
 
 
 # ---- the QP map of a picture whose QP changes per LCU ----

@@ -11,23 +11,9 @@
 
 static_assert(sizeof(kvz_hip_filter_picture) == 264, "layout documented in kvz_hip.h");
 
-namespace {
-
-int refuse(const char *entry, int i, const char *why)
-{
-  char msg[200];
-  snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (%s)", entry, i, why);
-  kvzhip::set_error_msg(msg);
-  return KVZ_HIP_ERR_INVALID;
-}
-
-}  // namespace
-
 extern "C" int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s)
 {
-  KVZ_CHECK_CTX();
-  if (n_pictures == 0) return KVZ_HIP_OK;
-  if (!pictures || n_pictures < 0 || n_pictures > KVZ_HIP_MAX_CHAIN_PICTURES) return kvzhip::invalid_arg(__func__);
+  KVZ_CHAIN_PROLOGUE(pictures, n_pictures);
   deblock_batch b;
   __builtin_memset(&b, 0, sizeof b);
   uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
@@ -36,17 +22,17 @@ extern "C" int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, in
   // every record is checked before anything is launched: a refused call writes nothing
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_filter_picture &p = pictures[i];
-    if (p.deblock.chroma != p.chroma) return refuse(__func__, i, "deblock.chroma differs from chroma");
+    if (p.deblock.chroma != p.chroma) return refuse_picture(__func__, i, "deblock.chroma differs from chroma");
     if (p.width > 16384 || p.height > 16384 ||
         !deblock_args_ok(__func__, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, p.width, p.height, p.cus, &p.deblock))
-      return refuse(__func__, i, "planes and the SCU map must be 4-byte aligned, width / height multiples of 8 in 8..16384, strides >= the width");
+      return refuse_picture(__func__, i, "planes and the SCU map must be 4-byte aligned, width / height multiples of 8 in 8..16384, strides >= the width");
     kvz_hip_tile_grid g;
-    if (!tile_grid_make(p.grid, p.width, p.height, &g)) return refuse(__func__, i, "invalid tile grid");
+    if (!tile_grid_make(p.grid, p.width, p.height, &g)) return refuse_picture(__func__, i, "invalid tile grid");
     deblock_pic &r = b.p[i];
     if (!tile_pool_add(p.grid, g, bounds, used, &r.tiles))
-      return refuse(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
+      return refuse_picture(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
     for (int j = 0; j < i; ++j)
-      if (p.rec_y == pictures[j].rec_y) return refuse(__func__, i, "an output shared with another picture");
+      if (p.rec_y == pictures[j].rec_y) return refuse_picture(__func__, i, "an output shared with another picture");
     r.cus = (const u32 *)p.cus;
     r.rec_y = p.rec_y; r.rec_u = p.chroma ? p.rec_u : nullptr; r.rec_v = p.chroma ? p.rec_v : nullptr;
     r.stride_y = p.stride_y; r.stride_c = p.stride_c;
@@ -55,7 +41,7 @@ extern "C" int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, in
     const size_t t = (size_t)(p.width >> 3) * (size_t)(p.height >> 3) * 2;
     threads = t > threads ? t : threads;
   }
-  tile_pool_pack(bounds, used, &b.pool);
+  tile_pool_pack(bounds, used, b.pool.bd);
   hipStream_t st = ctx_stream(s);
   // the launch sequence depends on the sizes alone: grid (blocks of the largest picture, pictures)
   const dim3 grid((unsigned)((threads + 255) / 256), (unsigned)n_pictures);

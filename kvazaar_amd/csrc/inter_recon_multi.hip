@@ -11,6 +11,7 @@
 // predict_tile of inter_recon_core.h, the single kernel's body.  No barrier, no atomics.  The kernels of inter_recon.hip are not
 // touched: this kernel has the translation unit to itself.
 #include "inter_recon_core.h"
+#include "chain_host.h"
 
 static_assert(sizeof(kvz_hip_recon_picture) == 104 && KVZ_HIP_RECON_POOL_PICTURES == 48, "layout documented in kvz_hip.h");
 
@@ -59,13 +60,6 @@ __global__ __launch_bounds__(256) void inter_recon_frames_kernel(multi_args k)
   predict_tile(lane, lds[wv], a, p.cus, p.width >> 2, p.pool_of, tx0, ty0);
 }
 
-int refuse(const char *entry, int i, const char *why)
-{
-  char msg[200];
-  snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (%s)", entry, i, why);
-  kvzhip::set_error_msg(msg);
-  return KVZ_HIP_ERR_INVALID;
-}
 
 }  // namespace
 
@@ -74,10 +68,8 @@ extern "C" {
 int kvz_hip_inter_recon_frames(const kvz_hip_recon_picture *pictures, int n_pictures, const kvz_hip_ref_picture *pool, int n_pool,
                                kvz_hip_stream s)
 {
-  KVZ_CHECK_CTX();
-  if (n_pictures == 0) return KVZ_HIP_OK;
-  if (!pictures || n_pictures < 0 || n_pictures > KVZ_HIP_MAX_CHAIN_PICTURES || !pool || n_pool < 1 || n_pool > KVZ_HIP_RECON_POOL_PICTURES)
-    return kvzhip::invalid_arg(__func__);
+  KVZ_CHAIN_PROLOGUE(pictures, n_pictures);
+  if (!pool || n_pool < 1 || n_pool > KVZ_HIP_RECON_POOL_PICTURES) return kvzhip::invalid_arg(__func__);
   multi_args k;
   __builtin_memset(&k, 0, sizeof k);
   k.n_pictures = n_pictures;
@@ -88,20 +80,20 @@ int kvz_hip_inter_recon_frames(const kvz_hip_recon_picture *pictures, int n_pict
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_recon_picture &p = pictures[i];
     const int width = p.width, height = p.height, chroma = p.params.chroma, n_refs = p.params.n_refs;
-    if (!p.pred_y || !p.cus || ((uintptr_t)p.cus & 3)) return refuse(__func__, i, "pred_y or cus is null, or cus misaligned");
+    if (!p.pred_y || !p.cus || ((uintptr_t)p.cus & 3)) return refuse_picture(__func__, i, "pred_y or cus is null, or cus misaligned");
     if (width < 8 || height < 8 || ((width | height) & 7) || p.stride_y < (uint32_t)width)
-      return refuse(__func__, i, "width / height must be multiples of 8, stride_y >= the width");
-    if (n_refs < 1 || n_refs > KVZ_HIP_MAX_REF_PICTURES) return refuse(__func__, i, "n_refs outside 1..16");
+      return refuse_picture(__func__, i, "width / height must be multiples of 8, stride_y >= the width");
+    if (n_refs < 1 || n_refs > KVZ_HIP_MAX_REF_PICTURES) return refuse_picture(__func__, i, "n_refs outside 1..16");
     if (chroma && (!p.pred_u || !p.pred_v || p.stride_c < (uint32_t)(width >> 1)))
-      return refuse(__func__, i, "a chroma plane is null, or stride_c below half the width");
+      return refuse_picture(__func__, i, "a chroma plane is null, or stride_c below half the width");
     for (int r = 0; r < n_refs; ++r) {
-      if (p.refs[r] >= n_pool) return refuse(__func__, i, "a reference index outside the pool");
+      if (p.refs[r] >= n_pool) return refuse_picture(__func__, i, "a reference index outside the pool");
       if (!ref_ok(pool[p.refs[r]], chroma, width, height))
-        return refuse(__func__, i, "a named pool picture of another size, with a missing plane or a short stride");
+        return refuse_picture(__func__, i, "a named pool picture of another size, with a missing plane or a short stride");
       named[p.refs[r]] = true;
     }
     for (int j = 0; j < i; ++j)
-      if (p.pred_y == pictures[j].pred_y) return refuse(__func__, i, "pred_y shared with another picture");
+      if (p.pred_y == pictures[j].pred_y) return refuse_picture(__func__, i, "pred_y shared with another picture");
     multi_pic &a = k.p[i];
     a.y = p.pred_y; a.u = chroma ? p.pred_u : nullptr; a.v = chroma ? p.pred_v : nullptr;
     a.cus = (const u32 *)p.cus;
@@ -112,14 +104,14 @@ int kvz_hip_inter_recon_frames(const kvz_hip_recon_picture *pictures, int n_pict
     for (int l = 0; l < 2; ++l)
       for (int r = 0; r < 16; ++r) a.pool_of[l][r] = p.params.ref_LX[l][r] < n_refs ? p.refs[p.params.ref_LX[l][r]] : 255;
     groups += ((unsigned long long)((width + 15) >> 4) * (unsigned long long)((height + 15) >> 4) + 3) / 4;
-    if (groups > 0x7fffffffull) return refuse(__func__, i, "the pictures of the call exceed the grid");
+    if (groups > 0x7fffffffull) return refuse_picture(__func__, i, "the pictures of the call exceed the grid");
   }
   // no destination may be a plane of a pool picture that some record names
   for (int i = 0; i < n_pictures; ++i)
     for (int r = 0; r < n_pool; ++r) {
       if (!named[r]) continue;
       const kvz_hip_ref_picture &q = pool[r];
-      if (k.p[i].y == q.y || (k.p[i].u && (k.p[i].u == q.u || k.p[i].v == q.v))) return refuse(__func__, i, "a destination plane is a named pool plane");
+      if (k.p[i].y == q.y || (k.p[i].u && (k.p[i].u == q.u || k.p[i].v == q.v))) return refuse_picture(__func__, i, "a destination plane is a named pool plane");
     }
   for (int r = 0; r < n_pool; ++r)
     if (named[r]) k.pool[r] = pool[r];

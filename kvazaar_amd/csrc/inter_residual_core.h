@@ -8,6 +8,7 @@
 #include "transform_core.h"
 #include "quant_core.h"
 #include "lcu_layout.h"
+#include "chain_host.h"
 
 using namespace kvzhip;
 
@@ -46,6 +47,19 @@ struct resid_pic {
   u8 chroma, slice_is_intra, signhide, pad;
 };
 struct resid_batch { resid_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; };
+// a checked record into the kernel's; qp: the picture's QP as the kernel is to see it (as it stands, or clamped: the entries differ)
+inline void fill(resid_pic &a, const kvz_hip_chain_picture &p, int qp)
+{
+  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+  a.src_y = p.src.y; a.src_u = chroma ? p.src.u : nullptr; a.src_v = chroma ? p.src.v : nullptr;
+  a.rec_y = p.rec_y; a.rec_u = chroma ? p.rec_u : nullptr; a.rec_v = chroma ? p.rec_v : nullptr;
+  a.src_stride_y = p.src.stride_y; a.src_stride_c = p.src.stride_c; a.rec_stride_y = p.stride_y; a.rec_stride_c = p.stride_c;
+  a.coeff_y = p.coeff_y; a.coeff_u = chroma ? p.coeff_u : nullptr; a.coeff_v = chroma ? p.coeff_v : nullptr;
+  a.cus = (u32 *)p.cus; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs; a.lcu_qp = p.lcu_qp;
+  a.qp = qp;
+  a.width = (uint16_t)width; a.height = (uint16_t)height; a.cus_stride = (uint16_t)(width >> 2); a.lcus_x = (uint16_t)((width + 63) >> 6);
+  a.chroma = (u8)chroma; a.slice_is_intra = p.params.slice_is_intra ? 1 : 0; a.signhide = p.params.signhide ? 1 : 0;
+}
 static_assert(sizeof(resid_pic) == 136 && sizeof(resid_batch) <= 3072, "the records travel in the kernel arguments");
 // The kernel works on a COPY of its picture's block, which the compiler takes apart into the loads of the fields that are used: for
 // resid_args that is the kernel as it was compiled with the argument itself, instruction for instruction, which a reference to the
@@ -445,15 +459,34 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
   }
 }
 
+// the slots of a launch of size N over one picture (the kernel's comment above), and the workgroups that hold them
+struct resid_slots { int nx_y, n_y, nx_c, n_c, groups; };
+template <int N>
+resid_slots residual_slots(int width, int height, int chroma)
+{
+  resid_slots s;
+  s.nx_y = (width + N - 1) / N; s.n_y = s.nx_y * ((height + N - 1) / N);
+  s.nx_c = ((width >> 1) + N - 1) / N; s.n_c = (chroma && N < 32) ? s.nx_c * (((height >> 1) + N - 1) / N) : 0;
+  constexpr int TPB = 256 / N;
+  s.groups = (s.n_y + 2 * s.n_c + TPB - 1) / TPB;
+  return s;
+}
+
 template <int N, typename... PER_LCU>
 void launch_size(const resid_args &a, const quant_consts &ky, const quant_consts &kc, int chroma, hipStream_t st, PER_LCU... q)
 {
-  const int nx_y = (a.width + N - 1) / N, n_y = nx_y * ((a.height + N - 1) / N);
-  const int cw = a.width >> 1, chh = a.height >> 1;
-  const int nx_c = (cw + N - 1) / N, n_c = (chroma && N < 32) ? nx_c * ((chh + N - 1) / N) : 0;
-  constexpr int TPB = 256 / N;
-  const int slots = n_y + 2 * n_c;
-  hipLaunchKernelGGL((inter_residual_tu_kernel<N, resid_args, PER_LCU...>), dim3((unsigned)((slots + TPB - 1) / TPB)), dim3(256), 0, st, a, ky, kc, nx_y, n_y, nx_c, n_c, q...);
+  const resid_slots n = residual_slots<N>(a.width, a.height, chroma);
+  hipLaunchKernelGGL((inter_residual_tu_kernel<N, resid_args, PER_LCU...>), dim3((unsigned)n.groups), dim3(256), 0, st, a, ky, kc, n.nx_y, n.n_y, n.nx_c, n.n_c, q...);
+}
+
+// several pictures (BATCH: resid_batch or a resid_batch_ts): workgroups of the launch of size N for the picture with the most slots
+template <int N, typename BATCH>
+void launch_pictures(const BATCH &b, int n_pictures, hipStream_t st)
+{
+  int groups = 0;
+  for (int i = 0; i < n_pictures; ++i) groups = max(groups, residual_slots<N>(b.p[i].width, b.p[i].height, b.p[i].chroma).groups);
+  const quant_consts none = {};                                               // not read: every TU derives its own
+  hipLaunchKernelGGL((inter_residual_tu_kernel<N, BATCH>), dim3((unsigned)groups, (unsigned)n_pictures), dim3(256), 0, st, b, none, none, 0, 0, 0, 0);
 }
 
 template <typename... PER_LCU>
@@ -468,24 +501,6 @@ void launch_width(int n, const resid_args &a, const quant_consts &ky, const quan
 // the three entries: lcu_qp == nullptr is one QP per call (params->qp).  SL: the entry with scaling lists, tables required and checked;
 // it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only.  TS: the 4x4 launch
 // takes *skip (checked by the caller); the launches of the other sizes are those of the entry without it
-// what every entry requires of one picture's arguments, the QP and the tables aside; lists: the entry takes scaling lists
-inline bool residual_frame_args_ok(const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
-                                   const kvz_hip_pixel *rec_v, uint32_t stride_c, const kvz_hip_cu_info *cus, const kvz_hip_coeff *coeff_y,
-                                   const kvz_hip_coeff *coeff_u, const kvz_hip_coeff *coeff_v, const kvz_hip_inter_residual_cost *costs,
-                                   const kvz_hip_inter_residual_params *params, bool lists)
-{
-  if (!src || !params || !rec_y || !cus || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
-    return false;
-  const int width = src->width, height = src->height;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      (params->scaling_list != 0) != lists)
-    return false;
-  if (params->chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
-                         src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
-    return false;
-  return true;
-}
-
 template <bool SL, bool TS = false>
 int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                    kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
@@ -493,7 +508,7 @@ int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pi
                    const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s,
                    const ts_source *skip = nullptr)
 {
-  if (!residual_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, costs, params, SL))
+  if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, costs, params, false, SL))
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
   if (SL && (!tables || !tables->quant || !tables->dequant || (((uintptr_t)tables->quant | (uintptr_t)tables->dequant) & 15)))

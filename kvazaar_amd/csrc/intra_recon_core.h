@@ -53,6 +53,20 @@ struct intra_pic {
   u8 chroma, slice_is_intra, signhide, pad;
 };
 struct intra_batch { intra_pic p[KVZ_HIP_MAX_CHAIN_PICTURES]; };
+// a checked record into the kernel's; qp: the picture's QP as the kernel is to see it (as it stands, or clamped: the entries differ)
+inline void fill(intra_pic &a, const kvz_hip_chain_picture &p, int qp)
+{
+  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+  a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
+  a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
+  a.src_stride[0] = p.src.stride_y; a.src_stride[1] = a.src_stride[2] = p.src.stride_c;
+  a.rec_stride[0] = p.stride_y; a.rec_stride[1] = a.rec_stride[2] = p.stride_c;
+  a.coeff[0] = p.coeff_y; a.coeff[1] = chroma ? p.coeff_u : nullptr; a.coeff[2] = chroma ? p.coeff_v : nullptr;
+  a.cus = (u32 *)p.cus; a.modes = p.intra_modes; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs; a.lcu_qp = p.lcu_qp;
+  a.qp = qp;
+  a.width = (uint16_t)width; a.height = (uint16_t)height; a.cus_stride = (uint16_t)(width >> 2); a.lcus_x = (uint16_t)((width + 63) >> 6);
+  a.chroma = (u8)chroma; a.slice_is_intra = p.params.slice_is_intra ? 1 : 0; a.signhide = p.params.signhide ? 1 : 0;
+}
 static_assert(sizeof(intra_pic) == 152 && sizeof(intra_batch) <= 3072, "the records travel in the kernel arguments");
 template <typename ARGS> struct picture_type { using type = ARGS; };
 template <> struct picture_type<intra_batch> { using type = intra_pic; };
@@ -663,25 +677,6 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
   }
 }
 
-// what every entry requires of one picture's arguments, the QP aside; lists: the entry takes scaling lists
-inline bool intra_frame_args_ok(const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
-                                const kvz_hip_pixel *rec_v, uint32_t stride_c, const kvz_hip_cu_info *cus, const uint8_t *intra_modes,
-                                const kvz_hip_coeff *coeff_y, const kvz_hip_coeff *coeff_u, const kvz_hip_coeff *coeff_v,
-                                const kvz_hip_inter_residual_cost *costs, const kvz_hip_inter_residual_params *params, bool lists)
-{
-  if (!src || !params || !rec_y || !cus || !intra_modes || !coeff_y || !src->y || ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) ||
-      ((uintptr_t)costs & 3))
-    return false;
-  const int width = src->width, height = src->height;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width ||
-      (params->scaling_list != 0) != lists)
-    return false;
-  if (params->chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
-                         src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
-    return false;
-  return true;
-}
-
 // the four entries; per_lcu: nothing (one QP per call, params->qp), one lcu_qp_source, that and a tile_source, or those and an
 // sl_source (the only one that takes, and requires, params->scaling_list != 0)
 template <typename... PER_LCU>
@@ -690,7 +685,7 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
                 kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                 const kvz_hip_inter_residual_params *params, kvz_hip_stream s, PER_LCU... per_lcu)
 {
-  if (!intra_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, costs, params,
+  if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, costs, params, true,
                            pack_has<sl_source, PER_LCU...>))
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;

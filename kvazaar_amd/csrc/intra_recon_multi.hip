@@ -29,55 +29,27 @@ __global__ __launch_bounds__(256) void intra_recon_init_multi_kernel(intra_batch
   }
 }
 
-int refuse(const char *entry, int i)
-{
-  char msg[160];
-  snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (null or misaligned buffer, size or parameter out of range, or an output shared with "
-           "another picture)", entry, i);
-  kvzhip::set_error_msg(msg);
-  return KVZ_HIP_ERR_INVALID;
-}
-
 }  // namespace
 
 extern "C" {
 
 int kvz_hip_intra_recon_frames(const kvz_hip_chain_picture *pictures, int n_pictures, kvz_hip_stream s)
 {
-  KVZ_CHECK_CTX();
-  if (n_pictures == 0) return KVZ_HIP_OK;
-  if (!pictures || n_pictures < 0 || n_pictures > KVZ_HIP_MAX_CHAIN_PICTURES) return kvzhip::invalid_arg(__func__);
+  KVZ_CHAIN_PROLOGUE(pictures, n_pictures);
   intra_batch b;
   __builtin_memset(&b, 0, sizeof b);
   int waves = 0, groups = 0, planes = 1, init_scus = 0;
   // every record is checked before anything is launched: a refused call writes nothing
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_chain_picture &p = pictures[i];
-    if (!intra_frame_args_ok(&p.src, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, p.cus, p.intra_modes, p.coeff_y, p.coeff_u, p.coeff_v, p.costs,
-                             &p.params, false))
-      return refuse(__func__, i);
-    // one QP for the picture: what the one-QP entry refuses
-    const kvz_hip_quant_params qp = { p.params.qp, p.params.slice_is_intra, p.params.signhide, 0, nullptr, nullptr };
-    quant_consts k;
-    if (!p.lcu_qp && (!make_consts(&qp, 4, 0, 0, &k) || !make_consts(&qp, 4, 2, 2, &k))) return refuse(__func__, i);
-    for (int j = 0; j < i; ++j)
-      if (p.rec_y == pictures[j].rec_y || p.cus == pictures[j].cus || p.coeff_y == pictures[j].coeff_y) return refuse(__func__, i);
-    const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+    if (const char *why = chain_record_why(pictures, i, true)) return refuse_picture(__func__, i, why);
     intra_pic &a = b.p[i];
-    a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
-    a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
-    a.src_stride[0] = p.src.stride_y; a.src_stride[1] = a.src_stride[2] = p.src.stride_c;
-    a.rec_stride[0] = p.stride_y; a.rec_stride[1] = a.rec_stride[2] = p.stride_c;
-    a.coeff[0] = p.coeff_y; a.coeff[1] = chroma ? p.coeff_u : nullptr; a.coeff[2] = chroma ? p.coeff_v : nullptr;
-    a.cus = (u32 *)p.cus; a.modes = p.intra_modes; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs; a.lcu_qp = p.lcu_qp;
-    a.qp = p.params.qp;
-    a.width = (uint16_t)width; a.height = (uint16_t)height; a.cus_stride = (uint16_t)(width >> 2); a.lcus_x = (uint16_t)((width + 63) >> 6);
-    a.chroma = (u8)chroma; a.slice_is_intra = p.params.slice_is_intra ? 1 : 0; a.signhide = p.params.signhide ? 1 : 0;
-    const int lcus_y = (height + 63) >> 6;
+    fill(a, p, p.params.qp);
+    const int lcus_y = (a.height + 63) >> 6;
     waves = max(waves, a.lcus_x + 2 * (lcus_y - 1));
     groups = max(groups, lcus_y);
-    if (chroma) planes = 3;
-    if (p.cbf_out || p.costs) init_scus = max(init_scus, (width >> 2) * (height >> 2));
+    if (a.chroma) planes = 3;
+    if (p.cbf_out || p.costs) init_scus = max(init_scus, (a.width >> 2) * (a.height >> 2));
   }
   hipStream_t st = ctx_stream(s);
   // the launch sequence depends on the sizes, the chroma flags and the presence of cbf_out / costs alone

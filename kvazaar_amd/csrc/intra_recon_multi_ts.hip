@@ -33,14 +33,6 @@ __global__ __launch_bounds__(256) void intra_recon_init_multi_ts_kernel(intra_ba
   }
 }
 
-int refuse(const char *entry, int i, const char *why)
-{
-  char msg[200];
-  snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (%s)", entry, i, why);
-  kvzhip::set_error_msg(msg);
-  return KVZ_HIP_ERR_INVALID;
-}
-
 template <bool SL, bool TS>
 int launch_waves(const intra_batch_ts_data &d, int waves, dim3 grid, hipStream_t st)
 {
@@ -59,9 +51,7 @@ extern "C" {
 
 int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s)
 {
-  KVZ_CHECK_CTX();
-  if (n_pictures == 0) return KVZ_HIP_OK;
-  if (!pictures || n_pictures < 0 || n_pictures > KVZ_HIP_MAX_CHAIN_PICTURES) return kvzhip::invalid_arg(__func__);
+  KVZ_CHAIN_PROLOGUE(pictures, n_pictures);
   bool options = false;
   for (int i = 0; i < n_pictures; ++i)
     options = options || pictures[i].grid || pictures[i].tables.quant || pictures[i].tables.dequant || pictures[i].ts;
@@ -80,55 +70,27 @@ int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int 
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_chain_picture_ts &r = pictures[i];
     const kvz_hip_chain_picture &p = r.pic;
-    const bool has_lists = r.tables.quant || r.tables.dequant;
-    if (has_lists != lists || (r.ts != nullptr) != skip)
-      return refuse(__func__, i, "a call is homogeneous: every record carries tables or none does, every record carries ts or none does");
-    if (has_lists && (!r.tables.quant || !r.tables.dequant || (((uintptr_t)r.tables.quant | (uintptr_t)r.tables.dequant) & 15)))
-      return refuse(__func__, i, "a table is null or not 16-byte aligned");
-    if (!intra_frame_args_ok(&p.src, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, p.cus, p.intra_modes, p.coeff_y, p.coeff_u, p.coeff_v, p.costs,
-                             &p.params, has_lists))
-      return refuse(__func__, i, "null or misaligned buffer, size or parameter out of range, or scaling_list does not say whether tables are given");
-    if (r.ts && (!r.tr_skip_out || (!r.ts->lcu_bit_cost && r.ts->bit_cost < 0) || ((uintptr_t)r.ts->lcu_bit_cost & 3)))
-      return refuse(__func__, i, "ts without tr_skip_out, a negative bit_cost without lcu_bit_cost, or a misaligned lcu_bit_cost");
-    // one QP for the picture: what the one-QP entry refuses
-    if (!p.lcu_qp && p.params.qp < 0) return refuse(__func__, i, "a negative qp without lcu_qp");
+    // the record's own checks, its grid and the grid's place in the pool, then the outputs of the earlier records: the order decides
+    // which reason a record with two defects reports
+    const char *why = chain_record_ts_why(pictures, i, true, lists, skip);
     kvz_hip_tile_grid g;
-    if (!tile_grid_make(r.grid, p.src.width, p.src.height, &g)) return refuse(__func__, i, "invalid tile grid");
-    if (r.grid && used + g.cols + g.rows + 2 > KVZ_HIP_CHAIN_TILE_BOUNDS)
-      return refuse(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
-    for (int j = 0; j < i; ++j) {
-      const kvz_hip_chain_picture &o = pictures[j].pic;
-      if (p.rec_y == o.rec_y || p.cus == o.cus || p.coeff_y == o.coeff_y || (r.ts && r.tr_skip_out == pictures[j].tr_skip_out))
-        return refuse(__func__, i, "an output shared with another picture");
-    }
-    const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+    pic_tiles t;
+    if (!why && !tile_grid_make(r.grid, p.src.width, p.src.height, &g)) why = "invalid tile grid";
+    if (!why && !tile_pool_add(r.grid, g, bounds, used, &t)) why = "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record";
+    if (!why) why = chain_record_ts_shared(pictures, i);
+    if (why) return refuse_picture(__func__, i, why);
     intra_pic_ts &a = b.p[i];
-    a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
-    a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
-    a.src_stride[0] = p.src.stride_y; a.src_stride[1] = a.src_stride[2] = p.src.stride_c;
-    a.rec_stride[0] = p.stride_y; a.rec_stride[1] = a.rec_stride[2] = p.stride_c;
-    a.coeff[0] = p.coeff_y; a.coeff[1] = chroma ? p.coeff_u : nullptr; a.coeff[2] = chroma ? p.coeff_v : nullptr;
-    a.cus = (u32 *)p.cus; a.modes = p.intra_modes; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs; a.lcu_qp = p.lcu_qp;
-    a.qp = clip_lcu_qp(p.params.qp);                                          // the single-picture tiled kernels clamp the picture's QP too
-    a.width = (uint16_t)width; a.height = (uint16_t)height; a.cus_stride = (uint16_t)(width >> 2); a.lcus_x = (uint16_t)((width + 63) >> 6);
-    a.chroma = (u8)chroma; a.slice_is_intra = p.params.slice_is_intra ? 1 : 0; a.signhide = p.params.signhide ? 1 : 0;
-    if (has_lists) { a.quant = r.tables.quant; a.dequant = r.tables.dequant; }
+    fill(a, p, clip_lcu_qp(p.params.qp));                                     // the single-picture tiled kernels clamp the picture's QP too
+    if (lists) { a.quant = r.tables.quant; a.dequant = r.tables.dequant; }
     if (r.ts) { a.lcu_bit_cost = r.ts->lcu_bit_cost; a.tr_skip_out = r.tr_skip_out; a.bit_cost = r.ts->bit_cost; }
-    if (r.grid) {
-      // the boundaries the call uses, 16 bits each (an LCU index is at most 256): cols + 1 of the columns, then rows + 1 of the rows
-      a.cols = (u8)g.cols; a.rows = (u8)g.rows;
-      a.col_at = (uint16_t)used;
-      for (int j = 0; j <= g.cols; ++j) bounds[used++] = (uint16_t)g.col_bd[j];
-      a.row_at = (uint16_t)used;
-      for (int j = 0; j <= g.rows; ++j) bounds[used++] = (uint16_t)g.row_bd[j];
-    }
-    const int lcus_y = (height + 63) >> 6;
+    // the kernel reads cols == 0 as "no grid": a picture without one keeps the zeros, where pic_tiles says one tile
+    if (r.grid) { a.cols = t.cols; a.rows = t.rows; a.col_at = t.col_at; a.row_at = t.row_at; }
     waves = max(waves, tile_grid_waves(g));
-    groups = max(groups, lcus_y * g.cols);
-    if (chroma) planes = 3;
-    if (p.cbf_out || p.costs) init_scus = max(init_scus, (width >> 2) * (height >> 2));
+    groups = max(groups, (int)t.lcus_y * g.cols);
+    if (a.chroma) planes = 3;
+    if (p.cbf_out || p.costs) init_scus = max(init_scus, (a.width >> 2) * (a.height >> 2));
   }
-  for (int j = 0; j < used; ++j) b.bd[j >> 1] |= (u32)bounds[j] << (16 * (j & 1));
+  tile_pool_pack(bounds, used, b.bd);
   hipStream_t st = ctx_stream(s);
   // the launch sequence depends on the sizes, the chroma flags, the grids and the presence of cbf_out / costs alone
   if (init_scus) {

@@ -310,15 +310,11 @@ int lossless_frame(const char *entry, bool intra, const kvz_hip_ref_picture *src
                    kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                    const kvz_hip_tile_grid *tiles, const kvz_hip_lossless *ll, kvz_hip_stream s)
 {
-  if (!ll || ll->reserved[0] || ll->reserved[1] || !src || !rec_y || !cus || (intra && !intra_modes) || !coeff_y || !src->y ||
-      ((uintptr_t)cus & 3) || ((uintptr_t)coeff_y & 15) || ((uintptr_t)costs & 3))
+  if (!ll || ll->reserved[0] || ll->reserved[1]) return kvzhip::invalid_arg(entry);
+  const kvz_hip_inter_residual_params flat = { 0, 0, 0, 0, ll->chroma, 0 };     // what the check of the arguments reads of them
+  if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, costs, &flat, intra, false))
     return kvzhip::invalid_arg(entry);
   const int width = src->width, height = src->height, chroma = ll->chroma ? 1 : 0;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || stride_y < (uint32_t)width || src->stride_y < (uint32_t)width)
-    return kvzhip::invalid_arg(entry);
-  if (chroma && (!rec_u || !rec_v || !coeff_u || !coeff_v || !src->u || !src->v || stride_c < (uint32_t)(width >> 1) ||
-                 src->stride_c < (uint32_t)(width >> 1) || (((uintptr_t)coeff_u | (uintptr_t)coeff_v) & 15)))
-    return kvzhip::invalid_arg(entry);
   kvz_hip_tile_grid grid;
   if (!tile_grid_make(intra ? tiles : nullptr, width, height, &grid)) return kvzhip::invalid_arg(entry);
   ll_args a;

@@ -12,25 +12,11 @@
 
 static_assert(sizeof(kvz_hip_filter_picture) == 264, "layout documented in kvz_hip.h");
 
-namespace {
-
-int refuse(const char *entry, int i, const char *why)
-{
-  char msg[200];
-  snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (%s)", entry, i, why);
-  kvzhip::set_error_msg(msg);
-  return KVZ_HIP_ERR_INVALID;
-}
-
-}  // namespace
-
 extern "C" {
 
 int kvz_hip_sao_stats_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s)
 {
-  KVZ_CHECK_CTX();
-  if (n_pictures == 0) return KVZ_HIP_OK;
-  if (!pictures || n_pictures < 0 || n_pictures > KVZ_HIP_MAX_CHAIN_PICTURES) return kvzhip::invalid_arg(__func__);
+  KVZ_CHAIN_PROLOGUE(pictures, n_pictures);
   stats_batch b;
   __builtin_memset(&b, 0, sizeof b);
   int groups = 0;
@@ -38,16 +24,16 @@ int kvz_hip_sao_stats_frames(const kvz_hip_filter_picture *pictures, int n_pictu
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_filter_picture &p = pictures[i];
     const int width = p.width, height = p.height, chroma = p.chroma ? 1 : 0;
-    if (p.deblock.chroma != p.chroma) return refuse(__func__, i, "deblock.chroma differs from chroma");
-    if (p.src.width != width || p.src.height != height) return refuse(__func__, i, "src.width / src.height differ from width / height");
-    if (!p.stats || ((uintptr_t)p.stats & 3) || ((uintptr_t)p.cands & 3)) return refuse(__func__, i, "stats is null, or stats or cands misaligned");
+    if (p.deblock.chroma != p.chroma) return refuse_picture(__func__, i, "deblock.chroma differs from chroma");
+    if (p.src.width != width || p.src.height != height) return refuse_picture(__func__, i, "src.width / src.height differ from width / height");
+    if (!p.stats || ((uintptr_t)p.stats & 3) || ((uintptr_t)p.cands & 3)) return refuse_picture(__func__, i, "stats is null, or stats or cands misaligned");
     if (!picture_ok(width, height) || !plane_ok(p.src.y, p.src.stride_y, width) || !plane_ok(p.rec_y, p.stride_y, width))
-      return refuse(__func__, i, "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8");
+      return refuse_picture(__func__, i, "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8");
     if (chroma && (!plane_ok(p.src.u, p.src.stride_c, width >> 1) || !plane_ok(p.src.v, p.src.stride_c, width >> 1) ||
                    !plane_ok(p.rec_u, p.stride_c, width >> 1) || !plane_ok(p.rec_v, p.stride_c, width >> 1)))
-      return refuse(__func__, i, "a chroma plane is null or misaligned, or its stride is");
+      return refuse_picture(__func__, i, "a chroma plane is null or misaligned, or its stride is");
     for (int j = 0; j < i; ++j)
-      if (p.stats == pictures[j].stats || (p.cands && p.cands == pictures[j].cands)) return refuse(__func__, i, "an output shared with another picture");
+      if (p.stats == pictures[j].stats || (p.cands && p.cands == pictures[j].cands)) return refuse_picture(__func__, i, "an output shared with another picture");
     stats_args &a = b.p[i];
     a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
     a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
@@ -68,9 +54,7 @@ int kvz_hip_sao_stats_frames(const kvz_hip_filter_picture *pictures, int n_pictu
 
 int kvz_hip_sao_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s)
 {
-  KVZ_CHECK_CTX();
-  if (n_pictures == 0) return KVZ_HIP_OK;
-  if (!pictures || n_pictures < 0 || n_pictures > KVZ_HIP_MAX_CHAIN_PICTURES) return kvzhip::invalid_arg(__func__);
+  KVZ_CHAIN_PROLOGUE(pictures, n_pictures);
   frame_batch b;
   __builtin_memset(&b, 0, sizeof b);
   uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
@@ -79,21 +63,21 @@ int kvz_hip_sao_frames(const kvz_hip_filter_picture *pictures, int n_pictures, k
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_filter_picture &p = pictures[i];
     const int width = p.width, height = p.height, chroma = p.chroma ? 1 : 0;
-    if (p.deblock.chroma != p.chroma) return refuse(__func__, i, "deblock.chroma differs from chroma");
-    if (!p.sao_luma || ((uintptr_t)p.sao_luma & 3) || p.dst_y == p.rec_y) return refuse(__func__, i, "sao_luma is null or misaligned, or dst_y is rec_y");
+    if (p.deblock.chroma != p.chroma) return refuse_picture(__func__, i, "deblock.chroma differs from chroma");
+    if (!p.sao_luma || ((uintptr_t)p.sao_luma & 3) || p.dst_y == p.rec_y) return refuse_picture(__func__, i, "sao_luma is null or misaligned, or dst_y is rec_y");
     if (!picture_ok(width, height) || !plane_ok(p.rec_y, p.stride_y, width) || !plane_ok(p.dst_y, p.dst_stride_y, width))
-      return refuse(__func__, i, "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8");
+      return refuse_picture(__func__, i, "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8");
     if (chroma && (!p.sao_chroma || ((uintptr_t)p.sao_chroma & 3) || p.dst_u == p.rec_u || p.dst_v == p.rec_v ||
                    !plane_ok(p.rec_u, p.stride_c, width >> 1) || !plane_ok(p.rec_v, p.stride_c, width >> 1) ||
                    !plane_ok(p.dst_u, p.dst_stride_c, width >> 1) || !plane_ok(p.dst_v, p.dst_stride_c, width >> 1)))
-      return refuse(__func__, i, "sao_chroma or a chroma plane is null or misaligned, a chroma stride is, or a dst plane is its rec plane");
+      return refuse_picture(__func__, i, "sao_chroma or a chroma plane is null or misaligned, a chroma stride is, or a dst plane is its rec plane");
     kvz_hip_tile_grid g;
-    if (!tile_grid_make(p.grid, width, height, &g)) return refuse(__func__, i, "invalid tile grid");
+    if (!tile_grid_make(p.grid, width, height, &g)) return refuse_picture(__func__, i, "invalid tile grid");
     frame_pic &r = b.p[i];
     if (!tile_pool_add(p.grid, g, bounds, used, &r.tiles))
-      return refuse(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
+      return refuse_picture(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
     for (int j = 0; j < i; ++j)
-      if (p.dst_y == pictures[j].dst_y) return refuse(__func__, i, "an output shared with another picture");
+      if (p.dst_y == pictures[j].dst_y) return refuse_picture(__func__, i, "an output shared with another picture");
     frame_args &a = r.a;
     a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
     a.dst[0] = p.dst_y; a.dst[1] = chroma ? p.dst_u : nullptr; a.dst[2] = chroma ? p.dst_v : nullptr;
@@ -106,7 +90,7 @@ int kvz_hip_sao_frames(const kvz_hip_filter_picture *pictures, int n_pictures, k
     a.sao[0] = p.sao_luma; a.sao[1] = chroma ? p.sao_chroma : nullptr;
     groups = max(groups, a.tiles_y + 2 * a.tiles_c);
   }
-  tile_pool_pack(bounds, used, &b.pool);
+  tile_pool_pack(bounds, used, b.pool.bd);
   // the launch depends on the sizes and the chroma flags alone: grid (tiles of the largest picture, pictures); the kernel's own
   // arguments are not read
   hipLaunchKernelGGL(sao_frame_kernel<frame_batch>, dim3((unsigned)groups, (unsigned)n_pictures), dim3(256), 0, ctx_stream(s), b.p[0].a, b);

@@ -1,6 +1,7 @@
-// tile_grid.h -- kvz_hip_tile_grid on the host and on the device, for the four *_tiles entries of the picture chain
-// (intra_recon_tiles.hip, cu_qp_tiles.hip, deblock_tiles.hip, sao_frame_tiles.hip).  At the end: the grids of the pictures of a multi-picture
-// call, which share one pool of boundaries (cu_qp_multi.hip, deblock_multi.hip, sao_frame_multi.hip).
+// tile_grid.h -- kvz_hip_tile_grid on the device, for the four *_tiles entries of the picture chain (intra_recon_tiles.hip,
+// cu_qp_tiles.hip, deblock_tiles.hip, sao_frame_tiles.hip); its host side (tile_grid_make, tile_grid_waves) is in chain_host.h.  At the
+// end: the grids of the pictures of a multi-picture call, which share one pool of boundaries (cu_qp_multi.hip, deblock_multi.hip,
+// sao_frame_multi.hip; filled on the host by tile_pool_add and tile_pool_pack, chain_host.h).
 //
 // The grid travels to every kernel by value (392 bytes of kernel arguments).  The lookups below index it with constants only --
 // the loops are fully unrolled and select -- because a dynamically indexed kernel argument array is copied to scratch; with a
@@ -8,49 +9,9 @@
 #pragma once
 
 #include "kvz_hip_internal.h"
+#include "chain_host.h"
 
 namespace {
-
-static_assert(sizeof(kvz_hip_tile_grid) == 392 && KVZ_HIP_MAX_TILES_PER_DIM == 48, "layout documented in kvz_hip.h");
-
-constexpr int TILE_MAX = KVZ_HIP_MAX_TILES_PER_DIM - 1;      // the largest count of tile columns or rows
-
-inline bool tile_bd_ok(int n, const int32_t *bd, int lcus)
-{
-  if (n < 1 || n > TILE_MAX || bd[0] != 0 || bd[n] != lcus) return false;
-  for (int i = 0; i < n; ++i)
-    if (bd[i + 1] <= bd[i]) return false;
-  return true;
-}
-
-// grid == NULL: one tile, the whole picture.  -> false for a malformed grid (tiles_col_bd / tiles_row_bd, encoder.c:472-481)
-inline bool tile_grid_make(const kvz_hip_tile_grid *grid, int width, int height, kvz_hip_tile_grid *out)
-{
-  const int lcus_x = (width + 63) >> 6, lcus_y = (height + 63) >> 6;
-  __builtin_memset(out, 0, sizeof *out);
-  if (!grid) {
-    out->cols = out->rows = 1;
-    out->col_bd[1] = lcus_x;
-    out->row_bd[1] = lcus_y;
-    return true;
-  }
-  if (!tile_bd_ok(grid->cols, grid->col_bd, lcus_x) || !tile_bd_ok(grid->rows, grid->row_bd, lcus_y)) return false;
-  // the entries beyond the counts are not the caller's to define: they travel as zeros
-  out->cols = grid->cols;
-  out->rows = grid->rows;
-  for (int i = 0; i <= grid->cols; ++i) out->col_bd[i] = grid->col_bd[i];
-  for (int i = 0; i <= grid->rows; ++i) out->row_bd[i] = grid->row_bd[i];
-  return true;
-}
-
-// the largest tile's wavefront count w + 2 (h - 1): the dependent launches of the intra stage
-inline int tile_grid_waves(const kvz_hip_tile_grid &g)
-{
-  int w = 0, h = 0;
-  for (int i = 0; i < g.cols; ++i) w = g.col_bd[i + 1] - g.col_bd[i] > w ? g.col_bd[i + 1] - g.col_bd[i] : w;
-  for (int i = 0; i < g.rows; ++i) h = g.row_bd[i + 1] - g.row_bd[i] > h ? g.row_bd[i + 1] - g.row_bd[i] : h;
-  return w + 2 * (h - 1);
-}
 
 // The lookups walk the boundaries in two parts: the first TILE_NEAR always, the rest only where the grid has more (a wave-uniform
 // branch on a kernel argument), so that the grids that occur -- a handful of tiles per direction -- cost a handful of compares.
@@ -112,38 +73,14 @@ __device__ __forceinline__ bool tile_starts_at(const int32_t (&bd)[KVZ_HIP_MAX_T
 }
 
 // ---- the grids of the pictures of a multi-picture call (cu_qp_multi.hip, deblock_multi.hip, sao_frame_multi.hip) ----
-// Sixteen kvz_hip_tile_grid do not fit the kernel arguments; the boundaries that a call uses do, as in kvz_hip_*_frames_ts: one pool of
-// KVZ_HIP_CHAIN_TILE_BOUNDS 16-bit values (an LCU index is at most 256) that the records share, two to a dword.  A picture's record
-// says where its cols + 1 column and rows + 1 row boundaries stand.  A picture without a grid is one tile and takes nothing from the
-// pool: the first boundary is 0 and the last is the picture's LCU count, so only the boundaries between them are ever read.
+// The pool of boundaries and a picture's place in it (pic_tiles) are described in chain_host.h.
 struct tile_pool {
   u32 bd[KVZ_HIP_CHAIN_TILE_BOUNDS / 2];
   __device__ __forceinline__ int bound(int i) const { return (int)((bd[i >> 1] >> (16 * (i & 1))) & 0xffffu); }
 };
-struct pic_tiles { uint16_t col_at, row_at, lcus_x, lcus_y; u8 cols, rows, pad[2]; };
-static_assert(sizeof(tile_pool) == 2 * KVZ_HIP_CHAIN_TILE_BOUNDS && sizeof(pic_tiles) == 12, "kernel arguments");
+static_assert(sizeof(tile_pool) == 2 * KVZ_HIP_CHAIN_TILE_BOUNDS, "kernel arguments");
 // what a kernel hands to the lookups: both live in the kernel arguments, so every read is a scalar load
 struct pool_grid { const tile_pool &pool; const pic_tiles &t; };
-
-// -> false where the pool is full.  g: what tile_grid_make made of grid
-inline bool tile_pool_add(const kvz_hip_tile_grid *grid, const kvz_hip_tile_grid &g, uint16_t *bounds, int &used, pic_tiles *t)
-{
-  __builtin_memset(t, 0, sizeof *t);
-  t->cols = (u8)g.cols; t->rows = (u8)g.rows;
-  t->lcus_x = (uint16_t)g.col_bd[g.cols]; t->lcus_y = (uint16_t)g.row_bd[g.rows];
-  if (!grid) return true;
-  if (used + g.cols + g.rows + 2 > KVZ_HIP_CHAIN_TILE_BOUNDS) return false;
-  t->col_at = (uint16_t)used;
-  for (int j = 0; j <= g.cols; ++j) bounds[used++] = (uint16_t)g.col_bd[j];
-  t->row_at = (uint16_t)used;
-  for (int j = 0; j <= g.rows; ++j) bounds[used++] = (uint16_t)g.row_bd[j];
-  return true;
-}
-inline void tile_pool_pack(const uint16_t *bounds, int used, tile_pool *pool)
-{
-  __builtin_memset(pool, 0, sizeof *pool);
-  for (int j = 0; j < used; ++j) pool->bd[j >> 1] |= (u32)bounds[j] << (16 * (j & 1));
-}
 
 // The lookups that the shared cores use, for a kvz_hip_tile_grid (the single-picture kernels: the functions above) and for a picture's
 // part of the pool (a loop over the boundaries between the first and the last; wave-uniform where the LCU position is).
