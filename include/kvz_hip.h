@@ -179,7 +179,17 @@ KVZ_HIP_API kvz_hip_stream kvz_hip_stream_create(void);
 KVZ_HIP_API void kvz_hip_stream_destroy(kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_stream_sync(kvz_hip_stream s);
 /* HIP-event timing of the enqueued work on stream s (used by bench.py for the
- * roofline: the event pair brackets exactly the launches issued in between). */
+ * roofline: the event pair brackets exactly the launches issued in between).
+ * What an event is for: it ORDERS and TIMES device work on ONE device.  Work enqueued behind kvz_hip_stream_wait_event on
+ * any stream of the same device sees everything the recording stream wrote before the record; kvz_hip_event_elapsed_ms
+ * returns the device time between two records.  An event does NOT publish memory: results reach the host through
+ * kvz_hip_stream_sync (and kvz_hip_memcpy_d2h, which synchronises), and a peer device through the exchange entries
+ * (kvz_hip_memcpy_peer, kvz_hip_halo_exchange, kvz_hip_tile_halo_exchange), which end with a fenced record of their own
+ * on their stream: an event recorded behind one of them orders a receiving device's work behind pixels it can see.  Any
+ * other write to a peer's memory (kvz_hip_copy_rects_batch with peer pointers) is published by kvz_hip_stream_sync.
+ * Nothing else does.  The events are therefore created without HIP's system-scope fence, which would write back
+ * and invalidate the device's caches at every record (tuning key "event_fence", read by kvz_hip_event_create: 0 = no
+ * system fence, the default; 1 = release to the device; 2 = HIP's default event). */
 KVZ_HIP_API void *kvz_hip_event_create(void);
 KVZ_HIP_API void kvz_hip_event_destroy(void *ev);
 KVZ_HIP_API int kvz_hip_event_record(void *ev, kvz_hip_stream s);

@@ -23,6 +23,8 @@ struct dev_ctx {
   int num_cus = 256;
   hipStream_t stream = nullptr;      // the device's default stream of this library (what a NULL kvz_hip_stream means)
   char name[256] = "";
+  hipEvent_t publish_ev = nullptr;   // default flags, i.e. a system-scope release when recorded: publish_to_peers()
+  std::mutex publish_mu;
 };
 static std::mutex g_mu;
 static dev_ctx g_ctx[KVZ_MAX_DEVICES];
@@ -38,7 +40,7 @@ static tune_entry g_tune[] = { { "sad_wgs_per_cu", {-1} }, { "satd8_wgs_per_cu",
                                { "sao_edge_fast", {-1} }, 
                                { "intra_rough_waves", {-1} }, { "pair_wave_kernel", {-1} }, { "qr4_wgs_per_cu", {-1} }, { "quant_wgs_per_cu", {-1} },
                                { "qr8_reg_kernel", {-1} }, { "qr8_wgs_per_cu", {-1} }, { "qr_tile_kernel", {-1} }, { "dct4_tile", {-1} }, { "dct4_wgs_per_cu", {-1} }, { "idct4_wgs_per_cu", {-1} },
-                               { "wg_chunk_min_wgs", {-1} }, { "pair_satd_threads", {-1} }, { "qr8_tile_kernel", {-1} }, { "qr_tile_pipe", {-1} }, { "pipe", {-1} }, { "dct_pipe", {-1} }, { "sample8_wave", {-1} }, { "full_qsad", {-1} }, { "service_streams", {-1} }, { "service_inflight", {-1} }, { "service_workers", {-1} }, { "service_linger_us", {-1} }, { "service_life_ms", {-1} }, { "service_spin_us", {-1} }, { "service_ticket_base_k", {-1} }, { "service_push", {-1} }, { "service_nap_us", {-1} }, { "service_spin_crowded_us", {-1} } };
+                               { "wg_chunk_min_wgs", {-1} }, { "pair_satd_threads", {-1} }, { "qr8_tile_kernel", {-1} }, { "qr_tile_pipe", {-1} }, { "pipe", {-1} }, { "dct_pipe", {-1} }, { "sample8_wave", {-1} }, { "full_qsad", {-1} }, { "service_streams", {-1} }, { "service_inflight", {-1} }, { "service_workers", {-1} }, { "service_linger_us", {-1} }, { "service_life_ms", {-1} }, { "service_spin_us", {-1} }, { "service_ticket_base_k", {-1} }, { "service_push", {-1} }, { "service_nap_us", {-1} }, { "service_spin_crowded_us", {-1} }, { "event_fence", {-1} } };
 int tuning(const char *key, int dflt)
 {
   for (auto &e : g_tune) if (!std::strcmp(e.key, key)) { const int v = e.value.load(std::memory_order_relaxed); return v >= 0 ? v : dflt; }
@@ -110,6 +112,7 @@ static int ctx_create_locked(int device)
   // default stream before the call (hipMemcpy, a framework's default stream) and before what it puts there afterwards --
   // what a host that passes NULL expects from a HIP API.  Streams from kvz_hip_stream_create() are non-blocking.
   if ((e = hipStreamCreateWithFlags(&c.stream, hipStreamDefault)) != hipSuccess) { set_error("hipStreamCreate", e); return KVZ_HIP_ERR_RUNTIME; }
+  if ((e = hipEventCreate(&c.publish_ev)) != hipSuccess) { set_error("hipEventCreate", e); return KVZ_HIP_ERR_RUNTIME; }
   c.ready.store(true, std::memory_order_release);
   return KVZ_HIP_OK;
 }
@@ -288,6 +291,18 @@ static int enable_peer(int cur, int other)
   return KVZ_HIP_OK;
 }
 
+// The exchange entries end with this: a record of the device's fenced event (HIP's default flags: a system-scope release) on the
+// exchange's stream.  Everything enqueued behind it -- a kvz_hip_event_record of the host's, which itself carries no system fence
+// (kvz_hip_event_create), and so the work of a receiving device that waits for that event -- comes after the pushed pixels have
+// been written back to memory a peer device can see.
+static int publish_to_peers(hipStream_t st)
+{
+  dev_ctx &c = g_ctx[ctx_device()];
+  std::lock_guard<std::mutex> lk(c.publish_mu);
+  HIP_TRY(hipEventRecord(c.publish_ev, st), "hipEventRecord(publish)");
+  return KVZ_HIP_OK;
+}
+
 int kvz_hip_memcpy_peer(void *dst, int dst_device, const void *src, int src_device, size_t bytes, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
@@ -304,7 +319,7 @@ int kvz_hip_memcpy_peer(void *dst, int dst_device, const void *src, int src_devi
   if (bytes == 0) return KVZ_HIP_OK;
   if ((rc = enable_peer(cur, cur == dst_device ? src_device : dst_device)) != KVZ_HIP_OK) return rc;
   HIP_TRY(hipMemcpyPeerAsync(dst, dst_device, src, src_device, bytes, ctx_stream(s)), "hipMemcpyPeerAsync");
-  return KVZ_HIP_OK;
+  return publish_to_peers(ctx_stream(s));
 }
 
 // The halo exchange of kvazaar_amd/shard.py (exchange_halo_into) for a host that drives its shards from ONE process: the
@@ -391,7 +406,8 @@ int kvz_hip_tile_halo_exchange(const kvz_hip_tile_plane *self, const kvz_hip_til
     rects[m].h = r.h;
     ++m;
   }
-  return copy_rects_launch(rects, m, ctx_stream(s), "kvz_hip_tile_halo_exchange");
+  if ((rc = copy_rects_launch(rects, m, ctx_stream(s), "kvz_hip_tile_halo_exchange")) != KVZ_HIP_OK) return rc;
+  return m > 0 ? publish_to_peers(ctx_stream(s)) : KVZ_HIP_OK;
 }
 
 kvz_hip_stream kvz_hip_stream_create(void)
@@ -413,8 +429,16 @@ int kvz_hip_stream_sync(kvz_hip_stream s)
 void *kvz_hip_event_create(void)
 {
   if (!ctx_enter() && (kvz_hip_init(-1) != KVZ_HIP_OK || !ctx_enter())) return nullptr;
+  // An event of this ABI times and orders work of ONE device (include/kvz_hip.h); results reach the host and peer devices through
+  // kvz_hip_stream_sync and the exchange entries.  HIP's default event is more: its record releases at system scope, i.e. writes
+  // back and invalidates the L2 of every XCD, and the next kernel waits for that and starts on cold caches -- 1.2 us of the
+  // 6 us a record costs between the launches bench.py brackets.  Tuning key event_fence, read here:
+  // 0 = no system fence (default), 1 = release to the device, 2 = HIP's default event.  Timing stays enabled in all three.
+  const int fence = tuning("event_fence", 0);
+  const unsigned flags = fence == 0 ? hipEventDisableSystemFence : fence == 1 ? hipEventReleaseToDevice : hipEventDefault;
   hipEvent_t ev = nullptr;
-  if (hipEventCreate(&ev) != hipSuccess) return nullptr;
+  hipError_t e = hipEventCreateWithFlags(&ev, flags);
+  if (e != hipSuccess) { set_error("hipEventCreateWithFlags", e); return nullptr; }
   return (void *)ev;
 }
 void kvz_hip_event_destroy(void *ev) { if (ev) (void)hipEventDestroy((hipEvent_t)ev); }
