@@ -1673,6 +1673,91 @@ KVZ_HIP_API int kvz_hip_inter_recon_frames(const kvz_hip_recon_picture *pictures
                                            const kvz_hip_ref_picture *pool, int n_pool, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
+/* nal group and the last stage of the picture chain: the checksum of  */
+/*   the decoded-picture-hash SEI and the per-plane squared error      */
+/*   reference: array_checksum (strategies-nal.h:34-55,                */
+/*   nal-generic.c:45-69) as kvz_image_checksum calls it per plane     */
+/*   (nal.c:65-74, encoder_state-bitstream.c:894-944), and the SSE     */
+/*   behind the PSNR (encmain.c:101-129)                               */
+/* ------------------------------------------------------------------ */
+/* THE ARITHMETIC, bit depth 8.  For a plane of width x height pixels with row stride `stride`:
+ *   checksum = ( sum over y, x of  data[y * stride + x] ^ mask(x, y) )  mod 2^32
+ *   mask(x, y) = ((x & 255) ^ (y & 255) ^ (x >> 8) ^ (y >> 8)) & 255
+ * x, y are the plane's own coordinates (chroma coordinates for a chroma plane); the SEI carries the 32 bits big-endian.
+ *   sse = sum of (src - rec)^2 per plane, an exact integer (the reference accumulates in double, exact below 2^53).
+ * MD5 IS LEFT OUT ON PURPOSE: array_md5 is one serial dependency chain per plane (64-byte blocks, each needing the state the
+ *   block before it left), so a GPU has nothing to run side by side; and array_md5_generic (nal-generic.c:29-43) hashes
+ *   width * height CONTIGUOUS bytes and ignores stride, so it is not a function of a plane in the sense of every entry here.
+ *   No array_md5 is registered: the selector keeps generic for it. */
+typedef struct { uint32_t checksum[3]; uint32_t sse[3]; } kvz_hip_lcu_hash;       /* 24 bytes; Y, U, V of one LCU */
+typedef struct { uint32_t checksum[3]; uint32_t n_lcu; uint64_t sse[3]; } kvz_hip_picture_hash;  /* 40 bytes */
+/* kvz_hip_lcu_hash: checksum[c] is the LCU's share of plane c's sum, taken with PICTURE coordinates in the mask, so the sum of
+ *   the records modulo 2^32 is the plane's checksum; sse[c] is the LCU's share of the squared error (4096 * 255^2 < 2^32).
+ *   An LCU is 64 x 64 luma and 32 x 32 chroma pixels, clipped at the right and bottom picture edge.  The planes a picture does
+ *   not have (4:0:0) and sse without a source are written as 0: every field of every record is written.
+ * kvz_hip_picture_hash: the sums over the LCU records; n_lcu the number of records summed; sse in 64 bits.
+ *
+ * (a) kvz_hip_picture_hash_frame: the hash of one reconstructed picture, the stage after kvz_hip_sao_frame (with --lossless, after
+ *   the intra stage).  Size, stride, alignment and chroma rules are those of kvz_hip_sao_stats_frame: planes and strides 4-byte
+ *   aligned, strides >= the width, width / height multiples of 8, at least 8, at most 16384; chroma 0 for 4:0:0 (the chroma
+ *   pointers are unused), 1 for 4:2:0.  The bytes between width and stride and below height are never read.
+ *   src: HOST, copied at the call, DEVICE planes; NULL or src->y == NULL means checksum only (sse 0); otherwise src->width /
+ *     src->height must equal width / height.
+ *   lcu_out: DEVICE, required, 4-byte aligned, n_lcu = ceil(width / 64) * ceil(height / 64) records in raster order over the LCUs
+ *     -- the first launch's output.  out: DEVICE, required, 8-byte aligned, one record.
+ *   Two launches: one workgroup per LCU reads every byte once (16-byte row loads where base and stride are 16-byte aligned, dwords
+ *     otherwise) and writes its record; one workgroup then sums the records.  No atomics on memory, no allocation, no buffer
+ *     owned by the call, nothing to clear beforehand, and no result depends on the order in which workgroups run.
+ *   Asynchronous on s; usable between kvz_hip_graph_begin / _end; the launch shapes depend on width, height and chroma only, so a
+ *     captured call may be replayed after the CONTENTS of the planes changed.
+ *   Errors: KVZ_HIP_ERR_INVALID for a missing pointer, a bad size or stride or a misaligned plane or record array; nothing is
+ *     written.  Without a device KVZ_HIP_ERR_NO_DEVICE before anything is looked at. */
+KVZ_HIP_API int kvz_hip_picture_hash_frame(const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                           const kvz_hip_pixel *rec_u, const kvz_hip_pixel *rec_v, uint32_t stride_c, int width,
+                                           int height, int chroma, kvz_hip_lcu_hash *lcu_out, kvz_hip_picture_hash *out,
+                                           kvz_hip_stream s);
+/* One picture of kvz_hip_picture_hash_frames: the arguments of kvz_hip_picture_hash_frame as a record (kvz_hip_filter_picture is
+ * full and fixed).  HOST memory, copied at the call; every pointer is DEVICE memory.  Offsets in front of the fields; no implicit
+ * padding. */
+typedef struct {
+  int32_t width, height;                      /*  0,  4 */
+  int32_t chroma;                             /*  8: 0 = 4:0:0, 1 = 4:2:0 */
+  int32_t reserved;                           /* 12: not read */
+  kvz_hip_ref_picture src;                    /* 16: src.y == NULL: checksum only; else src.width / src.height = width / height */
+  const kvz_hip_pixel *rec_y, *rec_u, *rec_v; /* 56, 64, 72 */
+  uint32_t stride_y, stride_c;                /* 80, 84 */
+  kvz_hip_lcu_hash *lcu_out;                  /* 88: written, n_lcu records */
+  kvz_hip_picture_hash *out;                  /* 96: written, one record */
+} kvz_hip_hash_picture;                       /* 104 bytes */
+/* (b) kvz_hip_picture_hash_frames: kvz_hip_picture_hash_frame for n_pictures (0..KVZ_HIP_MAX_CHAIN_PICTURES) pictures in the same two
+ *   launches, the picture being one more grid dimension; 0 is a no-op.
+ *   THE RULE: per picture, lcu_out and out hold byte for byte what kvz_hip_picture_hash_frame leaves for the record's fields.
+ *   Pictures may differ in size, chroma format and in whether they carry src.  The records (96 bytes per picture) travel in the
+ *   kernel arguments.  Every record is checked before anything is launched: a refusal (KVZ_HIP_ERR_INVALID) names the record in
+ *   kvz_hip_last_error() ("picture 2") and writes nothing.  Records that share lcu_out or out are refused.  Everything else as (a). */
+KVZ_HIP_API int kvz_hip_picture_hash_frames(const kvz_hip_hash_picture *pictures, int n_pictures, kvz_hip_stream s);
+/* (c) the strategy's contract, for arbitrary planes: array_checksum of up to KVZ_HIP_MAX_HASH_PLANES planes in two launches.
+ *   planes: HOST records, copied at the call; data is DEVICE memory.  width, height in 1..65536, any stride >= width, any base
+ *     alignment (16-byte loads where a row segment is 16-byte aligned, dwords where it is 4-byte aligned, bytes otherwise);
+ *     no byte outside the width x height pixels is read.
+ *   block_sums: DEVICE scratch, 4-byte aligned, the sum over the planes of kvz_hip_array_checksum_blocks(width, height) values (one
+ *     per 64 x 64 block; a host-only helper that needs no device and returns 0 for a size out of range).  Every value used is
+ *     written first: nothing to clear.
+ *   checksums: DEVICE, 4-byte aligned, n_planes values, the checksum of plane i at [i], in the host's byte order.
+ *   n_planes == 0 is a no-op.  Asynchronous on s; no allocation, no atomics on memory; usable between kvz_hip_graph_begin / _end.
+ *   Errors as (a); a refusal names the record ("plane 2"). */
+#define KVZ_HIP_MAX_HASH_PLANES 48
+typedef struct {
+  const kvz_hip_pixel *data;                  /*  0: DEVICE */
+  int32_t width, height;                      /*  8, 12 */
+  uint32_t stride;                            /* 16 */
+  uint32_t reserved;                          /* 20: not read */
+} kvz_hip_hash_plane;                         /* 24 bytes */
+KVZ_HIP_API size_t kvz_hip_array_checksum_blocks(int width, int height);
+KVZ_HIP_API int kvz_hip_array_checksum_batch(const kvz_hip_hash_plane *planes, int n_planes, uint32_t *block_sums,
+                                             uint32_t *checksums, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
 /* (1) strategy registration -- the drop-in boundary                   */
 /* ------------------------------------------------------------------ */
 /* kvz_strategyselector_register (strategyselector.h:87, strategyselector.c:216-256) */
@@ -1735,6 +1820,9 @@ KVZ_HIP_API int kvz_strategy_register_quant_hip(void *opaque, uint8_t bitdepth);
 KVZ_HIP_API int kvz_strategy_register_ipol_hip(void *opaque, uint8_t bitdepth);
 KVZ_HIP_API int kvz_strategy_register_intra_hip(void *opaque, uint8_t bitdepth);   /* strategies-intra.h:52-55 */
 KVZ_HIP_API int kvz_strategy_register_sao_hip(void *opaque, uint8_t bitdepth);     /* strategies-sao.h:64-69 */
+/* strategies-nal.h:34-55: array_checksum only, with the reference's signature (host pointers, any stride and alignment, complete
+ * on return, four bytes big-endian and nothing else of the output array).  array_md5 is not registered (see the nal group above). */
+KVZ_HIP_API int kvz_strategy_register_nal_hip(void *opaque, uint8_t bitdepth);
 
 #ifdef __cplusplus
 }

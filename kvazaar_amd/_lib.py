@@ -138,6 +138,31 @@ class ReconPicture(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32), ("cus", C.c_void_p), ("refs", C.c_uint8 * 16), ("params", InterReconParams)]
 
 
+MAX_HASH_PLANES = 48         # KVZ_HIP_MAX_HASH_PLANES
+
+
+class LcuHash(C.Structure):
+    """kvz_hip_lcu_hash"""
+    _fields_ = [("checksum", C.c_uint32 * 3), ("sse", C.c_uint32 * 3)]
+
+
+class PictureHash(C.Structure):
+    """kvz_hip_picture_hash"""
+    _fields_ = [("checksum", C.c_uint32 * 3), ("n_lcu", C.c_uint32), ("sse", C.c_uint64 * 3)]
+
+
+class HashPicture(C.Structure):
+    """kvz_hip_hash_picture"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("chroma", C.c_int32), ("reserved", C.c_int32), ("src", RefPicture),
+                ("rec_y", C.c_void_p), ("rec_u", C.c_void_p), ("rec_v", C.c_void_p), ("stride_y", C.c_uint32), ("stride_c", C.c_uint32),
+                ("lcu_out", C.c_void_p), ("out", C.c_void_p)]
+
+
+class HashPlane(C.Structure):
+    """kvz_hip_hash_plane"""
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -255,6 +280,10 @@ SIGNATURES = {
     "kvz_hip_sao_stats_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_sao_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_inter_recon_frames": (_I, [C.POINTER(ReconPicture), _I, C.POINTER(RefPicture), _I, _P]),
+    "kvz_hip_picture_hash_frame": (_I, [_P, _P, _U, _P, _P, _U, _I, _I, _I, _P, _P, _P]),
+    "kvz_hip_picture_hash_frames": (_I, [C.POINTER(HashPicture), _I, _P]),
+    "kvz_hip_array_checksum_blocks": (_SZ, [_I, _I]),
+    "kvz_hip_array_checksum_batch": (_I, [C.POINTER(HashPlane), _I, _P, _P, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),
@@ -264,6 +293,7 @@ SIGNATURES = {
     "kvz_strategy_register_ipol_hip": (_I, [_P, C.c_uint8]),
     "kvz_strategy_register_intra_hip": (_I, [_P, C.c_uint8]),
     "kvz_strategy_register_sao_hip": (_I, [_P, C.c_uint8]),
+    "kvz_strategy_register_nal_hip": (_I, [_P, C.c_uint8]),
 }
 
 

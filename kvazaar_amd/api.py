@@ -1322,6 +1322,80 @@ def _filter_frames(entry, staged):
     return [st.result() for st in staged]
 
 
+# ---- the last stage of the chain: the SEI checksum and the squared error of a reconstructed picture; array_checksum of planes ----
+LCU_HASH = np.dtype([("checksum", "<u4", (3,)), ("sse", "<u4", (3,))])                            # kvz_hip_lcu_hash
+PICTURE_HASH = np.dtype([("checksum", "<u4", (3,)), ("n_lcu", "<u4"), ("sse", "<u8", (3,))])      # kvz_hip_picture_hash
+
+
+class _HashPicture:
+    """the planes of one picture of kvz_hip_picture_hash_frame(s) on the device, its kvz_hip_hash_picture record with output arrays of
+    its own, and how the outputs come back.  fill: the byte that the output arrays hold before the call."""
+
+    def __init__(self, rec, src=None, chroma=1, fill=0):
+        chroma = int(chroma)
+        r = _stage_planes(rec, chroma)
+        w, h = r[0].w, r[0].h
+        self.record = p = _lib.HashPicture()
+        p.width, p.height, p.chroma = w, h, chroma
+        p.rec_y, p.stride_y = r[0].ptr, r[0].stride
+        if chroma:
+            p.rec_u, p.rec_v, p.stride_c = r[1].ptr, r[2].ptr, r[1].stride
+        self.keep = [r]
+        if src is not None:
+            s = _stage_planes(src, chroma)
+            assert (s[0].w, s[0].h) == (w, h)
+            p.src = _lib.RefPicture(s[0].ptr, s[1].ptr if chroma else None, s[2].ptr if chroma else None, s[0].stride,
+                                    s[1].stride if chroma else 0, w, h)
+            self.keep.append(s)
+        self.n_lcu = lcu_count(w, h)
+        self.lcu_out = DeviceBuffer.from_numpy(np.full(self.n_lcu * LCU_HASH.itemsize, fill, np.uint8))
+        self.out = DeviceBuffer.from_numpy(np.full(PICTURE_HASH.itemsize, fill, np.uint8))
+        p.lcu_out, p.out = self.lcu_out.ptr, self.out.ptr
+
+    def call_single(self, L, stream=None):
+        """kvz_hip_picture_hash_frame with the record's fields -> its return code"""
+        p = self.record
+        return L.kvz_hip_picture_hash_frame(C.byref(p.src) if p.src.y else None, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, p.width, p.height,
+                                            p.chroma, p.lcu_out, p.out, stream)
+
+    def result(self):
+        """(LCU_HASH records [LCUs], the PICTURE_HASH record)"""
+        return (self.lcu_out.to_numpy(np.uint8, (self.n_lcu * LCU_HASH.itemsize,)).view(LCU_HASH),
+                self.out.to_numpy(np.uint8, (PICTURE_HASH.itemsize,)).view(PICTURE_HASH)[0])
+
+
+def picture_hash_frame(rec, src=None, chroma=1):
+    """kvz_hip_picture_hash_frame.  rec, src: (y, u, v) uint8 planes or PlaneViews of the reconstruction and of the source (u, v None
+    for 4:0:0; u and v share one stride); src None: checksum only.  Returns (lcu, picture): LCU_HASH records in raster order over the
+    LCUs and the PICTURE_HASH record."""
+    L = _lib.init()
+    st = _HashPicture(rec, src, chroma)
+    check(st.call_single(L), "picture_hash_frame")
+    return st.result()
+
+
+def picture_hash_frames(pictures):
+    """kvz_hip_picture_hash_frames.  pictures: a list of up to MAX_CHAIN_PICTURES dicts, each with the arguments of picture_hash_frame
+    by name (rec; optional src, chroma).  Returns the list of picture_hash_frame's results, one per picture."""
+    L = _lib.init()
+    staged = [_HashPicture(**p) for p in pictures]
+    records = (_lib.HashPicture * max(len(staged), 1))(*[st.record for st in staged])
+    check(L.kvz_hip_picture_hash_frames(records, len(staged), None), "picture_hash_frames")
+    return [st.result() for st in staged]
+
+
+def array_checksum_batch(planes):
+    """kvz_hip_array_checksum_batch.  planes: up to MAX_HASH_PLANES uint8 planes or PlaneViews (any size, stride and offset).  Returns
+    the checksums, uint32 [planes]."""
+    L = _lib.init()
+    st = [_Staged(p) for p in planes]
+    records = (_lib.HashPlane * max(len(st), 1))(*[_lib.HashPlane(p.ptr, p.w, p.h, p.stride, 0) for p in st])
+    blocks = sum(L.kvz_hip_array_checksum_blocks(p.w, p.h) for p in st)
+    scratch, out = DeviceBuffer(4 * blocks), DeviceBuffer(4 * len(st))
+    check(L.kvz_hip_array_checksum_batch(records, len(st), scratch.ptr, out.ptr, None), "array_checksum_batch")
+    return out.to_numpy(np.uint32, (len(st),))
+
+
 # ---- tile halo exchange: batched rectangle copies on device pointers ----
 def copy_rects(rects, stream=None):
     """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most

@@ -1,8 +1,9 @@
 // chain_host.h -- the host side that the multi-picture entries of the picture chain share (kvz_hip_*_frames, kvz_hip_*_frames_ts and the
 // filter stages' kvz_hip_cu_qp_frames, kvz_hip_deblock_frames, kvz_hip_sao_stats_frames, kvz_hip_sao_frames, kvz_hip_inter_recon_frames):
 // the refusal that names a record, the prologue on the record count, what every residual-stage entry requires of one picture's
-// arguments, the checks of a kvz_hip_chain_picture / kvz_hip_chain_picture_ts record, and the tile grid on the host with the pool of
-// boundaries that the grids of a call share.
+// arguments, the checks of a kvz_hip_chain_picture / kvz_hip_chain_picture_ts record, the tile grid on the host with the pool of
+// boundaries that the grids of a call share, and the record checks of the hash stage (kvz_hip_picture_hash_frame(s),
+// kvz_hip_array_checksum_batch; tests/test_picture_hash_abi.py runs those without a device).
 //
 // Host only: pointer and integer arithmetic on the structs of kvz_hip.h, which compare pointers and never follow them (a
 // kvz_hip_tile_grid and a kvz_hip_trskip are host memory and are read).  No device code and no HIP call, so a plain C++17 compiler
@@ -183,6 +184,51 @@ inline const char *chain_record_ts_shared(const kvz_hip_chain_picture_ts *pictur
   const kvz_hip_chain_picture_ts &r = pictures[i];
   for (int j = 0; j < i; ++j)
     if (chain_output_shared(r.pic, pictures[j].pic) || (r.ts && r.tr_skip_out == pictures[j].tr_skip_out)) return "an output shared with another picture";
+  return nullptr;
+}
+
+// ---- the hash stage: kvz_hip_picture_hash_frame(s) and kvz_hip_array_checksum_batch ----
+static_assert(sizeof(kvz_hip_lcu_hash) == 24 && sizeof(kvz_hip_picture_hash) == 40 && sizeof(kvz_hip_hash_picture) == 104 &&
+              sizeof(kvz_hip_hash_plane) == 24, "layout documented in kvz_hip.h");
+
+// the plane rule of the whole-picture SAO entries: 4-byte aligned base and stride, stride >= the width
+inline bool hash_plane_ok(const void *p, uint32_t stride, int w)
+{
+  return p && !((uintptr_t)p & 3) && !(stride & 3) && stride >= (uint32_t)w;
+}
+
+// kvz_hip_picture_hash_frames, and kvz_hip_picture_hash_frame with its arguments as record 0
+inline const char *hash_record_why(const kvz_hip_hash_picture *pictures, int i)
+{
+  const kvz_hip_hash_picture &p = pictures[i];
+  const int width = p.width, height = p.height;
+  if (!p.lcu_out || !p.out || ((uintptr_t)p.lcu_out & 3) || ((uintptr_t)p.out & 7)) return "lcu_out or out is null or misaligned";
+  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || !hash_plane_ok(p.rec_y, p.stride_y, width))
+    return "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8";
+  if (p.chroma && (!hash_plane_ok(p.rec_u, p.stride_c, width >> 1) || !hash_plane_ok(p.rec_v, p.stride_c, width >> 1)))
+    return "a chroma plane is null or misaligned, or its stride is";
+  if (p.src.y) {
+    if (p.src.width != width || p.src.height != height) return "src.width / src.height differ from width / height";
+    if (!hash_plane_ok(p.src.y, p.src.stride_y, width) ||
+        (p.chroma && (!hash_plane_ok(p.src.u, p.src.stride_c, width >> 1) || !hash_plane_ok(p.src.v, p.src.stride_c, width >> 1))))
+      return "a src plane is null or misaligned, or its stride is";
+  }
+  for (int j = 0; j < i; ++j)
+    if (p.lcu_out == pictures[j].lcu_out || p.out == pictures[j].out) return "an output shared with another picture";
+  return nullptr;
+}
+
+// the 64 x 64 blocks of a plane of kvz_hip_array_checksum_batch; 0 for a size out of range
+inline size_t hash_plane_blocks(int width, int height)
+{
+  if (width < 1 || height < 1 || width > 65536 || height > 65536) return 0;
+  return (size_t)((width + 63) >> 6) * (size_t)((height + 63) >> 6);
+}
+inline const char *hash_plane_why(const kvz_hip_hash_plane &p)
+{
+  if (!p.data) return "data is null";
+  if (!hash_plane_blocks(p.width, p.height)) return "width or height outside 1..65536";
+  if (p.stride < (uint32_t)p.width) return "stride below the width";
   return nullptr;
 }
 

@@ -29,6 +29,8 @@ namespace kvzhip {
 int launch_frac_step(const u8 *win, int w, int h, int step, int fme_level, int hx, int hy,
                      u8 *filtered, i16 *hor_out, i16 *cols_out, hipStream_t st);
 int launch_extend_block(const u8 *rect, int rw, int rh, int ox, int oy, u8 *out, int ow, int oh, hipStream_t st);
+int array_checksum_launch(const kvz_hip_hash_plane *planes, const int *y0, int n_planes, uint32_t *block_sums, uint32_t *checksums, hipStream_t st,
+                          const char *entry);
 }
 
 namespace {
@@ -632,6 +634,38 @@ void hip_inter_recon_bipred(const int hi_prec_luma_rec0, const int hi_prec_luma_
   }
 }
 
+// ---------------- nal group ----------------
+// array_checksum (strategies-nal.h:34-39, nal-generic.c:45-69): four bytes, big-endian, and nothing else of checksum_out.  The rows
+// are staged packed; a plane that does not fit the staging buffer goes in bands of rows, each with its first row for the mask, and
+// the bands' sums are added modulo 2^32.
+void hip_array_checksum(const kvz_hip_pixel *data, const int height, const int width, const int stride, unsigned char checksum_out[],
+                        const uint8_t bitdepth)
+{
+  (void)bitdepth;           // registered for bitdepth 8 only
+  u32 sum = 0;
+  if (width > 0 && height > 0) {
+    if (width > 65536) die("array_checksum: bad arguments", KVZ_HIP_ERR_INVALID);
+    call_ctx &c = tls(); stage s(c);
+    // what a band needs beside its pixels: one value per 64 x 64 block and the result
+    const int fit = (int)((c.cap - (c.cap >> 4)) / (size_t)width), band = fit < height ? fit : height;
+    const size_t blocks = kvz_hip_array_checksum_blocks(width, band);
+    const size_t od = s.take((size_t)width * band), in_end = s.off, ob = s.take(blocks * 4), oc = s.take(4);
+    for (int y0 = 0; y0 < height; y0 += band) {
+      const int rows = height - y0 < band ? height - y0 : band;
+      pack_rows(c.h + od, data + (size_t)y0 * stride, width, rows, (size_t)stride);
+      s.h2d(0, in_end);
+      const kvz_hip_hash_plane p = { c.d + od, width, rows, (u32)width, 0 };
+      MUST(array_checksum_launch(&p, &y0, 1, (u32 *)(c.d + ob), (u32 *)(c.d + oc), c.st, "array_checksum"));
+      s.d2h(oc, 4); s.sync();
+      sum += *(u32 *)(c.h + oc);
+    }
+  }
+  checksum_out[0] = (unsigned char)(sum >> 24);
+  checksum_out[1] = (unsigned char)(sum >> 16);
+  checksum_out[2] = (unsigned char)(sum >> 8);
+  checksum_out[3] = (unsigned char)sum;
+}
+
 int reg(void *opaque, const char *type, void *fptr)
 {
   kvz_hip_register_fn f = g_registrar ? g_registrar : (kvz_hip_register_fn)kvz_strategyselector_register;
@@ -773,6 +807,13 @@ int kvz_strategy_register_sao_hip(void *opaque, uint8_t bitdepth)
   ok &= reg(opaque, "sao_reconstruct_color", (void *)&hip_sao_reconstruct_color);
   ok &= reg(opaque, "sao_band_ddistortion", (void *)&hip_sao_band_ddistortion);
   return ok;
+}
+
+// STRATEGIES_NAL_EXPORTS, strategies-nal.h:51-53: array_checksum.  array_md5 is one serial chain per plane and stays with generic.
+int kvz_strategy_register_nal_hip(void *opaque, uint8_t bitdepth)
+{
+  if (!hook_ready(bitdepth)) return 0;
+  return reg(opaque, "array_checksum", (void *)&hip_array_checksum);
 }
 
 }  // extern "C"

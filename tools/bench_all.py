@@ -255,6 +255,88 @@ def main():
         chain_filter_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
     if not args.only or any(o in "inter_recon_frames_1080p_p_x4 inter_recon_frames_1080p_b_x4" for o in args.only.split(",")):
         inter_recon_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "picture_hash_frame_1080p picture_hash_frame_4k picture_hash_frames_1080p_x16 array_checksum_batch_1080p" for o in args.only.split(",")):
+        picture_hash_rows(L, st, dev, max(args.rounds, 5))
+
+
+def picture_hash_rows(L, st, dev, rounds, iters=20):
+    """The hash stage: kvz_hip_picture_hash_frame for one 1080p (1088 coded rows) and one 4K 4:2:0 picture with its source,
+    kvz_hip_picture_hash_frames for sixteen 1080p pictures, kvz_hip_array_checksum_batch for the three planes of the 1080p picture.
+    Device time by events, ms per call: median and min..max over the rounds; GB/s = bytes read (source and reconstruction, 3 per luma
+    pixel; the plane entry reads the reconstruction alone) / time.  Beside them, in the same run, what a host does today for the same
+    picture: kvz_hip_memcpy_d2h of the three planes (host wall clock, synchronised), then the compiled reference's generic8 per plane and
+    the squared error as a numpy sum (the reference's own loop is a static function of its command-line tool) on the CPU -- where the
+    reference is not built, numpy stands in for generic8 too and the row says so."""
+    import time
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from kvazaar_amd import api
+    g = torch.Generator(device=dev); g.manual_seed(41)
+    print("%-32s %9s %10s %18s %10s" % ("kernel", "launches", "ms", "min..max ms", "GB/s"))
+
+    def picture(W, H):
+        src = [torch.randint(0, 256, (H >> c, W >> c), dtype=torch.uint8, device=dev, generator=g) for c in (0, 1, 1)]
+        rec = [(p.to(torch.int16) + torch.randint(-6, 7, p.shape, dtype=torch.int16, device=dev, generator=g)).clamp_(0, 255).to(torch.uint8) for p in src]
+        lcu = torch.empty(api.lcu_count(W, H) * 6, dtype=torch.int32, device=dev)
+        out = torch.empty(5, dtype=torch.int64, device=dev)
+        r = _lib.HashPicture()
+        r.width, r.height, r.chroma = W, H, 1
+        r.src = _lib.RefPicture(src[0].data_ptr(), src[1].data_ptr(), src[2].data_ptr(), W, W // 2, W, H)
+        r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), W, W // 2
+        r.lcu_out, r.out = lcu.data_ptr(), out.data_ptr()
+        return r, (src, rec, lcu, out)
+
+    def row(name, launches, fn, nbytes):
+        t = [timed(L, st, lambda: _lib.check(fn(), name), iters=iters, warm=3) for _ in range(rounds)]
+        ms = float(np.median(t))
+        print("%-32s %9d %10.4f %18s %10.1f" % (name, launches, ms, "%.4f..%.4f" % (min(t), max(t)), nbytes / ms / 1e6))
+
+    def single(r):
+        return lambda: L.kvz_hip_picture_hash_frame(C.byref(r.src), r.rec_y, r.stride_y, r.rec_u, r.rec_v, r.stride_c, r.width, r.height, 1, r.lcu_out, r.out, st)
+    hd, keep_hd = picture(1920, 1088)
+    uhd, keep_uhd = picture(3840, 2160)
+    many = [picture(1920, 1088) for _ in range(16)]
+    recs = (_lib.HashPicture * 16)(*[m[0] for m in many])
+    planes = (_lib.HashPlane * 3)(*[_lib.HashPlane(p.data_ptr(), p.shape[1], p.shape[0], p.shape[1], 0) for p in keep_hd[1]])
+    blocks = sum(L.kvz_hip_array_checksum_blocks(p.shape[1], p.shape[0]) for p in keep_hd[1])
+    scratch, sums = torch.empty(blocks, dtype=torch.int32, device=dev), torch.empty(3, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    row("picture_hash_frame_1080p", 2, single(hd), 3.0 * 1920 * 1088)
+    row("picture_hash_frame_4k", 2, single(uhd), 3.0 * 3840 * 2160)
+    row("picture_hash_frames_1080p_x16", 2, lambda: L.kvz_hip_picture_hash_frames(recs, 16, st), 16 * 3.0 * 1920 * 1088)
+    row("array_checksum_batch_1080p", 2, lambda: L.kvz_hip_array_checksum_batch(planes, 3, scratch.data_ptr(), sums.data_ptr(), st), 1.5 * 1920 * 1088)
+
+    # what a host does today: the planes copied back, then the checksum and the squared error on the CPU
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import picture_hash_model as M
+    import ref_lib as R
+    fn = None
+    if R.available():
+        import gen_picture_hash_golden as G
+        fn = G.reference_functions()["generic8"]
+    for name, (r, keep) in (("1080p", (hd, keep_hd)), ("4k", (uhd, keep_uhd))):
+        src, rec = keep[0], keep[1]
+        host = [np.empty(tuple(p.shape), np.uint8) for p in rec]
+        host_src = [p.cpu().numpy() for p in src]
+        t_copy, t_sum, t_sse = [], [], []
+        for _ in range(rounds):
+            _lib.check(L.kvz_hip_stream_sync(st), "sync")
+            t0 = time.perf_counter()
+            for p, h in zip(rec, host):
+                _lib.check(L.kvz_hip_memcpy_d2h(h.ctypes.data, p.data_ptr(), h.nbytes, st), "d2h")
+            _lib.check(L.kvz_hip_stream_sync(st), "sync")
+            t1 = time.perf_counter()
+            sums_host = [G.call(fn, h, h.shape[1], h.shape[0]) if fn else M.plane_checksum(h, h.shape[1], h.shape[0]) for h in host]
+            t2 = time.perf_counter()
+            sse_host = [M.plane_sse(a, b, b.shape[1], b.shape[0]) for a, b in zip(host_src, host)]
+            t3 = time.perf_counter()
+            t_copy.append((t1 - t0) * 1e3); t_sum.append((t2 - t1) * 1e3); t_sse.append((t3 - t2) * 1e3)
+        _lib.check(single(r)(), "picture_hash_frame")
+        _lib.check(L.kvz_hip_stream_sync(st), "sync")
+        got = keep[3].cpu().numpy()
+        assert [int(v) & 0xFFFFFFFF for v in (got[0], got[0] >> 32, got[1])] == sums_host and [int(v) for v in got[2:5]] == sse_host, "the device and the host disagree"
+        print("host today, %-5s: d2h of the planes %.3f ms, %s %.3f ms, squared error (numpy) %.3f ms  (medians of %d)" % (
+            name, float(np.median(t_copy)), "generic8" if fn else "checksum (numpy, no reference built)", float(np.median(t_sum)), float(np.median(t_sse)), rounds))
 
 
 def inter_recon_multi_rows(L, st, dev, rounds, only, pictures=4, iters=20):

@@ -42,6 +42,8 @@ kvz_hip_intra_recon_frames_ts, every picture with the same grid, the same tables
 all N pictures in one call each as well: kvz_hip_deblock_frames, kvz_hip_sao_stats_frames and kvz_hip_sao_frames, and with --lcu-qp
 kvz_hip_cu_qp_frames after the intra stage.  --lossless (one launch per picture already) stays single-picture and is refused with
 --pictures.
+The last stage of a picture in every sequence is its hash, kvz_hip_picture_hash_frame on what kvz_hip_sao_frame wrote (with --lossless on
+what the intra stage wrote; with --pictures kvz_hip_picture_hash_frames for all N): the SEI checksum and the squared error stay on the device.
 """
 import argparse
 import ctypes as C
@@ -160,6 +162,13 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
         stages["tu"].append(("intra_recon_frame_lossless", 1, lambda s: L.kvz_hip_intra_recon_frame_lossless(
             ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
             ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), None, None, grid.ctypes.data if tiles else None, C.byref(ll), s)))
+        # the last stage of a picture: the SEI checksum and the squared error of the finished reconstruction
+        ll_lcu = torch.empty(api.lcu_count(W, H) * 6, dtype=torch.int32, device=dev)
+        ll_hash = torch.empty(5, dtype=torch.int64, device=dev)
+        keep += [ll_lcu, ll_hash]
+        stages["tu"].append(("picture_hash_frame", api.lcu_count(W, H), lambda s: L.kvz_hip_picture_hash_frame(
+            ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, W, H, 1, ll_lcu.data_ptr(),
+            ll_hash.data_ptr(), s)))
         del stages["sao"]                                            # no deblocking, no SAO (encoder.c:623-628)
         return stages, keep
     if pictures:
@@ -385,6 +394,17 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
         stages["sao"].insert(0, ("deblock_frames", pictures, lambda s: L.kvz_hip_deblock_frames(f_recs, pictures, s)))
         stages["sao"].insert(1, ("sao_stats_frames", pictures * 3 * n_lcu, lambda s: L.kvz_hip_sao_stats_frames(f_recs, pictures, s)))
         stages["sao"].insert(2, ("sao_frames", pictures, lambda s: L.kvz_hip_sao_frames(f_recs, pictures, s)))
+        # the last stage: the SEI checksum and the squared error of every finished picture, in one call
+        h_recs = (_lib.HashPicture * pictures)()
+        keep.append(h_recs)
+        for i in range(pictures):
+            lcu, tot = torch.empty(n_lcu * 6, dtype=torch.int32, device=dev), torch.empty(5, dtype=torch.int64, device=dev)
+            keep += [lcu, tot]
+            f, r = f_recs[i], h_recs[i]
+            r.width, r.height, r.chroma, r.src = W, DH, 1, f.src
+            r.rec_y, r.rec_u, r.rec_v, r.stride_y, r.stride_c = f.dst_y, f.dst_u, f.dst_v, f.dst_stride_y, f.dst_stride_c
+            r.lcu_out, r.out = lcu.data_ptr(), tot.data_ptr()
+        stages["sao"].insert(3, ("picture_hash_frames", pictures * n_lcu, lambda s: L.kvz_hip_picture_hash_frames(h_recs, pictures, s)))
         return stages, keep
     stages["sao"].insert(1, ("sao_stats_frame", 3 * n_lcu, lambda s: L.kvz_hip_sao_stats_frame(
         so_tab.ctypes.data, dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, 1, so_stats.data_ptr(), so_cands.data_ptr(), s)))
@@ -396,6 +416,13 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
         stages["sao"].insert(2, ("sao_frame", 1, lambda s: L.kvz_hip_sao_frame(
             dby.data_ptr(), W, dbu.data_ptr(), dbv.data_ptr(), W // 2, so_dst[0].data_ptr(), W, so_dst[1].data_ptr(), so_dst[2].data_ptr(), W // 2,
             W, DH, so_luma.data_ptr(), so_chroma.data_ptr(), 1, s)))
+    # the last stage of a picture: the SEI checksum and the squared error of the finished reconstruction
+    so_lcu = torch.empty(n_lcu * 6, dtype=torch.int32, device=dev)
+    so_hash = torch.empty(5, dtype=torch.int64, device=dev)
+    keep += [so_lcu, so_hash]
+    stages["sao"].insert(3, ("picture_hash_frame", n_lcu, lambda s: L.kvz_hip_picture_hash_frame(
+        so_tab.ctypes.data, so_dst[0].data_ptr(), W, so_dst[1].data_ptr(), so_dst[2].data_ptr(), W // 2, W, DH, 1, so_lcu.data_ptr(),
+        so_hash.data_ptr(), s)))
     return stages, keep
 
 
