@@ -189,7 +189,24 @@ KVZ_HIP_API int kvz_hip_stream_sync(kvz_hip_stream s);
  * other write to a peer's memory (kvz_hip_copy_rects_batch with peer pointers) is published by kvz_hip_stream_sync.
  * Nothing else does.  The events are therefore created without HIP's system-scope fence, which would write back
  * and invalidate the device's caches at every record (tuning key "event_fence", read by kvz_hip_event_create: 0 = no
- * system fence, the default; 1 = release to the device; 2 = HIP's default event). */
+ * system fence, the default; 1 = release to the device; 2 = HIP's default event).
+ * The handle is opaque (it is not a hipEvent_t).
+ * A RECORD THAT DIRECTLY FOLLOWS A BATCH LAUNCH MARKS THAT LAUNCH'S COMPLETION.  When kvz_hip_event_record is the next operation
+ * of this ABI on the stream after kvz_hip_sad_nxn_batch, kvz_hip_satd_nxn_batch, their _dual_ forms or kvz_hip_transform_batch
+ * (DCT / IDCT / DST / IDST), and the caller had recorded an event just before that entry as well, the record enqueues nothing:
+ * the event stands for the end of that kernel, which the kernel's own dispatch reports.  It orders (kvz_hip_stream_wait_event)
+ * and times (kvz_hip_event_elapsed_ms) exactly as a record behind the kernel does, and like every event of this ABI it has
+ * never published memory.  Records with nothing in between share that instant: the time between them is 0.  Every other
+ * record -- behind any other entry, behind a copy, a memset, a wait, a graph launch, inside a capture, or with no record in
+ * front of the launch -- is a record of its own, as before.
+ * ONE CAVEAT: the library sees only what goes through this ABI.  A stream from kvz_hip_stream_create, or a hipStream_t of the
+ * caller's, can also take work by other means -- a framework that was handed the stream, plain HIP calls.  (NULL is the
+ * library's own stream of the device, which nobody else holds; work on HIP's legacy default stream is ordered against it by
+ * HIP but never enqueued on it.)  Work placed that way BETWEEN one of the launches above and the record behind it is not
+ * covered by the event.  Such a caller puts any operation of this ABI in between or switches the behaviour off: tuning key
+ * "event_alias", 1 = on (the default), 0 = every record is a packet of its own.
+ * THREADS: a record rides only on a launch of the calling thread.  Threads that share a stream (NULL is one per device) get
+ * records of their own for each other's launches, so each thread's record still covers the work it enqueued before it. */
 KVZ_HIP_API void *kvz_hip_event_create(void);
 KVZ_HIP_API void kvz_hip_event_destroy(void *ev);
 KVZ_HIP_API int kvz_hip_event_record(void *ev, kvz_hip_stream s);

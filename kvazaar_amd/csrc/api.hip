@@ -7,6 +7,7 @@
 // a thread that never chose one uses the process default = the first device initialised.  Every entry runs on the
 // calling thread's current device: its default stream, its CU count, its staging buffers.
 #include "kvz_hip_internal.h"
+#include "event_alias.h"
 
 #include <atomic>
 #include <cstdio>
@@ -40,7 +41,7 @@ static tune_entry g_tune[] = { { "sad_wgs_per_cu", {-1} }, { "satd8_wgs_per_cu",
                                { "sao_edge_fast", {-1} }, 
                                { "intra_rough_waves", {-1} }, { "pair_wave_kernel", {-1} }, { "qr4_wgs_per_cu", {-1} }, { "quant_wgs_per_cu", {-1} },
                                { "qr8_reg_kernel", {-1} }, { "qr8_wgs_per_cu", {-1} }, { "qr_tile_kernel", {-1} }, { "dct4_tile", {-1} }, { "dct4_wgs_per_cu", {-1} }, { "idct4_wgs_per_cu", {-1} },
-                               { "wg_chunk_min_wgs", {-1} }, { "pair_satd_threads", {-1} }, { "qr8_tile_kernel", {-1} }, { "qr_tile_pipe", {-1} }, { "pipe", {-1} }, { "dct_pipe", {-1} }, { "sample8_wave", {-1} }, { "full_qsad", {-1} }, { "service_streams", {-1} }, { "service_inflight", {-1} }, { "service_workers", {-1} }, { "service_linger_us", {-1} }, { "service_life_ms", {-1} }, { "service_spin_us", {-1} }, { "service_ticket_base_k", {-1} }, { "service_push", {-1} }, { "service_nap_us", {-1} }, { "service_spin_crowded_us", {-1} }, { "event_fence", {-1} } };
+                               { "wg_chunk_min_wgs", {-1} }, { "pair_satd_threads", {-1} }, { "qr8_tile_kernel", {-1} }, { "qr_tile_pipe", {-1} }, { "pipe", {-1} }, { "dct_pipe", {-1} }, { "sample8_wave", {-1} }, { "full_qsad", {-1} }, { "service_streams", {-1} }, { "service_inflight", {-1} }, { "service_workers", {-1} }, { "service_linger_us", {-1} }, { "service_life_ms", {-1} }, { "service_spin_us", {-1} }, { "service_ticket_base_k", {-1} }, { "service_push", {-1} }, { "service_nap_us", {-1} }, { "service_spin_crowded_us", {-1} }, { "event_fence", {-1} }, { "event_alias", {-1} } };
 int tuning(const char *key, int dflt)
 {
   for (auto &e : g_tune) if (!std::strcmp(e.key, key)) { const int v = e.value.load(std::memory_order_relaxed); return v >= 0 ? v : dflt; }
@@ -66,7 +67,70 @@ bool ctx_enter()
   }
   return true;
 }
-hipStream_t ctx_stream(kvz_hip_stream s) { return s ? (hipStream_t)s : g_ctx[ctx_device()].stream; }
+static hipStream_t raw_stream(kvz_hip_stream s) { return s ? (hipStream_t)s : g_ctx[ctx_device()].stream; }
+
+// ---- events that ride on a launch (event_alias.h has the rules) ----
+// The flags of kvz_hip_event_create's events and of the carriers, from the tuning key event_fence.
+static unsigned event_flags(int fence) { return fence == 0 ? hipEventDisableSystemFence : fence == 1 ? hipEventReleaseToDevice : hipEventDefault; }
+struct carrier_factory {
+  // pool = device * 3 + event_fence: a carrier is an event of one device and is created like the ABI's own events, so that a
+  // carried launch releases no wider than the record it stands for
+  bool create(int pool, hipEvent_t *out)
+  {
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != pool / 3) return false;
+    if (hipEventCreateWithFlags(out, event_flags(pool % 3)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return true;
+  }
+  void destroy(hipEvent_t) {}        // the table lives as long as the process
+};
+typedef event_alias<hipEvent_t, carrier_factory> alias_table;
+static alias_table &aliases()
+{
+  static alias_table *t = new alias_table();       // never destroyed: events may outlive every static destructor
+  return *t;
+}
+// what kvz_hip_event_create returns: the event's own HIP event, and the carrier its last record was aliased to, if any
+struct abi_event {
+  hipEvent_t own = nullptr;
+  alias_table::event_state alias;
+};
+
+// Every entry resolves its stream here, once or more: that is what tells the table that the stream has moved on.
+// kvz_hip_event_record alone uses raw_stream(): it is an operation only if it turns out to be a real record.
+hipStream_t ctx_stream(kvz_hip_stream s)
+{
+  hipStream_t st = raw_stream(s);
+  aliases().touch(st);
+  return st;
+}
+
+// the carrier pool of the calling thread's device under the current event_fence
+static int event_pool()
+{
+  int fence = tuning("event_fence", 0);
+  if (fence < 0 || fence > 2) fence = 2;
+  return ctx_device() * 3 + fence;
+}
+
+hipEvent_t launch_carrier(hipStream_t st)
+{
+  if (!tuning("event_alias", 1)) return nullptr;
+  alias_table &t = aliases();
+  if (!t.armed(st)) return nullptr;
+  // inside a capture the record / wait pairs are the graph's fork and join edges: they stay real records
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  if (cap != hipStreamCaptureStatusNone) return nullptr;
+  // The carrier's flavour is event_fence as it stands NOW, at the launch; the ABI event that will alias it took its flags when it
+  // was created.  The two agree while the key is left alone between kvz_hip_event_create and the launch, which is how the key is
+  // meant to be used (set once, before the events are made).  If it was changed in between, the record behind this launch releases
+  // as the key says now, not as the event was made; no event of this ABI publishes memory either way (include/kvz_hip.h).
+  hipEvent_t ev = nullptr;
+  return t.arm(st, event_pool(), &ev) ? ev : nullptr;
+}
+// launch_carried(): the launch that took launch_carrier()'s event failed, so no record may stand on it
+void launch_uncarry(hipStream_t st) { aliases().disarm(st); }
 int num_cus() { const int d = ctx_device(); return d >= 0 ? g_ctx[d].num_cus : 256; }
 
 void set_error(const char *what, hipError_t e)
@@ -418,7 +482,12 @@ kvz_hip_stream kvz_hip_stream_create(void)
   if (e != hipSuccess) { set_error("hipStreamCreate", e); return nullptr; }
   return (kvz_hip_stream)st;
 }
-void kvz_hip_stream_destroy(kvz_hip_stream s) { if (s) (void)hipStreamDestroy((hipStream_t)s); }
+void kvz_hip_stream_destroy(kvz_hip_stream s)
+{
+  if (!s) return;
+  aliases().forget_stream((hipStream_t)s);       // a later stream may get the same address
+  (void)hipStreamDestroy((hipStream_t)s);
+}
 int kvz_hip_stream_sync(kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
@@ -435,24 +504,44 @@ void *kvz_hip_event_create(void)
   // 6 us a record costs between the launches bench.py brackets.  Tuning key event_fence, read here:
   // 0 = no system fence (default), 1 = release to the device, 2 = HIP's default event.  Timing stays enabled in all three.
   const int fence = tuning("event_fence", 0);
-  const unsigned flags = fence == 0 ? hipEventDisableSystemFence : fence == 1 ? hipEventReleaseToDevice : hipEventDefault;
-  hipEvent_t ev = nullptr;
-  hipError_t e = hipEventCreateWithFlags(&ev, flags);
-  if (e != hipSuccess) { set_error("hipEventCreateWithFlags", e); return nullptr; }
-  return (void *)ev;
+  abi_event *a = new abi_event();
+  hipError_t e = hipEventCreateWithFlags(&a->own, event_flags(fence));
+  if (e != hipSuccess) { set_error("hipEventCreateWithFlags", e); delete a; return nullptr; }
+  // the carrier this event may come to alias is made here, not inside the launch that the event times
+  if (tuning("event_alias", 1)) aliases().provision_event(a->alias, event_pool());
+  return (void *)a;
 }
-void kvz_hip_event_destroy(void *ev) { if (ev) (void)hipEventDestroy((hipEvent_t)ev); }
+void kvz_hip_event_destroy(void *ev)
+{
+  if (!ev) return;
+  abi_event *a = (abi_event *)ev;
+  aliases().destroy_event(a->alias);
+  (void)hipEventDestroy(a->own);
+  delete a;
+}
+// A record that directly follows a launch which carries an event of the table's (launch_carried, kvz_hip_internal.h) means "when
+// that kernel has ended", and the kernel's own dispatch packet already says so: the event takes the carrier and no marker packet
+// enters the queue (tuning key event_alias, 1 = on).  Every other record is a hipEventRecord of the event's own handle.
 int kvz_hip_event_record(void *ev, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  HIP_TRY(hipEventRecord((hipEvent_t)ev, ctx_stream(s)), "hipEventRecord");
+  if (!ev) return kvzhip::invalid_arg(__func__);
+  abi_event *a = (abi_event *)ev;
+  hipStream_t st = raw_stream(s);
+  hipEvent_t carrier = nullptr;
+  if (aliases().record(a->alias, st, &carrier)) return KVZ_HIP_OK;
+  HIP_TRY(hipEventRecord(a->own, st), "hipEventRecord");
   return KVZ_HIP_OK;
 }
 int kvz_hip_event_elapsed_ms(void *start, void *stop, float *ms)
 {
   KVZ_CHECK_CTX();
-  HIP_TRY(hipEventSynchronize((hipEvent_t)stop), "hipEventSynchronize");
-  HIP_TRY(hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop), "hipEventElapsedTime");
+  if (!start || !stop || !ms) return kvzhip::invalid_arg(__func__);
+  abi_event *a = (abi_event *)start, *b = (abi_event *)stop;
+  const hipEvent_t ea = aliases().current(a->alias, a->own), eb = aliases().current(b->alias, b->own);
+  HIP_TRY(hipEventSynchronize(eb), "hipEventSynchronize");
+  if (ea == eb) { *ms = 0.0f; return KVZ_HIP_OK; }       // two records behind one launch with nothing in between: the same instant
+  HIP_TRY(hipEventElapsedTime(ms, ea, eb), "hipEventElapsedTime");
   return KVZ_HIP_OK;
 }
 
@@ -460,7 +549,8 @@ int kvz_hip_stream_wait_event(kvz_hip_stream s, void *ev)
 {
   KVZ_CHECK_CTX();
   if (!ev) return kvzhip::invalid_arg(__func__);
-  HIP_TRY(hipStreamWaitEvent(ctx_stream(s), (hipEvent_t)ev, 0), "hipStreamWaitEvent");
+  abi_event *a = (abi_event *)ev;
+  HIP_TRY(hipStreamWaitEvent(ctx_stream(s), aliases().current(a->alias, a->own), 0), "hipStreamWaitEvent");
   return KVZ_HIP_OK;
 }
 

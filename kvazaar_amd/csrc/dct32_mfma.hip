@@ -151,10 +151,10 @@ int launch_dct32_mfma(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   const size_t cap = wg_cap(inverse ? tuning("idct32_wgs_per_cu", 96) : tuning("dct32_wgs_per_cu", 4096));
   if (wgs > cap) wgs = cap;
   if (tuning("dct_pipe", 0)) {
-    if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<32, true, false, true>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
-    else hipLaunchKernelGGL((dct32_mfma_kernel<32, false, false, true>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
-  } else if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<32, true>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
-  else hipLaunchKernelGGL((dct32_mfma_kernel<32, false>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
+    if (inverse) launch_carried(dct32_mfma_kernel<32, true, false, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
+    else launch_carried(dct32_mfma_kernel<32, false, false, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
+  } else if (inverse) launch_carried(dct32_mfma_kernel<32, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
+  else launch_carried(dct32_mfma_kernel<32, false>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
   KVZ_CHECK_LAUNCH("dct32_mfma_kernel");
   return KVZ_HIP_OK;
 }
@@ -169,11 +169,11 @@ int launch_dct4_tile(bool inverse, bool dst, const i16 *in, i16 *out, size_t cou
   if (wgs > cap) wgs = cap;
   const dim3 g((unsigned)wgs), b(256);
   if (dst) {
-    if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<4, true, true>), g, b, 0, st, in, out, count);
-    else hipLaunchKernelGGL((dct32_mfma_kernel<4, false, true>), g, b, 0, st, in, out, count);
+    if (inverse) launch_carried(dct32_mfma_kernel<4, true, true>, g, b, 0, st, in, out, count);
+    else launch_carried(dct32_mfma_kernel<4, false, true>, g, b, 0, st, in, out, count);
   } else {
-    if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<4, true, false>), g, b, 0, st, in, out, count);
-    else hipLaunchKernelGGL((dct32_mfma_kernel<4, false, false>), g, b, 0, st, in, out, count);
+    if (inverse) launch_carried(dct32_mfma_kernel<4, true, false>, g, b, 0, st, in, out, count);
+    else launch_carried(dct32_mfma_kernel<4, false, false>, g, b, 0, st, in, out, count);
   }
   KVZ_CHECK_LAUNCH("dct32_mfma_kernel<4>");
   return KVZ_HIP_OK;
@@ -186,8 +186,8 @@ int launch_dct16_tile(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   // workgroups per CU (0.5 GiB arrays): forward 64: 6.43, 96: 6.50, 128: 6.52, 192: 6.42, 256: 6.34 TB/s; inverse 32: 6.16, 64: 6.17, 96: 5.98, 128: 5.81
   const size_t cap = wg_cap(inverse ? tuning("idct16_wgs_per_cu", 64) : tuning("dct16_wgs_per_cu", 128));
   if (wgs > cap) wgs = cap;
-  if (inverse) hipLaunchKernelGGL((dct32_mfma_kernel<16, true>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
-  else hipLaunchKernelGGL((dct32_mfma_kernel<16, false>), dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
+  if (inverse) launch_carried(dct32_mfma_kernel<16, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
+  else launch_carried(dct32_mfma_kernel<16, false>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
   KVZ_CHECK_LAUNCH("dct32_mfma_kernel<16>");
   return KVZ_HIP_OK;
 }

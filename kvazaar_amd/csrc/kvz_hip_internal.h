@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stddef.h>
 #include <stdint.h>
 
@@ -19,7 +20,9 @@ namespace kvzhip {
 int ctx_device();                               // the calling thread's current device (-1: none initialised)
 bool ctx_ready();
 bool ctx_enter();                               // ready, and the calling thread's HIP device = its kvz_hip device
-hipStream_t ctx_stream(kvz_hip_stream s);      // NULL -> library default stream
+hipStream_t ctx_stream(kvz_hip_stream s);      // NULL -> library default stream; counts as an operation on it (event_alias.h)
+hipEvent_t launch_carrier(hipStream_t st);     // the event launch_carried() binds to the dispatch, or NULL: launch as ever
+void launch_uncarry(hipStream_t st);           // that launch failed: nothing was carried
 void set_error(const char *what, hipError_t e);
 void set_error_msg(const char *what);
 int invalid_arg(const char *entry);             // records "<entry>: invalid argument" and returns KVZ_HIP_ERR_INVALID
@@ -61,8 +64,24 @@ static inline unsigned stream_grid(size_t work_items, unsigned items_per_block, 
   return (unsigned)(need < cap ? need : cap);
 }
 
-// ---- device helpers ----
 #if defined(__HIPCC__)
+
+// The launch of an entry that enqueues ONE kernel and nothing behind it, on the stream its ctx_stream() call returned.  When the
+// caller recorded an event just before the entry, the record that will follow can ride on this dispatch (api.hip,
+// kvz_hip_event_record): the launch then binds a carrier event to the dispatch packet, whose completion signal supplies the
+// end timestamp and the ordering point.  Otherwise, and always inside a capture, this is hipLaunchKernelGGL.
+template <typename T> struct launch_arg { typedef T type; };
+template <typename... KArgs>
+static inline void launch_carried(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned lds, hipStream_t st,
+                                  typename launch_arg<KArgs>::type... args)
+{
+  if (hipEvent_t stop = launch_carrier(st)) {
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, st, nullptr, stop, 0, args...);
+    if (hipPeekAtLastError() != hipSuccess) launch_uncarry(st);      // the entry's KVZ_CHECK_LAUNCH reports it; the event was never bound
+  } else hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+}
+
+// ---- device helpers ----
 
 // DPP cross-lane moves (no LDS traffic).  quad_perm / row_half_mirror / row_mirror.
 template <int CTRL>

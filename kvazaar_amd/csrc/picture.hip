@@ -718,7 +718,7 @@ static int launch_sad(int n, const u8 *a, const u8 *b, size_t count, u32 *costs,
   case N: {                                                                                       \
     size_t chunks = count * (N * N / 16);                                                         \
     unsigned grid = stream_grid(chunks, (threads / 64) * 64 * U, (unsigned)tuning("sad_wgs_per_cu", 256)); \
-    hipLaunchKernelGGL((sad_nxn_kernel<N, U, DUAL>), dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
+    launch_carried(sad_nxn_kernel<N, U, DUAL>, dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
   } break;
   switch (n) {
     KVZ_SAD_CASE(4, 4)
@@ -739,19 +739,19 @@ static int launch_satd(int n, const u8 *a, const u8 *b, size_t count, u32 *costs
   const unsigned threads = 256;
   switch (n) {
     case 4:
-      if (!DUAL) hipLaunchKernelGGL((satd4_kernel<4>), dim3(stream_grid(count, threads * 4)), dim3(threads), 0, st, a, b, costs, count);
-      else hipLaunchKernelGGL((satd_4x4_kernel<DUAL>), dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
+      if (!DUAL) launch_carried(satd4_kernel<4>, dim3(stream_grid(count, threads * 4)), dim3(threads), 0, st, a, b, costs, count);
+      else launch_carried(satd_4x4_kernel<DUAL>, dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
     case 8:
-      if (!DUAL) hipLaunchKernelGGL((satd8_kernel<4>), dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
-      else hipLaunchKernelGGL((satd_nxn_kernel<8, DUAL>), dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
+      if (!DUAL) launch_carried(satd8_kernel<4>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
+      else launch_carried(satd_nxn_kernel<8, DUAL>, dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
     case 16:
-      if (!DUAL) hipLaunchKernelGGL((satd16_kernel<4>), dim3(stream_grid(count * 16, threads * 4)), dim3(threads), 0, st, a, b, costs, count);
-      else hipLaunchKernelGGL((satd_nxn_kernel<16, DUAL>), dim3(stream_grid(count * 4, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
+      if (!DUAL) launch_carried(satd16_kernel<4>, dim3(stream_grid(count * 16, threads * 4)), dim3(threads), 0, st, a, b, costs, count);
+      else launch_carried(satd_nxn_kernel<16, DUAL>, dim3(stream_grid(count * 4, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
-    case 32: hipLaunchKernelGGL((satd_nxn_kernel<32, DUAL>), dim3(stream_grid(count * 16, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is); break;
-    case 64: hipLaunchKernelGGL((satd_nxn_kernel<64, DUAL>), dim3(stream_grid(count * 64, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is); break;
+    case 32: launch_carried(satd_nxn_kernel<32, DUAL>, dim3(stream_grid(count * 16, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is); break;
+    case 64: launch_carried(satd_nxn_kernel<64, DUAL>, dim3(stream_grid(count * 64, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is); break;
     default: return kvzhip::invalid_arg("kvz_hip_satd_nxn_batch / kvz_hip_satd_nxn_dual_batch (n must be 4, 8, 16, 32 or 64)");
   }
   KVZ_CHECK_LAUNCH("satd_nxn_kernel");
