@@ -1363,8 +1363,9 @@ typedef struct {
  *   other SCUs are left untouched; the host clears the array once, as it does cbf_out.
  * Equals the reference where cfg.trskip_enable is set and state->qp < cfg.fast_residual_cost_limit (--fast-residual-cost N) holds
  *   for every LCU.  At or above the limit the reference prices coefficients with CABAC on the live context state
- *   (get_coeff_cabac_cost), which is OUT OF SCOPE, as are RDOQ and the transform-skip term of the intra rough
- *   search (search_intra.c:105-167).  Lossless coding switches transform skip off (encoder.c:623-628) and has entries of its own:
+ *   (get_coeff_cabac_cost): kvz_hip_inter_residual_frame_ts_cabac and kvz_hip_intra_recon_frame_ts_cabac (below) are these entries
+ *   with that rule, and kvz_hip_coeff_cost_batch is the count for any TU of the coefficient arrays they write.  OUT OF SCOPE: RDOQ
+ *   and the transform-skip term of the intra rough search (search_intra.c:105-167).  Lossless coding switches transform skip off (encoder.c:623-628) and has entries of its own:
  *   kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below).
  * Errors: ts != NULL with tr_skip_out == NULL, with bit_cost < 0 while lcu_bit_cost == NULL, or with lcu_bit_cost not 4-byte
  *   aligned returns KVZ_HIP_ERR_INVALID and nothing is written; so does every error of the _sl entry.
@@ -1384,6 +1385,120 @@ KVZ_HIP_API int kvz_hip_intra_recon_frame_ts(const kvz_hip_ref_picture *src, kvz
                                              const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
                                              const kvz_hip_scaling_tables *tables, const kvz_hip_trskip *ts, uint8_t *tr_skip_out,
                                              const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Coefficient pricing with CABAC: the counting coder                  */
+/*   reference: get_coeff_cabac_cost (rdo.c:158-197), the branch of    */
+/*   kvz_get_coeff_cost (rdo.c:208-222) at or above                    */
+/*   cfg.fast_residual_cost_limit -- the default, the limit being 0    */
+/*   (cfg.c:82) -- over kvz_encode_coeff_nxn in counting mode          */
+/*   (encode_coding_tree.c:49-345) with context.c:303-385 and          */
+/*   cabac.c:91-282                                                    */
+/* ------------------------------------------------------------------ */
+/* What the counting coder reads of state->cabac (cabac.h:41-88).  The count (23 - bits_left) + 8 * num_buffered_bytes is the number
+ * of renormalisation shifts plus the number of bypass bins: a function of `range` and these context bytes, never of `low`.
+ * range: cabac.range, 256..510.
+ * ctx[0..135]: the 136 contiguous bytes of cabac_data_t.ctx from cu_sig_coeff_group_model[0] through cu_abs_model_chroma[1], in
+ *   the reference's order (one memcpy from &cabac.ctx.cu_sig_coeff_group_model[0]); ctx[136] / ctx[137]:
+ *   transform_skip_model_luma / _chroma; ctx[138..139]: spare, not read.
+ * Bytes are uc_state (state << 1 | mps).  The result is specified for 0..125, the values the reference's coder produces; any other
+ *   value is read as (value >> 1) & 63 for the state and cannot cause an access outside a table. */
+typedef struct {
+  uint16_t range;
+  uint16_t reserved;
+  uint8_t ctx[140];
+} kvz_hip_coeff_ctx;            /* 144 bytes; DEVICE array, 2-byte aligned */
+
+/* One TU of kvz_hip_coeff_cost_batch.
+ * offset: in coefficients from `coeffs`, to width * width contiguous row-major values; a multiple of 4 (the reference reads four
+ *   coefficients at a time).  A TU of the picture chain's coeff_y / coeff_u / coeff_v arrays is addressed by its z-order offset
+ *   (LCU * 4096 or 1024 + 16 * z-order index of its first 4x4 block) unchanged.
+ * width: 4 / 8 / 16 / 32.  type: 0 (luma) or 2 (chroma), the reference's `type`, which also indexes
+ *   cu_sig_coeff_group_model[type].  scan_mode: 0 (diagonal), 1 (horizontal), 2 (vertical), 1 and 2 only at width <= 8:
+ *   kvz_get_scan_order produces nothing else.  tr_skip: 0 / 1, the value of the transform_skip_flag bin that is coded at width 4
+ *   with trskip_enable (kvz_get_coeff_cost passes 0, rdo.c:194).  ctx_index: the TU's set in ctx_sets. */
+typedef struct {
+  uint32_t offset;
+  uint8_t width, type, scan_mode, tr_skip;
+  uint32_t ctx_index;
+} kvz_hip_coeff_cost_desc;      /* 12 bytes; DEVICE array, 4-byte aligned */
+
+typedef struct {
+  int32_t signhide;             /* cfg.signhide_enable */
+  int32_t trskip_enable;        /* cfg.trskip_enable */
+  int32_t lossless;             /* cfg.lossless: no sign is hidden (encode_coding_tree.c:261-262) */
+  int32_t reserved;
+} kvz_hip_coeff_cost_params;    /* 16 bytes; HOST struct, copied at the call */
+
+/* bits_out[i] = get_coeff_cabac_cost of TU descs[i] (rdo.c:158-197): 0 when all its coefficients are zero, else the bits that
+ * kvz_encode_coeff_nxn produces in counting mode, started from range and contexts of ctx_sets[descs[i].ctx_index].  A set is never
+ * written: every TU is priced on a private copy, as the reference copies its state (rdo.c:177-178), so the result does not depend
+ * on the order or the grouping of the descriptors.  Every branch that counting mode reaches is covered: the transform_skip_flag
+ * bin, the last position's prefixes and suffixes with x and y swapped for the vertical scan, coded_sub_block_flag with its inferred
+ * first and last cases, sig_coeff_flag with kvz_context_calc_pattern_sig_ctx / kvz_context_get_sig_ctx_inc and the inferred flag,
+ * the greater-1 run with c1 and ctx_set, the one greater-2 flag, the signs with sign hiding, and kvz_cabac_write_coeff_remain with
+ * the Rice parameter capped at 4.  The crypto branches are not reached in counting mode.
+ * coeffs (8-byte aligned), descs, ctx_sets and bits_out (4-byte aligned) are DEVICE; params is HOST.
+ * A descriptor outside the rules above, or with ctx_index >= n_sets, is skipped and its bits_out left untouched.
+ * Errors (KVZ_HIP_ERR_INVALID, nothing written): a missing pointer with n > 0, n_sets == 0, a misaligned array, n above 2^31 - 1.
+ *   n == 0 is KVZ_HIP_OK and nothing is looked at.
+ * Launches and capture: two launches (the 4x4 TUs a lane each, the larger ones a wave each), asynchronous on s, no work memory,
+ *   no allocation, no synchronisation with the host; usable between kvz_hip_graph_begin / _end, and a captured call may be
+ *   replayed after the CONTENTS of coeffs, descs and ctx_sets changed.  The ABI version stays 4.
+ * This is the coeff_bits term of kvz_cu_rd_cost_luma / _chroma (search.c:300, :369-370) as the reference computes it by default;
+ *   the chain's coeff_abs_* sums are that term only under --fast-residual-cost.  OUT OF SCOPE: RDOQ (its lambda, error_scale and
+ *   full state have no reachable reference entry), the transform-tree flag bits of the rd cost and the intra rough search's
+ *   transform-skip term.
+ * Any `range` and any context byte is memory-safe: range is used as (range >> 6) & 3 where it indexes, a byte as (byte >> 1) & 63.
+ * Both launches run over the whole list whatever its mix and pass over the other class's descriptors, which costs a descriptor
+ *   read each; a caller with many TUs of one class loses nothing by sorting them into calls of their own. */
+KVZ_HIP_API int kvz_hip_coeff_cost_batch(const kvz_hip_coeff *coeffs, const kvz_hip_coeff_cost_desc *descs, size_t n,
+                                         const kvz_hip_coeff_ctx *ctx_sets, uint32_t n_sets,
+                                         const kvz_hip_coeff_cost_params *params, uint32_t *bits_out, kvz_hip_stream s);
+
+/* How the two transform-skip stages price coefficients when the reference does it with CABAC.
+ * ctx_sets: DEVICE, n_sets records, 2-byte aligned.  lcu_ctx: DEVICE, optional, 2-byte aligned: one set index per LCU in picture
+ *   raster order; NULL means set 0 everywhere.  The search of an LCU runs on the state the previous LCU's coding left, so a set per
+ *   LCU is the reference's granularity.  An index >= n_sets is used as n_sets - 1: nothing is read outside the table.
+ * fast_limit: cfg.fast_residual_cost_limit (--fast-residual-cost N; 0 by default, cfg.c:82). */
+typedef struct {
+  const kvz_hip_coeff_ctx *ctx_sets;
+  uint32_t n_sets;
+  int32_t fast_limit;
+  const uint16_t *lcu_ctx;
+} kvz_hip_coeff_pricing;        /* 24 bytes; HOST struct, copied at the call */
+
+/* kvz_hip_inter_residual_frame_ts and kvz_hip_intra_recon_frame_ts with one more argument, placed before params: the pricing rule of
+ * kvz_get_coeff_cost (rdo.c:208-222) as the reference applies it inside kvz_quantize_residual_trskip (transform.c:229-276).
+ * pricing == NULL: the call IS the _ts entry, byte for byte (it calls it, and that entry names itself in kvz_hip_last_error).
+ * Otherwise everything of the _ts contract holds except coeff_cost of a trial, which becomes per TU the rule of rdo.c:214:
+ *   if the QP of the TU's LCU (the clamped lcu_qp value, or params->qp) is >= fast_limit, coeff_cost is get_coeff_cabac_cost
+ *   (rdo.c:158-197) of the trial's 16 coefficients -- the count kvz_hip_coeff_cost_batch returns -- on the LCU's set, with type 0,
+ *   the TU's scan order (diagonal in the inter entry, kvz_get_scan_order of the intra mode in the intra entry), signhide from
+ *   params, trskip_enable 1, lossless 0 and the transform_skip_flag bin 0 for BOTH trials (rdo.c:188-194 passes 0 whatever the
+ *   trial is); a trial without coefficients costs 0 bits.  Otherwise coeff_cost is the estimate, as in the _ts entry.
+ *   Cost, tie rule, winner, tr_skip_out, cbf, costs, launch count and capture rules are exactly the _ts entry's; a captured call
+ *   may also be replayed after the CONTENTS of ctx_sets and lcu_ctx changed.
+ * Errors beyond the _ts entry's (KVZ_HIP_ERR_INVALID, nothing written): pricing != NULL with ts == NULL, with ctx_sets == NULL or
+ *   not 2-byte aligned, with n_sets == 0, or with a misaligned lcu_ctx.
+ * The multi-picture _frames_ts entries take no pricing yet.  OUT OF SCOPE: RDOQ, the transform-tree flag bits of the rd cost and
+ *   the transform-skip term of the intra rough search.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame_ts_cabac(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                      kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c,
+                                                      kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                                      kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                                      const int8_t *lcu_qp, const kvz_hip_scaling_tables *tables,
+                                                      const kvz_hip_trskip *ts, uint8_t *tr_skip_out,
+                                                      const kvz_hip_coeff_pricing *pricing,
+                                                      const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frame_ts_cabac(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
+                                                   kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
+                                                   const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
+                                                   kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
+                                                   const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
+                                                   const kvz_hip_scaling_tables *tables, const kvz_hip_trskip *ts, uint8_t *tr_skip_out,
+                                                   const kvz_hip_coeff_pricing *pricing,
+                                                   const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* Lossless coding in the picture chain: residual and intra stages     */

@@ -163,6 +163,16 @@ class HashPlane(C.Structure):
     _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class CoeffCostParams(C.Structure):
+    """kvz_hip_coeff_cost_params"""
+    _fields_ = [("signhide", C.c_int32), ("trskip_enable", C.c_int32), ("lossless", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CoeffPricing(C.Structure):
+    """kvz_hip_coeff_pricing"""
+    _fields_ = [("ctx_sets", C.c_void_p), ("n_sets", C.c_uint32), ("fast_limit", C.c_int32), ("lcu_ctx", C.c_void_p)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -269,6 +279,10 @@ SIGNATURES = {
     "kvz_hip_inter_residual_frame_ts": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P, _P, _P]),
     "kvz_hip_intra_recon_frame_ts": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P,
                                           _P, _P]),
+    "kvz_hip_inter_residual_frame_ts_cabac": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip), _P,
+                                                   C.POINTER(CoeffPricing), _P, _P]),
+    "kvz_hip_intra_recon_frame_ts_cabac": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip),
+                                                _P, C.POINTER(CoeffPricing), _P, _P]),
     "kvz_hip_inter_residual_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_intra_recon_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_inter_residual_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
@@ -284,6 +298,7 @@ SIGNATURES = {
     "kvz_hip_picture_hash_frames": (_I, [C.POINTER(HashPicture), _I, _P]),
     "kvz_hip_array_checksum_blocks": (_SZ, [_I, _I]),
     "kvz_hip_array_checksum_batch": (_I, [C.POINTER(HashPlane), _I, _P, _P, _P]),
+    "kvz_hip_coeff_cost_batch": (_I, [_P, _P, _SZ, _P, _U, C.POINTER(CoeffCostParams), _P, _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -790,7 +790,7 @@ TRSKIP = np.dtype([("bit_cost", "<i4"), ("reserved", "<i4"), ("lcu_bit_cost", "<
 
 
 def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                         trskip=None, tr_skip=None, scaling=None):
+                         trskip=None, tr_skip=None, pricing=None, scaling=None):
     """kvz_hip_inter_residual_frame.  src: (y, u, v) uint8 planes of the source picture (its luma shape is the picture size;
     u, v None for 4:0:0); pred: (y, u, v) planes holding the prediction, at least as large (a wider array gives a stride);
     cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
@@ -800,23 +800,28 @@ def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhid
     scaling: the pair of packed arrays of pack_scaling_tables -> kvz_hip_inter_residual_frame_sl (with or without lcu_qp).
     trskip: the bit cost of transform skip, (int)(lambda + 0.5) as one int or as an int32 array [LCUs] in raster order ->
     kvz_hip_inter_residual_frame_ts (with or without lcu_qp and scaling); the dict gains tr_skip, uint8 [height / 4, width / 4].
-    tr_skip: optional initial contents of that array (default zeros)."""
+    tr_skip: optional initial contents of that array (default zeros).
+    pricing (with trskip): dict(sets=COEFF_CTX [m], fast_limit=int, lcu_ctx=uint16 [LCUs] or None) -> kvz_hip_inter_residual_frame_ts_cabac:
+    a trial is priced with CABAC on its LCU's set where the LCU's QP is at or above fast_limit.  An empty dict: that entry with
+    pricing == NULL."""
     return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, scaling=scaling,
-                           trskip=trskip, tr_skip=tr_skip)
+                           trskip=trskip, tr_skip=tr_skip, pricing=pricing)
 
 
 def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                      tiles=None, trskip=None, tr_skip=None, scaling=None):
+                      tiles=None, trskip=None, tr_skip=None, pricing=None, scaling=None):
     """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
     intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
     dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp.  tiles: a TILE_GRID record ->
     kvz_hip_intra_recon_frame_tiles (with or without lcu_qp).  scaling: the pair of packed arrays of pack_scaling_tables ->
     kvz_hip_intra_recon_frame_sl (with or without lcu_qp and tiles).  trskip, tr_skip: as in inter_residual_frame ->
-    kvz_hip_intra_recon_frame_ts (with or without lcu_qp, tiles and scaling)."""
+    kvz_hip_intra_recon_frame_ts (with or without lcu_qp, tiles and scaling).  pricing: as in inter_residual_frame ->
+    kvz_hip_intra_recon_frame_ts_cabac."""
     cus = np.ascontiguousarray(cus)
     modes = np.ascontiguousarray(modes, dtype=np.uint8)
     assert modes.shape == cus.shape + (2,)
-    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling, trskip, tr_skip)
+    return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling, trskip, tr_skip,
+                           pricing)
 
 
 class _StagedPicture:
@@ -867,7 +872,7 @@ class _StagedPicture:
 
 
 def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None, scaling=None,
-                    trskip=None, tr_skip=None):
+                    trskip=None, tr_skip=None, pricing=None):
     """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries; tiles given (intra only): the
     _tiles entry; scaling given: the _sl entries, the packed arrays uploaded for the call; trskip given: the _ts entries"""
     L = _lib.init()
@@ -887,6 +892,7 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
         tail = (dq.ptr,) + tail
     dqp = dq.ptr if lcu_qp is not None else None
     dts = None
+    assert pricing is None or trskip is not None
     if trskip is not None:
         ts = _lib.TrSkip(0, 0, None)
         if np.ndim(trskip) == 0:
@@ -897,7 +903,26 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
         tsk = np.zeros(cus.shape, np.uint8) if tr_skip is None else np.ascontiguousarray(tr_skip, dtype=np.uint8).reshape(cus.shape)
         dts = DeviceBuffer.from_numpy(tsk)
         g = _grid(tiles) if tiles is not None else None
-        if modes is None:
+        if pricing is not None:
+            # the _ts_cabac entries: the sets and the optional index per LCU uploaded for the call
+            pr_ref = None                                        # an empty dict: the entries with pricing == NULL
+            if pricing:
+                sets = np.ascontiguousarray(pricing["sets"], dtype=COEFF_CTX).ravel()
+                dsets = DeviceBuffer.from_numpy(sets)
+                dlc = None
+                if pricing.get("lcu_ctx") is not None:
+                    dlc = DeviceBuffer.from_numpy(np.ascontiguousarray(pricing["lcu_ctx"], dtype=np.uint16).reshape(lcu_count(width, height)))
+                pr = _lib.CoeffPricing(dsets.ptr, len(sets), int(pricing["fast_limit"]), dlc.ptr if dlc is not None else None)
+                pr_ref = C.byref(pr)
+            if modes is None:
+                assert tiles is None
+                check(L.kvz_hip_inter_residual_frame_ts_cabac(*planes, *outs, dqp, C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr,
+                                                              pr_ref, prm.ctypes.data, None), "inter_residual frame_ts_cabac")
+            else:
+                check(L.kvz_hip_intra_recon_frame_ts_cabac(*planes, st.dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None,
+                                                           C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr, pr_ref,
+                                                           prm.ctypes.data, None), "intra_recon frame_ts_cabac")
+        elif modes is None:
             assert tiles is None
             check(L.kvz_hip_inter_residual_frame_ts(*planes, *outs, dqp, C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr,
                                                     prm.ctypes.data, None), "inter_residual frame_ts")
@@ -1394,6 +1419,45 @@ def array_checksum_batch(planes):
     scratch, out = DeviceBuffer(4 * blocks), DeviceBuffer(4 * len(st))
     check(L.kvz_hip_array_checksum_batch(records, len(st), scratch.ptr, out.ptr, None), "array_checksum_batch")
     return out.to_numpy(np.uint32, (len(st),))
+
+
+# ---- coefficient pricing with CABAC ----
+COEFF_CTX = np.dtype([("range", "<u2"), ("reserved", "<u2"), ("ctx", "u1", (140,))])              # kvz_hip_coeff_ctx
+COEFF_COST_DESC = np.dtype([("offset", "<u4"), ("width", "u1"), ("type", "u1"), ("scan_mode", "u1"), ("tr_skip", "u1"),
+                            ("ctx_index", "<u4")])                                                # kvz_hip_coeff_cost_desc
+CABAC_CTX_BYTES = 184        # sizeof cabac_data_t.ctx (cabac.h:53-87)
+
+
+def coeff_ctx_from_dump(ctx184, cabac_range):
+    """A kvz_hip_coeff_ctx record cut from a dump of the reference's context block: the 184 bytes of cabac_data_t.ctx and
+    cabac.range.  Bytes 32..167 (cu_sig_coeff_group_model[0] .. cu_abs_model_chroma[1]) become ctx[0..135], bytes 182 / 183
+    (transform_skip_model_luma / _chroma) ctx[136] / ctx[137]."""
+    d = np.frombuffer(bytes(bytearray(ctx184)), dtype=np.uint8)
+    if d.size != CABAC_CTX_BYTES:
+        raise ValueError("a context dump is %d bytes, not %d" % (CABAC_CTX_BYTES, d.size))
+    if not 256 <= int(cabac_range) <= 510:
+        raise ValueError("cabac.range lies in 256..510")
+    rec = np.zeros((), dtype=COEFF_CTX)
+    rec["range"] = int(cabac_range)
+    rec["ctx"][:136] = d[32:168]
+    rec["ctx"][136:138] = d[182:184]
+    return rec
+
+
+def coeff_cost_batch(coeffs, descs, ctx_sets, signhide=1, trskip_enable=1, lossless=0, bits=None):
+    """kvz_hip_coeff_cost_batch.  coeffs: int16 array holding the TUs; descs [n] COEFF_COST_DESC; ctx_sets [m] COEFF_CTX.
+    bits: what bits_out holds before the call (a skipped descriptor keeps its value), zeros by default.  Returns uint32 [n]."""
+    L = _lib.init()
+    coeffs = np.ascontiguousarray(coeffs, dtype=np.int16).ravel()
+    descs = np.ascontiguousarray(descs, dtype=COEFF_COST_DESC)
+    ctx_sets = np.ascontiguousarray(ctx_sets, dtype=COEFF_CTX).ravel()
+    n = len(descs)
+    bits = np.zeros(n, dtype=np.uint32) if bits is None else np.ascontiguousarray(bits, dtype=np.uint32)
+    assert bits.shape == (n,)
+    d_c, d_d, d_s, d_b = (DeviceBuffer.from_numpy(a) for a in (coeffs, descs, ctx_sets, bits))
+    prm = _lib.CoeffCostParams(int(signhide), int(trskip_enable), int(lossless), 0)
+    check(L.kvz_hip_coeff_cost_batch(d_c.ptr, d_d.ptr, n, d_s.ptr, len(ctx_sets), C.byref(prm), d_b.ptr, None), "coeff_cost_batch")
+    return d_b.to_numpy(np.uint32, (n,))
 
 
 # ---- tile halo exchange: batched rectangle copies on device pointers ----

@@ -9,6 +9,7 @@
 #include "quant_core.h"
 #include "lcu_layout.h"
 #include "chain_host.h"
+#include "coeff_cabac_core.h"
 
 using namespace kvzhip;
 
@@ -140,6 +141,25 @@ __device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const
 // the trailing argument, or where the kernel takes none (several pictures) what it made of its picture's record
 __device__ __forceinline__ const ts_source &skip_or(const ts_source &m) { return m; }
 template <typename... P> __device__ __forceinline__ const ts_source &skip_or(const ts_source &, const lcu_qp_source &q, const P &...p) { return skip_of(q, p...); }
+// CABAC pricing of the two trials (kvz_hip_inter_residual_frame_ts_cabac) is one more trailing argument after the transform-skip source:
+// the context sets, a set index per LCU (or nullptr: set 0) and cfg.fast_residual_cost_limit.  Per TU the rule of rdo.c:214: at or
+// above the limit the price of a trial is get_coeff_cabac_cost of its 16 levels (coeff_cabac_core.h), below it the estimate.  The two
+// instantiations live in inter_residual_ts_cabac.hip; those above compile to the code they were.
+struct cabac_source { const kvz_hip_coeff_ctx *sets; const uint16_t *lcu_ctx; u32 n_sets; int fast_limit; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const ts_source &, const cabac_source &) { return q; }
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &, const ts_source &, const cabac_source &) { return q; }
+__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t, const ts_source &, const cabac_source &) { return t; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const ts_source &t, const cabac_source &) { return t; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const sl_source &, const ts_source &t, const cabac_source &) { return t; }
+__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const ts_source &, const cabac_source &c) { return c; }
+__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const sl_source &, const ts_source &, const cabac_source &c) { return c; }
+// a trial's levels in LDS rows of LD, and the TU's private context set interleaved over the workgroup's TUs
+struct cabac_lds_coeffs { const i16 *p; int ld; __device__ __forceinline__ int at(int x, int y) const { return p[y * ld + x]; } };
+template <int STRIDE> struct cabac_lds_ctx {
+  u8 *p;
+  __device__ __forceinline__ u32 get(int i) const { return p[i * STRIDE]; }
+  __device__ __forceinline__ void set(int i, u32 v) { p[i * STRIDE] = (u8)v; }
+};
 template <typename T, typename U> struct same_type { static constexpr bool value = false; };
 template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
 template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
@@ -154,8 +174,9 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
                                                                 int nx_y, int n_y, int nx_c, int n_c, PER_LCU... per_lcu)
 {
   constexpr bool MULTI = batch_of<ARGS>::multi, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl,
-                 TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts;
+                 TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts, CABAC = pack_has<cabac_source, PER_LCU...>;
   static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
+  static_assert(!CABAC || (TS && !MULTI), "CABAC pricing: the single-picture transform-skip launch only");
   constexpr int TPB = 256 / N, W4 = N / 4;
   constexpr int LD = lds_tile_ld(N);
   __shared__ __attribute__((aligned(16))) i16 sa[TPB * N * LD];     // residual / coefficients
@@ -409,8 +430,42 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
       const int v = ts.lcu_bit_cost ? ts.lcu_bit_cost[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)] : ts.bit_cost;
       bit_cost = (u32)max(v, 0);
     }
-    const u32 cost1 = group_sum<4>(ssd) + trskip_coeff_cost(group_sum<4>(sab), tu_qp) * bit_cost;
-    const u32 cost2 = group_sum<4>(ssd2) + trskip_coeff_cost(group_sum<4>(sab2), tu_qp) * bit_cost;
+    [[maybe_unused]] u32 price1 = 0, price2 = 0;
+    if constexpr (CABAC) {
+      price1 = trskip_coeff_cost(group_sum<4>(sab), tu_qp);
+      price2 = trskip_coeff_cost(group_sum<4>(sab2), tu_qp);
+      // rdo.c:214 per TU.  The transformed trial's levels go to the transform scratch, the skipped trial's are in tq; the TU's first
+      // thread prices one after the other, each on a fresh copy of its LCU's set, which the TU's four threads make.  Every thread
+      // of the workgroup runs the barriers; a slot that is no luma TU, or whose LCU lies below the limit, copies and prices nothing
+      __shared__ u8 s_cabac[kvzhip::CC_CTX_USED * TPB];
+      const cabac_source &cb = cabac_of(per_lcu...);
+      const bool on = valid && plane == 0 && tu_qp >= cb.fast_limit;
+      const kvz_hip_coeff_ctx *set = cb.sets;
+      if (on) {
+        const u32 want = cb.lcu_ctx ? (u32)cb.lcu_ctx[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)] : 0u;
+        set += min(want, cb.n_sets - 1u);                                     // an index beyond the table is its last set
+      }
+      *(u32 *)(tb + row * LD) = q1.x;
+      *(u32 *)(tb + row * LD + 2) = q1.y;
+      const kvzhip::coeff_cabac_flags fl = { k.signhide != 0, true, false };
+      u32 bits[2] = { 0u, 0u };
+#pragma unroll
+      for (int trial = 0; trial < 2; ++trial) {
+        if (on)
+          for (int i = row; i < kvzhip::CC_CTX_USED; i += 4) s_cabac[i * TPB + tu] = set->ctx[i];
+        __syncthreads();
+        if (on && row == 0) {
+          const cabac_lds_coeffs cf = { trial ? tq : tb, LD };
+          const cabac_lds_ctx<TPB> ctx = { s_cabac + tu };
+          bits[trial] = kvzhip::coeff_cabac_count(cf, ctx, set->range, 2, 0, 0, 0u, fl, (trial ? has2 : has) ? 1ull : 0ull);   // inter: diagonal
+        }
+        __syncthreads();
+      }
+      const u32 b1 = group_sum<4>(bits[0]), b2 = group_sum<4>(bits[1]);
+      if (on) { price1 = b1; price2 = b2; }
+    }
+    const u32 cost1 = group_sum<4>(ssd) + (CABAC ? price1 : trskip_coeff_cost(group_sum<4>(sab), tu_qp)) * bit_cost;
+    const u32 cost2 = group_sum<4>(ssd2) + (CABAC ? price2 : trskip_coeff_cost(group_sum<4>(sab2), tu_qp)) * bit_cost;
     const bool skip = plane == 0 && cost1 > cost2;
     if (skip) {
       has = has2; ssd = ssd2; sab = sab2; keep[0] = o2;
@@ -501,12 +556,12 @@ void launch_width(int n, const resid_args &a, const quant_consts &ky, const quan
 // the three entries: lcu_qp == nullptr is one QP per call (params->qp).  SL: the entry with scaling lists, tables required and checked;
 // it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only.  TS: the 4x4 launch
 // takes *skip (checked by the caller); the launches of the other sizes are those of the entry without it
-template <bool SL, bool TS = false>
+template <bool SL, bool TS = false, bool CABAC = false>
 int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                    kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
                    kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
                    const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s,
-                   const ts_source *skip = nullptr)
+                   const ts_source *skip = nullptr, const cabac_source *price = nullptr)
 {
   if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, costs, params, false, SL))
     return kvzhip::invalid_arg(entry);
@@ -539,15 +594,17 @@ int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pi
       const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
       const sl_source lists = { tables->quant, tables->dequant, params->qp };
       if constexpr (TS) {
-        if (n == 4) launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip);
-        else launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+        if (n != 4) launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+        else if constexpr (CABAC) launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip, *price);
+        else launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip);
       } else {
         launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
       }
     } else if (TS && n == 4) {
       if constexpr (TS) {
         const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
-        launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip);
+        if constexpr (CABAC) launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip, *price);
+        else launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip);
       }
     } else if (lcu_qp) {
       const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };

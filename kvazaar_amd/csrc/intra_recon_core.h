@@ -12,6 +12,7 @@
 #include "lcu_layout.h"
 #include "intra_core.h"
 #include "tile_grid.h"
+#include "coeff_cabac_core.h"
 
 using namespace kvzhip;
 
@@ -146,6 +147,14 @@ struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { r
 
 // what a 4x4 luma TU needs for the two trials of transform skip: state->qp and the bit cost of its LCU, and where the choice goes
 struct ts_lcu { int qp; u32 bit_cost; u8 *out; };
+// CABAC pricing of the two trials: the LCU's context set, and whether its QP is at or above cfg.fast_residual_cost_limit (rdo.c:214)
+struct cabac_lcu { const kvz_hip_coeff_ctx *set; bool on; };
+struct cabac_lds_coeffs { const i16 *p; int ld; __device__ __forceinline__ int at(int x, int y) const { return p[y * ld + x]; } };
+struct cabac_lds_ctx {
+  u8 *p;
+  __device__ __forceinline__ u32 get(int i) const { return p[i]; }
+  __device__ __forceinline__ void set(int i, u32 v) { p[i] = (u8)v; }
+};
 
 // One leaf TU, N wide, by the whole wave.  Called under wave-uniform conditions only.  TILES: tr stands for the picture in everything
 // about the TU's neighbours; without it tr is not read, and the code is compiled from the expressions it always had.  SL: k carries the
@@ -156,11 +165,14 @@ struct ts_lcu { int qp; u32 bit_cost; u8 *out; };
 // kvz_itransformskip.  They meet once, after the reconstruction: each quad sums its SSD and |coeff|, prices its trial, reads the
 // other quad's cost through a lane exchange, and the lanes of the trial that stands write the tile, the coefficients and the flags.
 // The lanes beyond 8 repeat lane % 8.  A chroma TU of the same kernel is coded as without TS.
-template <int N, bool TILES, bool SL = false, bool TS = false, typename ARGS>
+// CABAC (with TS): where the LCU's QP is at or above the limit, a trial's price is get_coeff_cabac_cost of its 16 levels
+// (coeff_cabac_core.h) instead of the estimate: the first lane of each trial's quad counts on a copy of the LCU's set of its own.
+template <int N, bool TILES, bool SL = false, bool TS = false, bool CABAC = false, typename ARGS>
 __device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
-                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq, const ts_lcu ts = {})
+                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq, const ts_lcu ts = {}, const cabac_lcu cb = {})
 {
   static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
+  static_assert(!CABAC || TS, "CABAC pricing belongs to the transform-skip decision");
   constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5, LD = lds_tile_ld(N), W4 = N / 4;
   const int lane = threadIdx.x, row = lane & (N - 1);
   bool own = lane < N;                                           // the lanes that touch global memory
@@ -403,7 +415,29 @@ __device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const t
     // transform.c:244-266: uint32 costs, the transformed trial wins ties.  The lanes of the trial that stands go on as the TU's lanes
     bool stands = true;
     if (dual) {
-      const u32 cost = group_sum<4>(ssd) + trskip_coeff_cost(group_sum<4>(sab), ts.qp) * ts.bit_cost;
+      [[maybe_unused]] u32 price = 0;
+      if constexpr (CABAC) {
+        price = trskip_coeff_cost(group_sum<4>(sab), ts.qp);
+        if (cb.on) {                                                           // wave-uniform, as dual is
+          __shared__ u8 s_cabac[2][kvzhip::CC_CTX_USED + 2];
+          for (int i = lane; i < kvzhip::CC_CTX_USED; i += 64) {
+            const u8 v = cb.set->ctx[i];
+            s_cabac[0][i] = v;
+            s_cabac[1][i] = v;
+          }
+          __syncthreads();
+          u32 bits = 0;
+          if (lane < 8 && (lane & 3) == 0) {
+            const cabac_lds_coeffs cf = { tq, LD };                            // tq is the lane's own trial's rows
+            const cabac_lds_ctx ctx = { s_cabac[trial] };
+            const kvzhip::coeff_cabac_flags fl = { k.signhide != 0, true, false };
+            bits = kvzhip::coeff_cabac_count(cf, ctx, cb.set->range, 2, 0, t.scan, 0u, fl, has ? 1ull : 0ull);
+          }
+          price = (u32)__shfl((int)bits, lane & 4, 64);                        // the lanes beyond 8 repeat lane % 8
+          __syncthreads();
+        }
+      }
+      const u32 cost = group_sum<4>(ssd) + (CABAC ? price : trskip_coeff_cost(group_sum<4>(sab), ts.qp)) * ts.bit_cost;
       const u32 other = (u32)__shfl_xor((int)cost, 4, 64);
       stands = trial ? cost < other : cost <= other;
     }
@@ -483,6 +517,19 @@ __host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_sou
 __device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l, const ts_source &) { return l; }
 __device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const ts_source &t) { return t; }
 __device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &t) { return t; }
+// CABAC pricing of the two trials (kvz_hip_intra_recon_frame_ts_cabac) is one more trailing argument after the transform-skip source:
+// the context sets, a set index per LCU (or nullptr: set 0) and cfg.fast_residual_cost_limit.  The workgroup picks its LCU's set
+// once, next to the QP.  Two instantiations in a translation unit of their own (intra_recon_ts_cabac.hip).
+struct cabac_source { const kvz_hip_coeff_ctx *sets; const uint16_t *lcu_ctx; u32 n_sets; int fast_limit; };
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const ts_source &, const cabac_source &) { return q; }
+__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &, const ts_source &, const cabac_source &) { return q; }
+__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const ts_source &, const cabac_source &) { return t; }
+__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &, const ts_source &, const cabac_source &) { return t; }
+__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l, const ts_source &, const cabac_source &) { return l; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const ts_source &t, const cabac_source &) { return t; }
+__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &t, const cabac_source &) { return t; }
+__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const tile_source &, const ts_source &, const cabac_source &c) { return c; }
+__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &, const cabac_source &c) { return c; }
 template <typename T, typename U> struct same_type { static constexpr bool value = false; };
 template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
 template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
@@ -505,7 +552,8 @@ template <typename ARGS, typename... PER_LCU>
 __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, PER_LCU... per_lcu)
 {
   constexpr bool MULTI = batch_of<ARGS>::multi, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2 || batch_of<ARGS>::tiles,
-                 SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl, TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts;
+                 SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl, TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts,
+                 CABAC = pack_has<cabac_source, PER_LCU...>;
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -602,6 +650,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
 
   lcu_sets<LCU_QP> own;                                                      // the LCU's own sets, [log2 N - 2]
   [[maybe_unused]] ts_lcu skip = {};
+  [[maybe_unused]] cabac_lcu price = {};
   if constexpr (MULTI) {
     // the array's value clamped as in the per-LCU entry, or the picture's QP as it stands as in the one-QP entry
     const int qp = (int)__builtin_amdgcn_readfirstlane((u32)(a.lcu_qp ? clip_lcu_qp((int)a.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]) : a.qp));
@@ -629,6 +678,11 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
       const ts_source &ts = skip_of(per_lcu...);
       const int v = (int)__builtin_amdgcn_readfirstlane((u32)(ts.lcu_bit_cost ? ts.lcu_bit_cost[(size_t)lcu_y * a.lcus_x + lcu_x] : ts.bit_cost));
       skip = { qp, (u32)max(v, 0), ts.tr_skip_out };
+    }
+    if constexpr (CABAC) {
+      const cabac_source &cb = cabac_of(per_lcu...);
+      const u32 want = __builtin_amdgcn_readfirstlane(cb.lcu_ctx ? (u32)cb.lcu_ctx[(size_t)lcu_y * a.lcus_x + lcu_x] : 0u);
+      price = { cb.sets + min(want, cb.n_sets - 1u), qp >= cb.fast_limit };   // an index beyond the table is its last set
     }
   }
 
@@ -662,6 +716,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
     if (n == 32) intra_tu<32, TILES, SL>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 16) intra_tu<16, TILES, SL>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 8) intra_tu<8, TILES, SL>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);
+    else if constexpr (CABAC) intra_tu<4, TILES, SL, TS, true>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq, skip, price);
     else intra_tu<4, TILES, SL, TS>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq, skip);
   }
 

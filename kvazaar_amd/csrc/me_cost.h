@@ -2,28 +2,14 @@
 // and the merge list, from the exp-Golomb lengths or, with --mv-rdo, from the CABAC model; and fracmv_within_tile.
 #pragma once
 #include "kvz_hip_internal.h"
+#include "cabac_tables.h"
 
 namespace kvzhip {
 
 // calc_mvd_cost / fracmv_within_tile on the flattened encoder state (include/kvz_hip.h).  The descriptor is copied
 // into (scalar) registers once per PU: the cost model runs for every one of the ~60 candidates of a search, and
 // reading the merge list from memory each time made scalar loads the longest chain of the kernel.
-// --mv-rdo: the CABAC probability tables of ITU-T H.265 (Tables 9-46 rangeTabLps, 9-47 transIdxLps) -- the reference's
-// kvz_g_auc_lpst_table / kvz_g_auc_next_state_lps (cabac.c:28-75); an MPS moves to min(state + 1, 62); the
-// renormalisation shift kvz_g_auc_renorm_table[lps >> 3] is clz(lps >> 3) - 26
-static __constant__ unsigned char c_range_lps[64 * 4] = {
-  128,176,208,240, 128,167,197,227, 128,158,187,216, 123,150,178,205, 116,142,169,195, 111,135,160,185, 105,128,152,175, 100,122,144,166,
-   95,116,137,158,  90,110,130,150,  85,104,123,142,  81, 99,117,135,  77, 94,111,128,  73, 89,105,122,  69, 85,100,116,  66, 80, 95,110,
-   62, 76, 90,104,  59, 72, 86, 99,  56, 69, 81, 94,  53, 65, 77, 89,  51, 62, 73, 85,  48, 59, 69, 80,  46, 56, 66, 76,  43, 53, 63, 72,
-   41, 50, 59, 69,  39, 48, 56, 65,  37, 45, 54, 62,  35, 43, 51, 59,  33, 41, 48, 56,  32, 39, 46, 53,  30, 37, 43, 50,  29, 35, 41, 48,
-   27, 33, 39, 45,  26, 31, 37, 43,  24, 30, 35, 41,  23, 28, 33, 39,  22, 27, 32, 37,  21, 26, 30, 35,  20, 24, 29, 33,  19, 23, 27, 31,
-   18, 22, 26, 30,  17, 21, 25, 28,  16, 20, 23, 27,  15, 19, 22, 25,  14, 18, 21, 24,  14, 17, 20, 23,  13, 16, 19, 22,  12, 15, 18, 21,
-   12, 14, 17, 20,  11, 14, 16, 19,  11, 13, 15, 18,  10, 12, 15, 17,  10, 12, 14, 16,   9, 11, 13, 15,   9, 11, 12, 14,   8, 10, 12, 14,
-    8,  9, 11, 13,   7,  9, 11, 12,   7,  9, 10, 12,   7,  8, 10, 11,   6,  8,  9, 11,   6,  7,  9, 10,   6,  7,  8,  9,   2,  2,  2,  2 };
-static __constant__ unsigned char c_trans_lps[64] = {
-   0, 0, 1, 2, 2, 4, 4, 5, 6, 7, 8, 9, 9,11,11,12,13,13,15,15,16,16,18,18,19,19,21,21,22,22,23,24,
-  24,25,26,26,27,27,28,29,29,30,30,30,31,32,32,33,33,33,34,34,35,35,35,36,36,36,37,37,37,38,38,63 };
-
+// --mv-rdo: the CABAC probability tables are those of cabac_tables.h
 // what kvz_calc_mvd_cost_cabac reads of state->cabac, and the bits its counting-mode encoder produces: the count
 // (23 - bits_left) + 8 * num_buffered_bytes (cabac.c:95-140) is the number of renormalisation shifts, a function of `range`
 // and the context states alone

@@ -257,6 +257,50 @@ def main():
         inter_recon_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
     if not args.only or any(o in "picture_hash_frame_1080p picture_hash_frame_4k picture_hash_frames_1080p_x16 array_checksum_batch_1080p" for o in args.only.split(",")):
         picture_hash_rows(L, st, dev, max(args.rounds, 5))
+    if not args.only or any(o in "coeff_cost_batch_1080p_4x4 coeff_cost_batch_1080p_8x8 coeff_cost_batch_1080p_16x16 coeff_cost_batch_1080p_32x32" for o in args.only.split(",")):
+        coeff_cost_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+
+
+def coeff_cost_rows(L, st, dev, rounds, only, iters=10):
+    """The CABAC coefficient pricing: kvz_hip_coeff_cost_batch over the luma TUs of one 1080p picture (1920 x 1088) cut into TUs of one
+    size, every TU addressed in place, one context set per LCU.  The coefficients are what a quantiser leaves at a middling QP: levels
+    of -3..3 whose density falls off from the DC corner (about a third of a 4x4 TU's positions hold a level, a twentieth of a 32x32
+    TU's), one TU in six empty.  Device time by events, ms per call: median and min..max over the rounds, and ns per TU."""
+    import numpy as np
+    from kvazaar_amd import api
+    g = torch.Generator(device=dev); g.manual_seed(43)
+    W, H = 1920, 1088
+    lcus = api.lcu_count(W, H)
+    host = np.random.default_rng(43)
+    sets = np.zeros(lcus, dtype=api.COEFF_CTX)
+    sets["range"] = host.integers(256, 511, lcus)
+    sets["ctx"][:, :138] = host.integers(0, 126, (lcus, 138))
+    d_sets = torch.from_numpy(sets.view(np.uint8).reshape(-1).copy()).to(dev)
+    prm = _lib.CoeffCostParams(1, 1, 0, 0)
+    print("%-32s %9s %10s %18s %10s %10s" % ("kernel", "launches", "ms", "min..max ms", "TUs", "ns / TU"))
+    for n in (4, 8, 16, 32):
+        name = "coeff_cost_batch_1080p_%dx%d" % (n, n)
+        if not any(o in name for o in only):
+            continue
+        count = W * H // (n * n)
+        yy, xx = torch.meshgrid(torch.arange(n, device=dev), torch.arange(n, device=dev), indexing="ij")
+        keep = torch.exp(-(xx + yy).float() / (n / 4.0)).reshape(1, n * n)
+        level = torch.randint(-3, 4, (count, n * n), dtype=torch.int16, device=dev, generator=g)
+        level *= (torch.rand((count, n * n), device=dev, generator=g) < keep).to(torch.int16)
+        level *= (torch.rand((count, 1), device=dev, generator=g) < 5.0 / 6.0).to(torch.int16)
+        descs = np.zeros(count, dtype=api.COEFF_COST_DESC)
+        descs["offset"] = np.arange(count, dtype=np.int64) * n * n
+        descs["width"], descs["ctx_index"] = n, descs["offset"] // 4096
+        d_descs = torch.from_numpy(descs.view(np.uint8).reshape(-1).copy()).to(dev)
+        bits = torch.zeros(count, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+
+        def fn():
+            _lib.check(L.kvz_hip_coeff_cost_batch(level.data_ptr(), d_descs.data_ptr(), count, d_sets.data_ptr(), lcus, C.byref(prm), bits.data_ptr(), st), name)
+        t = [timed(L, st, fn, iters=iters, warm=2) for _ in range(rounds)]
+        ms = float(np.median(t))
+        print("%-32s %9d %10.4f %18s %10d %10.2f   mean %.1f bits / TU" % (name, 2, ms, "%.4f..%.4f" % (min(t), max(t)), count, ms * 1e6 / count,
+                                                                        float(bits.float().mean())))
 
 
 def picture_hash_rows(L, st, dev, rounds, iters=20):

@@ -30,6 +30,9 @@ entries, which then launch the kernels of the entries without lists -- the basel
 --transform-skip: both residual calls go through their *_ts entries with one bit cost, (int)(lambda + 0.5) at the frame's QP: every 4x4
 luma TU is coded transformed and transform-skipped and the cheaper trial is kept.  Combines with --lcu-qp, --tiles and --scaling-list
 (without --scaling-list the tables are NULL, as with `none`).
+--cabac-cost (with --transform-skip): the two residual calls go through their *_ts_cabac entries: every trial is priced as the reference
+does by default, with the CABAC counting coder on the context set of the TU's LCU (a set per LCU, fast_limit 0) instead of the estimate.
+Run with and without it for the cost of the pricing.
 --lossless: the picture chain of a frame coded with --lossless: prediction, then kvz_hip_inter_residual_frame_lossless and
 kvz_hip_intra_recon_frame_lossless (implicit_rdpcm on), one kernel launch each.  The quantising batches, the QP map, deblocking and SAO
 are left out: encoder.c:623-628 switches sign hiding, transform skip, deblocking and SAO off under --lossless.  Combines with --tiles
@@ -62,7 +65,7 @@ from kvazaar_amd._lib import QuantParams  # noqa: E402
 W, H = 1920, 1080
 
 
-def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, lossless=False, pictures=0):
+def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, lossless=False, pictures=0, cabac_cost=False):
     """-> {stage: [(name, units, launch(stream))]}, plus the tensors kept alive"""
     g = torch.Generator(device=dev); g.manual_seed(7)
     keep = []
@@ -264,6 +267,27 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
             ts = _lib.TrSkip(18, 0, None)
             rc_skip, ir_skip = (torch.zeros(ir_cus.shape, dtype=torch.uint8, device=dev) for _ in range(2))
             keep += [ts, rc_skip, ir_skip]
+            if cabac_cost:
+                # the reference's default pricing inside the decision: a context set per LCU, fast_limit 0 (cfg.c:82), so every
+                # trial of every 4x4 luma TU is priced with the counting coder
+                n_lcu = api.lcu_count(W, H)
+                host = np.random.default_rng(36)
+                cc_sets = np.zeros(n_lcu, dtype=api.COEFF_CTX)
+                cc_sets["range"] = host.integers(256, 511, n_lcu)
+                cc_sets["ctx"][:, :138] = host.integers(0, 126, (n_lcu, 138))
+                cc_sets_d, cc_idx_d = up(cc_sets.view(np.uint8).reshape(-1)), up(np.arange(n_lcu, dtype=np.uint16))
+                pricing = _lib.CoeffPricing(cc_sets_d.data_ptr(), n_lcu, 0, cc_idx_d.data_ptr())
+                keep += [cc_sets_d, cc_idx_d, pricing]
+                stages["tu"].append(("inter_residual_frame_ts_cabac", 1, lambda s: L.kvz_hip_inter_residual_frame_ts_cabac(
+                    rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
+                    rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
+                    C.byref(ts), rc_skip.data_ptr(), C.byref(pricing), ir_prm.ctypes.data, s)))
+                stages["tu"].append(("intra_recon_frame_ts_cabac", 1, lambda s: L.kvz_hip_intra_recon_frame_ts_cabac(
+                    ir_tab.ctypes.data, ir_rec[0].data_ptr(), W, ir_rec[1].data_ptr(), ir_rec[2].data_ptr(), W // 2, ir_cus_d.data_ptr(), ir_modes_d.data_ptr(),
+                    ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
+                    ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data if tiles else None, sl_ref, C.byref(ts), ir_skip.data_ptr(),
+                    C.byref(pricing), ir_prm.ctypes.data, s)))
+        if trskip and not cabac_cost:
             stages["tu"].append(("inter_residual_frame_ts", 1, lambda s: L.kvz_hip_inter_residual_frame_ts(
                 rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
                 rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
@@ -273,7 +297,7 @@ def build_stages(L, dev, lcu_qp=False, tiles=None, lists=None, trskip=False, los
                 ir_co[0].data_ptr(), ir_co[1].data_ptr(), ir_co[2].data_ptr(), ir_cbf.data_ptr() if lcu_qp else None, None,
                 ir_qp.data_ptr() if lcu_qp else None, grid.ctypes.data if tiles else None, sl_ref, C.byref(ts), ir_skip.data_ptr(),
                 ir_prm.ctypes.data, s)))
-        else:
+        elif not trskip:
             stages["tu"].append(("inter_residual_frame_sl", 1, lambda s: L.kvz_hip_inter_residual_frame_sl(
                 rc_src_tab.ctypes.data, rc_dst[0].data_ptr(), W, rc_dst[1].data_ptr(), rc_dst[2].data_ptr(), W // 2, rc_cus_d.data_ptr(),
                 rc_co[0].data_ptr(), rc_co[1].data_ptr(), rc_co[2].data_ptr(), None, None, ir_qp.data_ptr() if lcu_qp else None, sl_ref,
@@ -481,6 +505,8 @@ def main():
                     help="the *_sl entries of the inter residual coding and the intra reconstruction; `none`: with tables == NULL (the baseline)")
     ap.add_argument("--transform-skip", action="store_true",
                     help="the *_ts entries of the inter residual coding and the intra reconstruction, with one bit cost")
+    ap.add_argument("--cabac-cost", action="store_true",
+                    help="with --transform-skip: the *_ts_cabac entries, every trial priced with CABAC on its LCU's context set (fast_limit 0)")
     ap.add_argument("--lossless", action="store_true",
                     help="a frame coded with --lossless: prediction, then the two *_lossless entries; no QP map, deblocking or SAO, which "
                          "encoder.c:623-628 switches off with sign hiding and transform skip")
@@ -504,7 +530,9 @@ def main():
     s = L.kvz_hip_stream_create()
     side = [L.kvz_hip_stream_create() for _ in range(7)]
     events = [L.kvz_hip_event_create() for _ in range(8)]
-    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list, args.transform_skip, args.lossless, args.pictures)
+    if args.cabac_cost and (not args.transform_skip or args.pictures):
+        ap.error("--cabac-cost belongs to --transform-skip, one picture at a time")
+    stages, keep = build_stages(L, dev, args.lcu_qp, tiles, args.scaling_list, args.transform_skip, args.lossless, args.pictures, args.cabac_cost)
     torch.cuda.synchronize()
     n_launch = sum(len(v) for v in stages.values())
 
