@@ -148,6 +148,12 @@ int launch_dct32_mfma(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   // leg (1 029 120 blocks) the forward kernel confirmed that what it wants is ONE BLOCK PER WAVE at any size, not a number of
   // workgroups per CU: cap 192: 5.77, 384: 5.90, 768: 6.07, 1100 (no wave takes a second block): 6.14 TB/s -- so the forward cap only
   // bounds the grid for lists beyond 4 M blocks.
+  // Occupancy, measured and dropped: at one block per wave the kernel below still carries its two prefetch tiles and the loop
+  // (76 VGPRs, 6 waves per SIMD).  A form without them (45 VGPRs, 8 waves per SIMD, 176 instead of 202 vector instructions per
+  // wave) held 53 instead of 42 resident waves and did not run faster: 6.53 against 6.48 TB/s here, headline launch median
+  // 164.1 against 164.9 us with a run-to-run spread of 3 %; two adjacent tiles per wave with both loads issued first (66 VGPRs):
+  // 6.48 TB/s, 163.8 us; three: 6.30 TB/s (profiles/headline_kernels_ab.txt).  At 6.2 - 6.5 TB/s with as many bytes written as
+  // read the kernel runs at the rate of a plain copy on this device; more waves in flight do not raise it.
   const size_t cap = wg_cap(inverse ? tuning("idct32_wgs_per_cu", 96) : tuning("dct32_wgs_per_cu", 4096));
   if (wgs > cap) wgs = cap;
   if (tuning("dct_pipe", 0)) {

@@ -36,14 +36,30 @@ __device__ __forceinline__ u32 sad16(uint4 a, uint4 b)
   return sad_dword(a.w, b.w, s);
 }
 
+// A result of the 8x8 streaming cost kernels.  NT: stored with the nontemporal policy.  The wave's 64 results leave
+// the vector cache as four 64-byte write requests either way (rocprofv3 TCP_TCC_WRITE_REQ: 0.26 M per 4.19 M blocks,
+// profiles/headline_kernels_before.txt), so the lane order of the store is not what costs time.  The policy is: stored nontemporal, a
+// headline launch (4.1 M blocks, 16.6 MB of costs) is 3 us shorter of 84 (sad_8x8) and 2.6 of 88 (satd_8x8), and the 0.5 GiB
+// rows of tools/bench_all.py go from 6.42 to 6.74 and from 6.29 to 6.58 TB/s (profiles/headline_kernels_ab.txt).  16.6 MB at
+// HBM speed is 2.8 us: the gain is the size of writing the costs back once, which the default policy seems to leave to the
+// kernel's end, where nothing overlaps it (not shown by a counter).  At 16x16, with a quarter of the costs per byte read, the rows
+// do not move beyond their noise (sad +1.9 %, satd -1.7 %) and the store stays as it was.  "cost_store_nt" 0 selects the
+// default-policy store.
+template <bool NT>
+__device__ __forceinline__ void store_cost(u32 *costs, size_t blk, u32 v)
+{
+  if (NT) __builtin_nontemporal_store(v, costs + blk);
+  else costs[blk] = v;
+}
+
 // ---------------------------------------------------------------------------
 // sad_NxN over contiguous block pairs (picture-generic.c:460-486) and the dual
 // variant (:497-519).  A "chunk" is 16 bytes; a block has L = N*N/16 chunks.
 // Each wave streams 64*U consecutive chunks per iteration (1 KiB per load
 // instruction, U loads per array in flight), reduces the L lanes of a block
-// with DPP and writes the wave's results with one coalesced store.
+// with DPP and writes the wave's results with one coalesced store (NT: store_cost above; N = 8).
 // ---------------------------------------------------------------------------
-template <int N, int U, bool DUAL>
+template <int N, int U, bool DUAL, bool NT = false>
 __global__ __launch_bounds__(256) void sad_nxn_kernel(const u8 *__restrict__ a, const u8 *__restrict__ b,
                                                       u32 *__restrict__ costs, size_t count,
                                                       size_t pred_stride, size_t item_stride)
@@ -117,7 +133,7 @@ __global__ __launch_bounds__(256) void sad_nxn_kernel(const u8 *__restrict__ a, 
       for (int i = 1; i < R; ++i) v = (p == i) ? r[i] : v;
       // block index of (iteration-result p, group g)
       const size_t blk = (base + (size_t)p * UB * 64) / L + g;
-      if (blk < count) costs[blk] = v;
+      if (blk < count) store_cost<NT>(costs, blk, v);
     }
   }
 }
@@ -187,7 +203,7 @@ __global__ __launch_bounds__(256) void satd_nxn_kernel(const u8 *__restrict__ a,
 // whose stage bit is set computes (partner - own) instead of (own - partner):
 // the sign of a whole coefficient never matters under the absolute sum.
 // ---------------------------------------------------------------------------
-template <int U>
+template <int U, bool NT = false>
 __global__ __launch_bounds__(256) void satd8_kernel(const u8 *__restrict__ a, const u8 *__restrict__ b,
                                                     u32 *__restrict__ costs, size_t count)
 {
@@ -232,7 +248,7 @@ __global__ __launch_bounds__(256) void satd8_kernel(const u8 *__restrict__ a, co
 #pragma unroll
       for (int i = 1; i < U; ++i) v = (p == i) ? r[i] : v;
       const size_t blk = (base + (size_t)p * 64) / 4 + g;
-      if (blk < count) costs[blk] = v;
+      if (blk < count) store_cost<NT>(costs, blk, v);
     }
   }
 }
@@ -714,18 +730,20 @@ static int launch_sad(int n, const u8 *a, const u8 *b, size_t count, u32 *costs,
 {
   // count here = number of block pairs (2 * items for DUAL)
   const unsigned threads = 256;
-#define KVZ_SAD_CASE(N, U)                                                                        \
+  const bool nt = tuning("cost_store_nt", 1) != 0;      // store_cost: nontemporal result stores at 8x8; 0: the default policy
+#define KVZ_SAD_CASE(N, U, NT)                                                                    \
   case N: {                                                                                       \
     size_t chunks = count * (N * N / 16);                                                         \
     unsigned grid = stream_grid(chunks, (threads / 64) * 64 * U, (unsigned)tuning("sad_wgs_per_cu", 256)); \
-    launch_carried(sad_nxn_kernel<N, U, DUAL>, dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
+    if (NT && nt) launch_carried(sad_nxn_kernel<N, U, DUAL, NT>, dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
+    else launch_carried(sad_nxn_kernel<N, U, DUAL>, dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
   } break;
   switch (n) {
-    KVZ_SAD_CASE(4, 4)
-    KVZ_SAD_CASE(8, 4)
-    KVZ_SAD_CASE(16, 4)
-    KVZ_SAD_CASE(32, 4)
-    KVZ_SAD_CASE(64, 4)
+    KVZ_SAD_CASE(4, 4, false)
+    KVZ_SAD_CASE(8, 4, true)
+    KVZ_SAD_CASE(16, 4, false)
+    KVZ_SAD_CASE(32, 4, false)
+    KVZ_SAD_CASE(64, 4, false)
     default: return kvzhip::invalid_arg("kvz_hip_sad_nxn_batch / kvz_hip_sad_nxn_dual_batch (n must be 4, 8, 16, 32 or 64)");
   }
 #undef KVZ_SAD_CASE
@@ -737,13 +755,15 @@ template <bool DUAL>
 static int launch_satd(int n, const u8 *a, const u8 *b, size_t count, u32 *costs, size_t ps, size_t is, hipStream_t st)
 {
   const unsigned threads = 256;
+  const bool nt = tuning("cost_store_nt", 1) != 0;      // as in launch_sad
   switch (n) {
     case 4:
       if (!DUAL) launch_carried(satd4_kernel<4>, dim3(stream_grid(count, threads * 4)), dim3(threads), 0, st, a, b, costs, count);
       else launch_carried(satd_4x4_kernel<DUAL>, dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
     case 8:
-      if (!DUAL) launch_carried(satd8_kernel<4>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
+      if (!DUAL && nt) launch_carried(satd8_kernel<4, true>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
+      else if (!DUAL) launch_carried(satd8_kernel<4>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
       else launch_carried(satd_nxn_kernel<8, DUAL>, dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
     case 16:
