@@ -970,7 +970,8 @@ typedef struct {
  *   through kvz_hip_inter_residual_frame_lossless (below) instead.  OUT OF SCOPE:
  *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID; kvz_hip_inter_residual_frame_sl
  *   below takes them) and per-CU QP (the qp field of the records is not read; a QP per LCU: kvz_hip_inter_residual_frame_qp below).  Intra CUs need their neighbours' reconstruction and are not handled, as in
- *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.
+ *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.  RDOQ is built since as a batch entry of its own,
+ *   kvz_hip_rdoq_batch (further below); this stage does not call it.
  * Outputs:
  *   rec planes: the reconstruction inside the inter CUs (a TU without coefficients keeps its prediction).
  *   coeff_y / coeff_u / coeff_v: DEVICE, 16-byte aligned, the layout of lcu->coeff: per LCU, in raster order of the
@@ -1308,7 +1309,9 @@ KVZ_HIP_API int kvz_hip_scaling_tables_pack(const int32_t *const quant_coeff[4][
  *   cbf_out / costs, tiles, error returns, launches, capture -- they are the entries they extend.  A captured call may be replayed
  *   after the CONTENTS of the two arrays changed (the pointers are part of the capture).
  * OUT OF SCOPE: RDOQ and its error_scale, transform skip, parsing --cqmfile, signalling the lists.  Lossless coding has entries of
- * its own, kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below): nothing is quantised there. */
+ * its own, kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below): nothing is quantised there.
+ * RDOQ with its error_scale is built since as a batch entry of its own, kvz_hip_rdoq_batch with kvz_hip_rdoq_tables_pack (further
+ * below); these two stages still quantise with the rdoq-off path. */
 KVZ_HIP_API int kvz_hip_inter_residual_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
                                                 kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
                                                 kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
@@ -1367,7 +1370,8 @@ typedef struct {
  *   (get_coeff_cabac_cost): kvz_hip_inter_residual_frame_ts_cabac and kvz_hip_intra_recon_frame_ts_cabac (below) are these entries
  *   with that rule, and kvz_hip_coeff_cost_batch is the count for any TU of the coefficient arrays they write.  OUT OF SCOPE: RDOQ
  *   and the transform-skip term of the intra rough search (search_intra.c:105-167).  Lossless coding switches transform skip off (encoder.c:623-628) and has entries of its own:
- *   kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below).
+ *   kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below).  RDOQ is built since as a batch entry of its
+ *   own, kvz_hip_rdoq_batch (further below); these stages do not call it.
  * Errors: ts != NULL with tr_skip_out == NULL, with bit_cost < 0 while lcu_bit_cost == NULL, or with lcu_bit_cost not 4-byte
  *   aligned returns KVZ_HIP_ERR_INVALID and nothing is written; so does every error of the _sl entry.
  * Launches and capture: asynchronous, no allocation, no synchronisation with the host, usable between kvz_hip_graph_begin / _end.
@@ -1449,7 +1453,9 @@ typedef struct {
  * This is the coeff_bits term of kvz_cu_rd_cost_luma / _chroma (search.c:300, :369-370) as the reference computes it by default;
  *   the chain's coeff_abs_* sums are that term only under --fast-residual-cost.  OUT OF SCOPE: RDOQ (its lambda, error_scale and
  *   full state have no reachable reference entry), the transform-tree flag bits of the rd cost and the intra rough search's
- *   transform-skip term.
+ *   transform-skip term.  That sentence on RDOQ did not last: kvz_rdoq reads of its state only lambda, qp, the contexts, bitdepth,
+ *   scaling_list and cfg.signhide_enable, a fabricated state reaches it, and RDOQ is now built as kvz_hip_rdoq_batch (further below),
+ *   which reads this section's kvz_hip_coeff_ctx beside a kvz_hip_rdoq_state.
  * Any `range` and any context byte is memory-safe: range is used as (range >> 6) & 3 where it indexes, a byte as (byte >> 1) & 63.
  * Both launches run over the whole list whatever its mix and pass over the other class's descriptors, which costs a descriptor
  *   read each; a caller with many TUs of one class loses nothing by sorting them into calls of their own. */
@@ -1483,7 +1489,8 @@ typedef struct {
  * Errors beyond the _ts entry's (KVZ_HIP_ERR_INVALID, nothing written): pricing != NULL with ts == NULL, with ctx_sets == NULL or
  *   not 2-byte aligned, with n_sets == 0, or with a misaligned lcu_ctx.
  * The multi-picture _frames_ts entries take no pricing yet.  OUT OF SCOPE: RDOQ, the transform-tree flag bits of the rd cost and
- *   the transform-skip term of the intra rough search.  The ABI version stays 4. */
+ *   the transform-skip term of the intra rough search.  The ABI version stays 4.  RDOQ is built since as a batch entry of its own,
+ *   kvz_hip_rdoq_batch (further below); these stages do not call it. */
 KVZ_HIP_API int kvz_hip_inter_residual_frame_ts_cabac(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
                                                       kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c,
                                                       kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
@@ -1565,6 +1572,98 @@ KVZ_HIP_API int kvz_hip_intra_recon_frame_lossless(const kvz_hip_ref_picture *sr
                                                    const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
                                                    kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
                                                    const kvz_hip_tile_grid *tiles, const kvz_hip_lossless *ll, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Rate-distortion optimised quantisation (RDOQ) of a list of TUs      */
+/*   reference: kvz_rdoq (rdo.c:548-881) with kvz_get_ic_rate          */
+/*   (rdo.c:233-278), kvz_get_coded_level (rdo.c:297-339),             */
+/*   get_rate_last / calc_last_bits (rdo.c:350-395) and                */
+/*   kvz_rdoq_sign_hiding (rdo.c:405-539), as kvz_quantize_residual    */
+/*   calls it under cfg.rdoq_enable (quant-generic.c:214-221); the     */
+/*   error scale of kvz_scalinglist_process (scalinglist.c:339-356);   */
+/*   --rdoq, on at preset medium and slower                            */
+/* ------------------------------------------------------------------ */
+/* The two tables RDOQ reads per coefficient, as DEVICE arrays of KVZ_HIP_SL_TABLE_LEN values in the layout of
+ * kvz_hip_scaling_tables: table (size_id, list, rem) at 36 * {0, 16, 80, 336}[size_id] + (6 * list + rem) * N * N.
+ * quant: scaling_list.quant_coeff, 16-byte aligned -- the array kvz_hip_scaling_tables_pack already produces.
+ * err_scale: scaling_list.error_scale, the encoder's own doubles (scalinglist.c:339-356), 8-byte aligned.
+ * RDOQ reads both for flat lists too (rdo.c:563-564), so the tables are always required. */
+typedef struct { const int32_t *quant; const double *err_scale; } kvz_hip_rdoq_tables;   /* 16 bytes; HOST struct, copied at the call */
+
+/* Host only: needs no device and no kvz_hip_init.  Copies scaling_list.quant_coeff and scaling_list.error_scale
+ * ([size_id][list][rem]) into two HOST arrays of KVZ_HIP_SL_TABLE_LEN values in the layout above; quant_out equals what
+ * kvz_hip_scaling_tables_pack writes.  The size-3 rule of that function holds: lists 0, 1 and 3 are read, the tables of lists 2, 4
+ * and 5 are filled with zeros.  A NULL argument or a NULL source pointer elsewhere returns KVZ_HIP_ERR_INVALID. */
+KVZ_HIP_API int kvz_hip_rdoq_tables_pack(const int32_t *const quant_coeff[4][6][6], const double *const error_scale[4][6][6],
+                                         int32_t *quant_out, double *err_out);
+
+/* What kvz_rdoq reads of the encoder state beyond the 136 context bytes of kvz_hip_coeff_ctx: one record per context set,
+ * index-parallel to the kvz_hip_coeff_ctx array (`range` and the transform-skip bytes of that record are not read).
+ * lambda: state->lambda, finite and above 0: the result is specified for such values alone (the reference divides by it, rdo.c:420-421).
+ *   Any other value -- zero, negative, infinite, NaN -- is memory-safe, because nothing is indexed with a cost, but what dest receives is
+ *   then unspecified.  qp: state->qp, 0..51; a TU whose record holds another value is skipped.
+ * root_cbf: cabac.ctx.cu_qt_root_cbf_model; qt_cbf_luma / qt_cbf_chroma: cabac.ctx.qt_cbf_model_luma / _chroma (cabac.h:61-62, :84).
+ * A context byte, here and in kvz_hip_coeff_ctx, is read as (byte >> 1) & 63 for the state and byte & 1 for the MPS, like the
+ *   counting coder: no value can index outside a table. */
+typedef struct {
+  double lambda;
+  int8_t qp;
+  uint8_t root_cbf;
+  uint8_t qt_cbf_luma[4];
+  uint8_t qt_cbf_chroma[4];
+  uint8_t reserved[6];
+} kvz_hip_rdoq_state;           /* 24 bytes; DEVICE array, 8-byte aligned */
+
+/* One TU of kvz_hip_rdoq_batch.
+ * src_offset / dst_offset: in coefficients from `coef` / `dest`, to width * width contiguous row-major values; multiples of 4.  A TU
+ *   of the picture chain's coefficient arrays is addressed by its z-order offset unchanged (see kvz_hip_coeff_cost_desc).
+ * width: 4 / 8 / 16 / 32.  type: 0 (luma) or 2 (chroma).  scan_mode: 0..2, 1 and 2 only at width <= 8.
+ * block_type: 1 = CU_INTRA, 2 = CU_INTER (cu.h:39-41).  tr_depth: 0..3, the depth kvz_quantize_residual hands to kvz_rdoq.
+ * ctx_index: the TU's record in ctx_sets and in states; 16 bits, as the set indices of kvz_hip_coeff_pricing.lcu_ctx are, which
+ *   keeps the record at 16 bytes. */
+typedef struct {
+  uint32_t src_offset;
+  uint32_t dst_offset;
+  uint8_t width, type, scan_mode, block_type;
+  uint8_t tr_depth;
+  uint8_t reserved;
+  uint16_t ctx_index;
+} kvz_hip_rdoq_desc;            /* 16 bytes; DEVICE array, 4-byte aligned */
+
+typedef struct {
+  int32_t signhide;             /* cfg.signhide_enable */
+  int32_t reserved[3];
+} kvz_hip_rdoq_params;          /* 16 bytes; HOST struct, copied at the call */
+
+/* dest at descs[i].dst_offset receives exactly what kvz_rdoq (rdo.c:548-881) leaves in dest_coeff for the TU at descs[i].src_offset:
+ * bit depth 8, state->qp, state->lambda and the contexts of record ctx_index, and the tables of (log2 N - 2,
+ * (block_type == CU_INTRA ? 0 : 3) + (type ? 1 : 0), qp_scaled % 6) with qp_scaled = kvz_get_scaled_qp(type, qp, 0).  All N * N
+ * values are written: the reference's first loop zeroes everything behind the last position it finds, and an all-zero TU comes
+ * out all zero.  coef and dest must not overlap.
+ * Arithmetic: every cost is an IEEE binary64 value computed in the reference's operation order, each multiplication, addition and
+ *   division rounded on its own (no fused multiply-add: the reference's object code holds none); block_uncoded_cost and base_cost
+ *   are summed in scan order by one lane.  |coef| * q is taken as a 64-bit product and then clamped as at rdo.c:629, which equals
+ *   the reference wherever its int32 product is defined.
+ * Covered: kvz_get_coded_level over max_abs_level and max_abs_level - 1, kvz_get_ic_rate with its escape-code loop, the c1 / c2 /
+ *   ctx_set / Rice-parameter updates, the zeroing of coefficient groups (rdo.c:759-812), the last-position search (:815-864) with
+ *   the root-cbf branch for inter luma and the qt-cbf branch otherwise, x and y swapped for the vertical scan, the clean-up
+ *   (:866-876), and kvz_rdoq_sign_hiding when params->signhide and abs_sum >= 2.  Context sets are never written: kvz_rdoq prices
+ *   with them and updates none, so the result does not depend on the order or the grouping of the descriptors.
+ * coef and dest (8-byte aligned), descs (4-byte aligned), ctx_sets (2-byte aligned) and states (8-byte aligned) are DEVICE, and so
+ *   are the two arrays of tables; tables and params are HOST.
+ * A descriptor outside the rules above, with ctx_index >= n_sets, or whose state holds a qp outside 0..51, is skipped and its dest is
+ *   left untouched.
+ * Errors (KVZ_HIP_ERR_INVALID, nothing written): a missing pointer with n > 0 (the pointers inside tables included), n_sets == 0, a
+ *   misaligned array, n above 2^31 - 1.  n == 0 is KVZ_HIP_OK and nothing is looked at.
+ * Launches and capture: two launches (the 4x4 TUs a lane each, the larger ones a wave each), asynchronous on s, no work memory, no
+ *   allocation, no synchronisation with the host; usable between kvz_hip_graph_begin / _end, and a captured call may be replayed
+ *   after the CONTENTS of coef, descs, ctx_sets, states and the tables changed.  The ABI version stays 4.
+ * This is a batch entry of its own, as kvz_hip_coeff_cost_batch was before its stages.  OUT OF SCOPE: RDOQ inside the _ts /
+ *   _frames_ts stages of the picture chain, RDOQ in the drop-in's quantize_residual (it needs the live CABAC state through an
+ *   accessor and keeps calling the host's kvz_rdoq), bit depths above 8. */
+KVZ_HIP_API int kvz_hip_rdoq_batch(const kvz_hip_coeff *coef, kvz_hip_coeff *dest, const kvz_hip_rdoq_desc *descs, size_t n,
+                                   const kvz_hip_coeff_ctx *ctx_sets, const kvz_hip_rdoq_state *states, uint32_t n_sets,
+                                   const kvz_hip_rdoq_tables *tables, const kvz_hip_rdoq_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* Several independent pictures through the residual stages at once    */
@@ -1677,7 +1776,8 @@ typedef struct {
  *   run time would carry the code of both); pictures coded with --lossless (one launch each already); prediction of several
  *   pictures (the QP map, deblocking and SAO of several pictures are kvz_hip_cu_qp_frames, kvz_hip_deblock_frames,
  *   kvz_hip_sao_stats_frames and kvz_hip_sao_frames below) in these entries -- it is an entry of its own,
- *   kvz_hip_inter_recon_frames further below; RDOQ.  The ABI version stays 4. */
+ *   kvz_hip_inter_recon_frames further below; RDOQ.  The ABI version stays 4.  (RDOQ exists as the batch entry kvz_hip_rdoq_batch,
+ *   above; inside these stages it is still to come.) */
 KVZ_HIP_API int kvz_hip_inter_residual_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 
@@ -1746,7 +1846,7 @@ typedef struct {
  *   40-byte reference pictures, and sixteen such tables do not fit the 4 KB of kernel arguments; a reference pool that the records
  *   share is a design of its own: kvz_hip_inter_recon_frames below); pictures coded with --lossless, whose chain ends before
  *   deblocking; the SAO mode / merge decision
- *   and RDOQ, which stay with the host.  The ABI version stays 4. */
+ *   and RDOQ, which stay with the host.  The ABI version stays 4.  (RDOQ as a batch entry: kvz_hip_rdoq_batch, above.) */
 KVZ_HIP_API int kvz_hip_cu_qp_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_sao_stats_frames(const kvz_hip_filter_picture *pictures, int n_pictures, kvz_hip_stream s);

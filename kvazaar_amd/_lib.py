@@ -173,6 +173,16 @@ class CoeffPricing(C.Structure):
     _fields_ = [("ctx_sets", C.c_void_p), ("n_sets", C.c_uint32), ("fast_limit", C.c_int32), ("lcu_ctx", C.c_void_p)]
 
 
+class RdoqTables(C.Structure):
+    """kvz_hip_rdoq_tables"""
+    _fields_ = [("quant", C.c_void_p), ("err_scale", C.c_void_p)]
+
+
+class RdoqParams(C.Structure):
+    """kvz_hip_rdoq_params"""
+    _fields_ = [("signhide", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 class KvzHipError(RuntimeError):
     pass
 
@@ -299,6 +309,8 @@ SIGNATURES = {
     "kvz_hip_array_checksum_blocks": (_SZ, [_I, _I]),
     "kvz_hip_array_checksum_batch": (_I, [C.POINTER(HashPlane), _I, _P, _P, _P]),
     "kvz_hip_coeff_cost_batch": (_I, [_P, _P, _SZ, _P, _U, C.POINTER(CoeffCostParams), _P, _P]),
+    "kvz_hip_rdoq_tables_pack": (_I, [_P, _P, _P, _P]),
+    "kvz_hip_rdoq_batch": (_I, [_P, _P, _P, _SZ, _P, _P, _U, C.POINTER(RdoqTables), C.POINTER(RdoqParams), _P]),
     "kvz_hip_set_registrar": (None, [_P]),
     "kvz_hip_dropin_calls": (C.c_ulonglong, []),
     "kvz_hip_set_state_accessors": (None, [_P]),

@@ -1460,6 +1460,77 @@ def coeff_cost_batch(coeffs, descs, ctx_sets, signhide=1, trskip_enable=1, lossl
     return d_b.to_numpy(np.uint32, (n,))
 
 
+# ---- rate-distortion optimised quantisation ----
+RDOQ_STATE = np.dtype([("lambda", "<f8"), ("qp", "i1"), ("root_cbf", "u1"), ("qt_cbf_luma", "u1", (4,)), ("qt_cbf_chroma", "u1", (4,)),
+                       ("reserved", "u1", (6,))])                                                   # kvz_hip_rdoq_state
+RDOQ_DESC = np.dtype([("src_offset", "<u4"), ("dst_offset", "<u4"), ("width", "u1"), ("type", "u1"), ("scan_mode", "u1"), ("block_type", "u1"),
+                      ("tr_depth", "u1"), ("reserved", "u1"), ("ctx_index", "<u2")])              # kvz_hip_rdoq_desc
+CU_INTRA, CU_INTER = 1, 2    # cu.h:39-41: kvz_hip_rdoq_desc.block_type
+
+
+def rdoq_state_from_dump(ctx184, lam, qp):
+    """A kvz_hip_rdoq_state record cut from a dump of the reference's context block (the 184 bytes of cabac_data_t.ctx) plus
+    state->lambda and state->qp: bytes 16..19 (qt_cbf_model_luma) and 20..23 (qt_cbf_model_chroma) and byte 181 (cu_qt_root_cbf_model).
+    coeff_ctx_from_dump cuts the kvz_hip_coeff_ctx record of the same index from the same dump."""
+    d = np.frombuffer(bytes(bytearray(ctx184)), dtype=np.uint8)
+    if d.size != CABAC_CTX_BYTES:
+        raise ValueError("a context dump is %d bytes, not %d" % (CABAC_CTX_BYTES, d.size))
+    if not 0 <= int(qp) <= 51:
+        raise ValueError("state->qp lies in 0..51")
+    rec = np.zeros((), dtype=RDOQ_STATE)
+    rec["lambda"], rec["qp"], rec["root_cbf"] = float(lam), int(qp), d[181]
+    rec["qt_cbf_luma"], rec["qt_cbf_chroma"] = d[16:20], d[20:24]
+    return rec
+
+
+def pack_rdoq_tables(quant, error_scale):
+    """kvz_hip_rdoq_tables_pack.  quant (int32) and error_scale (float64): [size_id][list][rem] -> N*N values (nested sequences or dicts
+    keyed (size_id, list, rem)), as scaling_list_t holds them after kvz_scalinglist_process; of the 32x32 lists only 0, 1 and 3 are read.
+    -> (quant int32, err_scale float64): two arrays of SL_TABLE_LEN values.  Needs no device."""
+    L = _lib.load()
+    keep, ptrs = [], []
+    for src, dt in ((quant, np.int32), (error_scale, np.float64)):
+        p = (C.c_void_p * 6 * 6 * 4)()
+        for size_id in range(4):
+            for list_id in range(6):
+                for rem in range(6):
+                    try:
+                        t = src[(size_id, list_id, rem)] if isinstance(src, dict) else src[size_id][list_id][rem]
+                    except (KeyError, IndexError):
+                        t = None
+                    if t is None:
+                        continue
+                    a = np.ascontiguousarray(t, dtype=dt).reshape(-1)
+                    assert a.size == 16 << (2 * size_id)
+                    keep.append(a)
+                    p[size_id][list_id][rem] = a.ctypes.data
+        ptrs.append(p)
+    out = np.zeros(SL_TABLE_LEN, np.int32), np.zeros(SL_TABLE_LEN, np.float64)
+    check(L.kvz_hip_rdoq_tables_pack(C.addressof(ptrs[0]), C.addressof(ptrs[1]), out[0].ctypes.data, out[1].ctypes.data), "rdoq_tables_pack")
+    return out
+
+
+def rdoq_batch(coef, descs, ctx_sets, states, tables, signhide=1, dest=None):
+    """kvz_hip_rdoq_batch.  coef: int16 array holding the TUs; descs [n] RDOQ_DESC; ctx_sets [m] COEFF_CTX and states [m] RDOQ_STATE, index-
+    parallel; tables = (quant int32, err_scale float64), the packed arrays of pack_rdoq_tables.  dest: what the destination array holds
+    before the call (a skipped descriptor keeps its values), zeros of coef's size by default.  Returns the destination array, int16."""
+    L = _lib.init()
+    coef = np.ascontiguousarray(coef, dtype=np.int16).ravel()
+    descs = np.ascontiguousarray(descs, dtype=RDOQ_DESC)
+    ctx_sets = np.ascontiguousarray(ctx_sets, dtype=COEFF_CTX).ravel()
+    states = np.ascontiguousarray(states, dtype=RDOQ_STATE).ravel()
+    assert len(states) == len(ctx_sets)
+    quant = np.ascontiguousarray(tables[0], dtype=np.int32).ravel()
+    err = np.ascontiguousarray(tables[1], dtype=np.float64).ravel()
+    assert quant.size == SL_TABLE_LEN and err.size == SL_TABLE_LEN
+    dest = np.zeros(coef.size, dtype=np.int16) if dest is None else np.ascontiguousarray(dest, dtype=np.int16).ravel()
+    d_c, d_o, d_d, d_s, d_t, d_q, d_e = (DeviceBuffer.from_numpy(a) for a in (coef, dest, descs, ctx_sets, states, quant, err))
+    tab = _lib.RdoqTables(d_q.ptr, d_e.ptr)
+    prm = _lib.RdoqParams(int(signhide))
+    check(L.kvz_hip_rdoq_batch(d_c.ptr, d_o.ptr, d_d.ptr, len(descs), d_s.ptr, d_t.ptr, len(ctx_sets), C.byref(tab), C.byref(prm), None), "rdoq_batch")
+    return d_o.to_numpy(np.int16, (dest.size,))
+
+
 # ---- tile halo exchange: batched rectangle copies on device pointers ----
 def copy_rects(rects, stream=None):
     """kvz_hip_copy_rects_batch: rects = [(src, dst, src_stride, dst_stride, w, h)] with device pointers (ints), at most

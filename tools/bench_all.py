@@ -39,7 +39,10 @@ def main():
     ap.add_argument("--tune", default="", help="key=v1,v2,... (interleaved rounds)")
     ap.add_argument("--mb", type=int, default=512, help="bytes per operand array (MiB)")
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--rdoq-cpu", action="store_true", help="no device: the compiled reference's kvz_rdoq on the inputs of the rdoq_batch rows, us per TU")
     args = ap.parse_args()
+    if args.rdoq_cpu:
+        return rdoq_cpu_rows()
     dev = torch.device("cuda", 0)
     L = _lib.init(0)
     st = L.kvz_hip_stream_create()
@@ -259,6 +262,88 @@ def main():
         picture_hash_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "coeff_cost_batch_1080p_4x4 coeff_cost_batch_1080p_8x8 coeff_cost_batch_1080p_16x16 coeff_cost_batch_1080p_32x32" for o in args.only.split(",")):
         coeff_cost_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "rdoq_batch_1080p_4x4 rdoq_batch_1080p_8x8 rdoq_batch_1080p_16x16 rdoq_batch_1080p_32x32" for o in args.only.split(",")):
+        rdoq_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+
+
+RDOQ_QP = 27
+
+
+def rdoq_inputs(n, count):
+    """What the rdoq_batch rows and --rdoq-cpu both run on: `count` luma TUs n wide from the recipe of tests/rdoq_cases.py (about 3 quantiser
+    steps at DC, decaying along x + y) at QP 27, intra and inter alternating, a context set per 4096 coefficients drawn from the fixture's
+    sets, the fixture's tables of flat lists.  numpy only, so that a machine without a device builds the same TUs."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rdoq_cases as K
+    from kvazaar_amd import api
+    z = np.load(os.path.join(ROOT, "tests", "golden", "rdoq.npz"))
+    g = np.random.default_rng(47 + n)
+    yy, xx = np.divmod(np.arange(n * n), n)
+    amp = 3.0 * K.step_of(n, 0, RDOQ_QP) * np.exp(-(xx + yy) / (n / 2.0))
+    coef = np.clip(np.rint(g.normal(0.0, 1.0, (count, n * n)) * amp * np.where(g.random((count, n * n)) < 0.04, 2.5, 1.0)), -32768, 32767).astype(np.int16)
+    n_sets = (count * n * n + 4095) // 4096
+    pick = g.integers(0, len(z["dumps"]), n_sets)
+    dumps = z["dumps"][pick]
+    descs = np.zeros(count, dtype=api.RDOQ_DESC)
+    descs["src_offset"] = descs["dst_offset"] = np.arange(count, dtype=np.int64) * n * n
+    descs["width"], descs["block_type"], descs["tr_depth"] = n, 1 + (np.arange(count) & 1), 1 if n < 32 else 0
+    descs["ctx_index"] = (descs["src_offset"] // 4096) % 65536
+    return coef, descs, dumps, K.lambda_of(RDOQ_QP), (z["quant"][0], z["err_scale"][0])
+
+
+def rdoq_rows(L, st, dev, rounds, only, iters=5):
+    """RDOQ: kvz_hip_rdoq_batch over one 1080p picture's worth (1920 x 1088) of luma TUs of one size (rdoq_inputs).  Device time by events,
+    ms per call: median and min..max over the rounds, TUs per second and ns per TU.  `--rdoq-cpu` prints the compiled reference's kvz_rdoq
+    on the same TUs where the reference is built."""
+    import numpy as np
+    from kvazaar_amd import api
+    W, H = 1920, 1088
+    prm = _lib.RdoqParams(1)
+    print("%-32s %9s %10s %18s %10s %12s %10s" % ("kernel", "launches", "ms", "min..max ms", "TUs", "MTU / s", "ns / TU"))
+    for n in (4, 8, 16, 32):
+        name = "rdoq_batch_1080p_%dx%d" % (n, n)
+        if not any(o in name for o in only):
+            continue
+        count = W * H // (n * n)
+        coef, descs, dumps, lam, (quant, err) = rdoq_inputs(n, count)
+        sets = np.array([api.coeff_ctx_from_dump(d, 256) for d in dumps], dtype=api.COEFF_CTX)
+        states = np.array([api.rdoq_state_from_dump(d, lam, RDOQ_QP) for d in dumps], dtype=api.RDOQ_STATE)
+        dev_arrays = [torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev) for a in (coef, descs, sets, states, quant, err)]
+        d_c, d_d, d_s, d_t, d_q, d_e = dev_arrays
+        dest = torch.zeros(coef.size, dtype=torch.int16, device=dev)
+        tab = _lib.RdoqTables(d_q.data_ptr(), d_e.data_ptr())
+        torch.cuda.synchronize()
+
+        def fn():
+            _lib.check(L.kvz_hip_rdoq_batch(d_c.data_ptr(), dest.data_ptr(), d_d.data_ptr(), count, d_s.data_ptr(), d_t.data_ptr(), len(sets), C.byref(tab),
+                                            C.byref(prm), st), name)
+        t = [timed(L, st, fn, iters=iters, warm=1) for _ in range(rounds)]
+        ms = float(np.median(t))
+        print("%-32s %9d %10.4f %18s %10d %12.3f %10.1f   %.2f levels / TU" % (name, 2, ms, "%.4f..%.4f" % (min(t), max(t)), count, count / ms / 1e3,
+                                                                                ms * 1e6 / count, float((dest != 0).float().sum()) / count))
+
+
+def rdoq_cpu_rows(limit=4000):
+    """the compiled reference's kvz_rdoq, one thread, on the first `limit` TUs of every rdoq_batch row (through ctypes: the call's own cost
+    of a few microseconds is inside the figure)"""
+    import time
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_rdoq as R
+    if not R.available():
+        print("rdoq_cpu: the compiled reference or its sources are not on this machine")
+        return
+    print("%-32s %10s %12s" % ("reference kvz_rdoq, 1 thread", "TUs", "us / TU"))
+    for n in (4, 8, 16, 32):
+        count = min(limit, 1920 * 1088 // (n * n))
+        coef, descs, dumps, lam, _ = rdoq_inputs(n, count)
+        R.rdoq(coef[0], n, 0, 0, 1, 0, RDOQ_QP, lam, dumps[0])
+        t0 = time.perf_counter()
+        for i in range(count):
+            R.rdoq(coef[i], n, 0, 0, int(descs["block_type"][i]), int(descs["tr_depth"][i]), RDOQ_QP, lam, dumps[int(descs["ctx_index"][i])], 1, 0)
+        dt = time.perf_counter() - t0
+        print("%-32s %10d %12.2f" % ("kvz_rdoq_%dx%d" % (n, n), count, dt * 1e6 / count))
 
 
 def coeff_cost_rows(L, st, dev, rounds, only, iters=10):
