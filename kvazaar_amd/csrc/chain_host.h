@@ -1,7 +1,8 @@
 // chain_host.h -- the host side that the multi-picture entries of the picture chain share (kvz_hip_*_frames, kvz_hip_*_frames_ts and the
 // filter stages' kvz_hip_cu_qp_frames, kvz_hip_deblock_frames, kvz_hip_sao_stats_frames, kvz_hip_sao_frames, kvz_hip_inter_recon_frames):
 // the refusal that names a record, the prologue on the record count, what every residual-stage entry requires of one picture's
-// arguments, the checks of a kvz_hip_chain_picture / kvz_hip_chain_picture_ts record, the tile grid on the host with the pool of
+// arguments and of each option (the single-picture entries pack their arguments into a record and ask the same checks), the checks of
+// a kvz_hip_chain_picture / kvz_hip_chain_picture_ts record, the tile grid on the host with the pool of
 // boundaries that the grids of a call share, and the record checks of the hash stage (kvz_hip_picture_hash_frame(s),
 // kvz_hip_array_checksum_batch; tests/test_picture_hash_abi.py runs those without a device).
 //
@@ -125,17 +126,33 @@ inline bool chain_picture_args_ok(const kvz_hip_chain_picture &p, bool intra, bo
     return false;
   return true;
 }
-// the same for the single-picture entries, which take the fields as loose arguments (params: scaling_list and chroma are read)
-inline bool chain_frame_args_ok(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v,
-                                uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
-                                kvz_hip_coeff *coeff_v, kvz_hip_inter_residual_cost *costs, const kvz_hip_inter_residual_params *params, bool intra,
-                                bool lists)
+// The single-picture entries take the fields as loose arguments: each packs them once into the record that kvz_hip.h says they are,
+// and everything behind the entry reads the record.  -> false without src or params, which are copied
+inline bool chain_picture_pack(kvz_hip_chain_picture *p, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                               kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes, kvz_hip_coeff *coeff_y,
+                               kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
+                               const kvz_hip_inter_residual_params *params)
 {
   if (!src || !params) return false;
-  const kvz_hip_chain_picture p = { *src, rec_y, rec_u, rec_v, stride_y, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, nullptr, costs, nullptr,
-                                    *params };
-  return chain_picture_args_ok(p, intra, lists);
+  *p = { *src, rec_y, rec_u, rec_v, stride_y, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, *params };
+  return true;
 }
+
+// ---- one check per option, for the single-picture entries and the records of a call alike ----
+// scaling lists: both tables, 16-byte aligned (a lane reads its row of each with 16-byte loads)
+inline bool chain_tables_ok(const kvz_hip_scaling_tables &t)
+{
+  return t.quant && t.dequant && !(((uintptr_t)t.quant | (uintptr_t)t.dequant) & 15);
+}
+// transform skip, ts != NULL: the array of choices, and a bit cost that is an aligned array or one value that is not negative
+inline bool chain_trskip_ok(const kvz_hip_trskip *ts, const uint8_t *tr_skip_out)
+{
+  return tr_skip_out && (ts->lcu_bit_cost || ts->bit_cost >= 0) && !((uintptr_t)ts->lcu_bit_cost & 3);
+}
+// one QP for the picture (no lcu_qp): what the one-QP entry refuses.  That entry asks make_consts (quant_core.h) for the constants of
+// the 4x4 luma and chroma TUs, which fails where scaled_qp is negative: for luma that is the QP itself, for chroma it is clamped into
+// 0..57 (tests/test_chain_host_checks.py holds this rule against what make_consts decided for every QP)
+inline bool chain_one_qp_ok(const kvz_hip_chain_picture &p) { return p.lcu_qp || p.params.qp >= 0; }
 
 // ---- the records of a call: why record i is refused, or nullptr.  The order of the checks is part of the interface: it decides
 // which reason a record with two defects reports (tests/test_chain_host_checks.py pins it). ----
@@ -151,10 +168,7 @@ inline const char *chain_record_why(const kvz_hip_chain_picture *pictures, int i
 {
   const char *const why = "null or misaligned buffer, size or parameter out of range, or an output shared with another picture";
   const kvz_hip_chain_picture &p = pictures[i];
-  if (!chain_picture_args_ok(p, intra, false)) return why;
-  // one QP for the picture: what the one-QP entry refuses.  That entry asks make_consts (quant_core.h) for the constants of the 4x4
-  // luma and chroma TUs, which fails where scaled_qp is negative: for luma that is the QP itself, for chroma it is clamped into 0..57
-  if (!p.lcu_qp && p.params.qp < 0) return why;
+  if (!chain_picture_args_ok(p, intra, false) || !chain_one_qp_ok(p)) return why;
   for (int j = 0; j < i; ++j)
     if (chain_output_shared(p, pictures[j])) return why;
   return nullptr;
@@ -169,14 +183,11 @@ inline const char *chain_record_ts_why(const kvz_hip_chain_picture_ts *pictures,
   const bool has_lists = r.tables.quant || r.tables.dequant;
   if (has_lists != lists || (r.ts != nullptr) != skip)
     return "a call is homogeneous: every record carries tables or none does, every record carries ts or none does";
-  if (has_lists && (!r.tables.quant || !r.tables.dequant || (((uintptr_t)r.tables.quant | (uintptr_t)r.tables.dequant) & 15)))
-    return "a table is null or not 16-byte aligned";
+  if (has_lists && !chain_tables_ok(r.tables)) return "a table is null or not 16-byte aligned";
   if (!chain_picture_args_ok(p, intra, has_lists))
     return "null or misaligned buffer, size or parameter out of range, or scaling_list does not say whether tables are given";
-  if (r.ts && (!r.tr_skip_out || (!r.ts->lcu_bit_cost && r.ts->bit_cost < 0) || ((uintptr_t)r.ts->lcu_bit_cost & 3)))
-    return "ts without tr_skip_out, a negative bit_cost without lcu_bit_cost, or a misaligned lcu_bit_cost";
-  // one QP for the picture: what the one-QP entry refuses
-  if (!p.lcu_qp && p.params.qp < 0) return "a negative qp without lcu_qp";
+  if (r.ts && !chain_trskip_ok(r.ts, r.tr_skip_out)) return "ts without tr_skip_out, a negative bit_cost without lcu_bit_cost, or a misaligned lcu_bit_cost";
+  if (!chain_one_qp_ok(p)) return "a negative qp without lcu_qp";
   return nullptr;
 }
 inline const char *chain_record_ts_shared(const kvz_hip_chain_picture_ts *pictures, int i)

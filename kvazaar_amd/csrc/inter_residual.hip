@@ -29,7 +29,11 @@ int kvz_hip_inter_residual_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *
                                  const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  return residual_frame<false>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, nullptr, nullptr, params, s);
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         nullptr, params);
+  if (!packed) return kvzhip::invalid_arg(__func__);
+  return residual_frame<false>(__func__, p, nullptr, s);
 }
 
 int kvz_hip_inter_residual_frame_qp(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
@@ -38,7 +42,11 @@ int kvz_hip_inter_residual_frame_qp(const kvz_hip_ref_picture *src, kvz_hip_pixe
                                     const int8_t *lcu_qp, const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  return residual_frame<false>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, nullptr, params, s);
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (!packed) return kvzhip::invalid_arg(__func__);
+  return residual_frame<false>(__func__, p, nullptr, s);
 }
 
 }  // extern "C"

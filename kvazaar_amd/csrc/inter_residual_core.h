@@ -8,6 +8,7 @@
 #include "transform_core.h"
 #include "quant_core.h"
 #include "lcu_layout.h"
+#include "frame_sources.h"
 #include "chain_host.h"
 #include "coeff_cabac_core.h"
 
@@ -100,69 +101,44 @@ __device__ __forceinline__ bool inter_cu_at(const ARGS &a, int x, int y, int &cu
   return cu_x + size <= a.width && cu_y + size <= a.height;
 }
 
-// Outputs that TUs accumulate into start from zero inside the inter CUs (and keep their contents elsewhere).
+// the rule as the init kernels ask it (zero_cu_outputs, frame_sources.h): the record is found from the position, as everywhere here
+struct inter_cu_rule {
+  template <typename PIC> __device__ __forceinline__ bool operator()(const PIC &a, int, int x, int y, int &cu_x, int &cu_y, int &leaf) const
+  {
+    return inter_cu_at(a, x, y, cu_x, cu_y, leaf);
+  }
+};
+
+// cbf_out and costs start from zero inside the inter CUs
 __global__ __launch_bounds__(256) void inter_residual_init_kernel(resid_args a, int n_scu)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_scu) return;
-  const int sy = i / a.cus_stride, sx = i - sy * a.cus_stride;
-  int cu_x, cu_y, leaf;
-  if (!inter_cu_at(a, 4 * sx, 4 * sy, cu_x, cu_y, leaf)) return;
-  if (a.cbf_out) a.cbf_out[i] = 0;
-  if (a.cost && cu_x == 4 * sx && cu_y == 4 * sy) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
-  }
+  zero_cu_outputs(a, i, inter_cu_rule());
 }
 
-// A QP per LCU (kvz_hip_inter_residual_frame_qp): the array and what else the constants depend on.  Every TU derives its own set
-// from the QP of the LCU it lies in, with the function the host uses (flat_consts, quant_core.h) -- a workgroup holds 256 / N
-// neighbouring slots of one row, up to four LCUs for N = 4, so the constants are per TU group, not per workgroup.  The kernel takes
-// it as an optional trailing argument: without it (one QP per call) the instantiation is the kernel as it was, argument for argument.
-struct lcu_qp_source { const int8_t *lcu_qp; int slice_is_intra, signhide; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { return q; }
-// Scaling lists (kvz_hip_inter_residual_frame_sl) are a second trailing argument after the QP source: the two packed arrays, and the
-// QP of every LCU where the source's array is NULL.  A TU's tables depend on its size, its plane and qp % 6 of its own LCU, so the
-// pointers are per TU group like the rest of the constants (sl_consts, quant_core.h).  The instantiation has a translation unit of
-// its own (inter_residual_sl.hip): the two above compile to the code they were.
+// The trailing sources of the kernel below (frame_sources.h), in their order.  The instantiations that an option adds have a
+// translation unit of their own, so that those that were there before it compile to the code they were.
+// A QP per LCU (kvz_hip_inter_residual_frame_qp, inter_residual.hip) is lcu_qp_source.  Every TU derives its own set from the QP of the
+// LCU it lies in -- a workgroup holds 256 / N neighbouring slots of one row, up to four LCUs for N = 4, so the constants are per TU
+// group, not per workgroup.  Without it (one QP per call) the instantiation is the kernel as it was, argument for argument.
+// Scaling lists (kvz_hip_inter_residual_frame_sl, inter_residual_sl.hip) are a second trailing argument after the QP source: the two
+// packed arrays, and the QP of every LCU where the source's array is NULL.  A TU's tables depend on its size, its plane and qp % 6 of
+// its own LCU, so the pointers are per TU group like the rest of the constants (sl_consts, quant_core.h).
 struct sl_source { const int32_t *quant, *dequant; int qp; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &) { return q; }
-__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t) { return t; }
-// Transform skip (kvz_hip_inter_residual_frame_ts) is the last trailing argument, after the QP source or after the lists, and only the
+// Transform skip (kvz_hip_inter_residual_frame_ts, inter_residual_ts.hip) comes after the QP source or after the lists, and only the
 // N = 4 launch takes it: a luma slot runs kvz_quantize_residual twice, transformed and skipped, prices both and keeps the cheaper one
 // (kvz_quantize_residual_trskip, transform.c:229-276).  qp: the QP of every LCU where the QP source's array is NULL and there are no
-// lists.  The two instantiations live in inter_residual_ts.hip; those above compile to the code they were.
+// lists.  Where the kernel takes no trailing argument (several pictures) it makes one of its picture's record.
 struct ts_source { const int32_t *lcu_bit_cost; u8 *tr_skip_out; int bit_cost, qp; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const ts_source &) { return q; }
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &, const ts_source &) { return q; }
-__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t, const ts_source &) { return t; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const ts_source &t) { return t; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const sl_source &, const ts_source &t) { return t; }
-// the trailing argument, or where the kernel takes none (several pictures) what it made of its picture's record
-__device__ __forceinline__ const ts_source &skip_or(const ts_source &m) { return m; }
-template <typename... P> __device__ __forceinline__ const ts_source &skip_or(const ts_source &, const lcu_qp_source &q, const P &...p) { return skip_of(q, p...); }
-// CABAC pricing of the two trials (kvz_hip_inter_residual_frame_ts_cabac) is one more trailing argument after the transform-skip source:
-// the context sets, a set index per LCU (or nullptr: set 0) and cfg.fast_residual_cost_limit.  Per TU the rule of rdo.c:214: at or
-// above the limit the price of a trial is get_coeff_cabac_cost of its 16 levels (coeff_cabac_core.h), below it the estimate.  The two
-// instantiations live in inter_residual_ts_cabac.hip; those above compile to the code they were.
-struct cabac_source { const kvz_hip_coeff_ctx *sets; const uint16_t *lcu_ctx; u32 n_sets; int fast_limit; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const ts_source &, const cabac_source &) { return q; }
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const sl_source &, const ts_source &, const cabac_source &) { return q; }
-__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const sl_source &t, const ts_source &, const cabac_source &) { return t; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const ts_source &t, const cabac_source &) { return t; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const sl_source &, const ts_source &t, const cabac_source &) { return t; }
-__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const ts_source &, const cabac_source &c) { return c; }
-__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const sl_source &, const ts_source &, const cabac_source &c) { return c; }
-// a trial's levels in LDS rows of LD, and the TU's private context set interleaved over the workgroup's TUs
-struct cabac_lds_coeffs { const i16 *p; int ld; __device__ __forceinline__ int at(int x, int y) const { return p[y * ld + x]; } };
+// CABAC pricing of the two trials (kvz_hip_inter_residual_frame_ts_cabac, inter_residual_ts_cabac.hip) is cabac_source, after the
+// transform-skip source: the rule is applied per TU, each on a private copy of its LCU's context set, interleaved over the
+// workgroup's TUs in LDS
 template <int STRIDE> struct cabac_lds_ctx {
   u8 *p;
   __device__ __forceinline__ u32 get(int i) const { return p[i * STRIDE]; }
   __device__ __forceinline__ void set(int i, u32 v) { p[i * STRIDE] = (u8)v; }
 };
-template <typename T, typename U> struct same_type { static constexpr bool value = false; };
-template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
-template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
 
 // Slots: [0, n_y) the N-aligned positions of Y, nx_y per row; then n_c of U and n_c of V, nx_c per row (n_c = 0 for
 // 4:0:0 and for N = 32).  A chroma slot (tx, ty) lies at the luma position (2 N tx, 2 N ty).
@@ -225,17 +201,17 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
   } else if constexpr (LCU_QP) {
     constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5;
     // ky and kc are not used.  A slot that is no TU runs the barriers with the constants of QP 0 and reads nothing
-    const lcu_qp_source &q = only(per_lcu...);
+    const lcu_qp_source &q = source_of<lcu_qp_source>(per_lcu...);
     if constexpr (SL) {
       // a slot that is no TU reads the tables of QP 0 of its size and plane: inside the arrays
-      const sl_source &t = lists_of(per_lcu...);
+      const sl_source &t = source_of<sl_source>(per_lcu...);
       const int qp = valid ? clip_lcu_qp(q.lcu_qp ? (int)q.lcu_qp[(size_t)(ly >> 6) * a.lcus_x + (lx >> 6)] : t.qp) : 0;
       k = sl_consts(qp, LOG2, plane, 0, q.slice_is_intra, q.signhide, t.quant, t.dequant);
       if constexpr (TS) tu_qp = qp;
     } else if constexpr (TS) {
       // without an array it is the QP of the one-QP entry, which is not clamped
       const int at = valid ? (int)((size_t)(ly >> 6) * a.lcus_x + (lx >> 6)) : 0;
-      const int qp = q.lcu_qp ? (valid ? clip_lcu_qp(q.lcu_qp[at]) : 0) : skip_of(per_lcu...).qp;
+      const int qp = q.lcu_qp ? (valid ? clip_lcu_qp(q.lcu_qp[at]) : 0) : source_of<ts_source>(per_lcu...).qp;
       k = flat_consts(qp, LOG2, plane, q.slice_is_intra, q.signhide);
       tu_qp = qp;
     } else {
@@ -360,7 +336,7 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
     // workgroup's) and never take it.
     [[maybe_unused]] ts_source of_picture = {};                              // several pictures: from the picture's record
     if constexpr (MULTI) of_picture = { a.lcu_bit_cost, a.tr_skip_out, a.bit_cost, 0 };
-    const ts_source &ts = skip_or(of_picture, per_lcu...);
+    const ts_source &ts = source_of<ts_source>(per_lcu..., of_picture);            // the trailing argument where there is one
     const uint2 q1 = make_uint2(*(const u32 *)(tq + row * LD), *(const u32 *)(tq + row * LD + 2));
     int any2 = 0;
 #pragma unroll
@@ -438,7 +414,7 @@ __global__ __launch_bounds__(256) void inter_residual_tu_kernel(ARGS args, quant
       // thread prices one after the other, each on a fresh copy of its LCU's set, which the TU's four threads make.  Every thread
       // of the workgroup runs the barriers; a slot that is no luma TU, or whose LCU lies below the limit, copies and prices nothing
       __shared__ u8 s_cabac[kvzhip::CC_CTX_USED * TPB];
-      const cabac_source &cb = cabac_of(per_lcu...);
+      const cabac_source &cb = source_of<cabac_source>(per_lcu...);
       const bool on = valid && plane == 0 && tu_qp >= cb.fast_limit;
       const kvz_hip_coeff_ctx *set = cb.sets;
       if (on) {
@@ -553,63 +529,47 @@ void launch_width(int n, const resid_args &a, const quant_consts &ky, const quan
   else launch_size<4>(a, ky, kc, chroma, st, q...);
 }
 
-// the three entries: lcu_qp == nullptr is one QP per call (params->qp).  SL: the entry with scaling lists, tables required and checked;
-// it launches the kernels that take them and no other, so each translation unit instantiates its own kernels only.  TS: the 4x4 launch
-// takes *skip (checked by the caller); the launches of the other sizes are those of the entry without it
+// the single-picture entries on their record (chain_picture_pack): p.lcu_qp == nullptr is one QP per call (p.params.qp).  SL: the entry
+// with scaling lists, tables required; it launches the kernels that take them and no other, so each translation unit instantiates its
+// own kernels only.  TS: the 4x4 launch takes *skip (checked by the caller), and *price with CABAC; the launches of the other sizes
+// are those of the entry without it
 template <bool SL, bool TS = false, bool CABAC = false>
-int residual_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
-                   kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
-                   kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp,
-                   const kvz_hip_scaling_tables *tables, const kvz_hip_inter_residual_params *params, kvz_hip_stream s,
+int residual_frame(const char *entry, const kvz_hip_chain_picture &p, const kvz_hip_scaling_tables *tables, kvz_hip_stream s,
                    const ts_source *skip = nullptr, const cabac_source *price = nullptr)
 {
-  if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, costs, params, false, SL))
-    return kvzhip::invalid_arg(entry);
-  const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
-  if (SL && (!tables || !tables->quant || !tables->dequant || (((uintptr_t)tables->quant | (uintptr_t)tables->dequant) & 15)))
-    return kvzhip::invalid_arg(entry);
-  const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
-  quant_consts ky = {}, kc = {};                                              // not read with a QP array
-  // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants
-  if (!lcu_qp && (!make_consts(&qp, 4, 0, 0, &ky) || !make_consts(&qp, 4, 2, 2, &kc))) return kvzhip::invalid_arg(entry);
+  if (!chain_picture_args_ok(p, false, SL) || (SL && (!tables || !chain_tables_ok(*tables))) || !chain_one_qp_ok(p)) return kvzhip::invalid_arg(entry);
+  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
   resid_args a;
-  a.src_y = src->y; a.src_u = chroma ? src->u : nullptr; a.src_v = chroma ? src->v : nullptr;
-  a.rec_y = rec_y; a.rec_u = chroma ? rec_u : nullptr; a.rec_v = chroma ? rec_v : nullptr;
-  a.src_stride_y = src->stride_y; a.src_stride_c = src->stride_c; a.rec_stride_y = stride_y; a.rec_stride_c = stride_c;
-  a.coeff_y = coeff_y; a.coeff_u = chroma ? coeff_u : nullptr; a.coeff_v = chroma ? coeff_v : nullptr;
-  a.cus = (u32 *)cus; a.cbf_out = cbf_out; a.cost = (u32 *)costs;
+  a.src_y = p.src.y; a.src_u = chroma ? p.src.u : nullptr; a.src_v = chroma ? p.src.v : nullptr;
+  a.rec_y = p.rec_y; a.rec_u = chroma ? p.rec_u : nullptr; a.rec_v = chroma ? p.rec_v : nullptr;
+  a.src_stride_y = p.src.stride_y; a.src_stride_c = p.src.stride_c; a.rec_stride_y = p.stride_y; a.rec_stride_c = p.stride_c;
+  a.coeff_y = p.coeff_y; a.coeff_u = chroma ? p.coeff_u : nullptr; a.coeff_v = chroma ? p.coeff_v : nullptr;
+  a.cus = (u32 *)p.cus; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs;
   a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
   a.width = width; a.height = height;
   hipStream_t st = ctx_stream(s);
-  if (cbf_out || costs) {
+  if (p.cbf_out || p.costs) {
     const int n_scu = (width >> 2) * (height >> 2);
     hipLaunchKernelGGL(inter_residual_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
     KVZ_CHECK_LAUNCH("inter_residual_init_kernel");
   }
-  // the shift of the transform depends on the size: q_bits, add and the dequantisation shift per launch
-  const int sizes[4] = { 32, 16, 8, 4 };
-  for (int i = 0; i < 4; ++i) {
-    const int n = sizes[i];
+  const kvz_hip_quant_params qp = { p.params.qp, p.params.slice_is_intra, p.params.signhide, 0, nullptr, nullptr };
+  const lcu_qp_source per_lcu = qp_source_of(p);
+  quant_consts ky = {}, kc = {};                                              // read by the kernel without a trailing source only
+  for (int n = 32; n >= 4; n >>= 1) {
     if constexpr (SL) {
-      const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
-      const sl_source lists = { tables->quant, tables->dequant, params->qp };
-      if constexpr (TS) {
-        if (n != 4) launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
-        else if constexpr (CABAC) launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip, *price);
-        else launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip);
-      } else {
-        launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
-      }
+      const sl_source lists = { tables->quant, tables->dequant, p.params.qp };
+      if (!TS || n != 4) launch_width(n, a, ky, kc, chroma, st, per_lcu, lists);
+      else if constexpr (CABAC) launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip, *price);
+      else if constexpr (TS) launch_size<4>(a, ky, kc, chroma, st, per_lcu, lists, *skip);
     } else if (TS && n == 4) {
-      if constexpr (TS) {
-        const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
-        if constexpr (CABAC) launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip, *price);
-        else launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip);
-      }
-    } else if (lcu_qp) {
-      const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+      if constexpr (CABAC) launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip, *price);
+      else if constexpr (TS) launch_size<4>(a, ky, kc, chroma, st, per_lcu, *skip);
+    } else if (p.lcu_qp) {
       launch_width(n, a, ky, kc, chroma, st, per_lcu);
     } else {
+      // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants.  The shift of
+      // the transform depends on the size: q_bits, add and the dequantisation shift per launch
       if (!make_consts(&qp, n, 0, 0, &ky) || !make_consts(&qp, n, 2, 2, &kc)) return kvzhip::invalid_arg(entry);
       launch_width(n, a, ky, kc, chroma, st);
     }

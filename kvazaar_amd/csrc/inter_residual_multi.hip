@@ -18,14 +18,7 @@ __global__ __launch_bounds__(256) void inter_residual_init_multi_kernel(resid_ba
   if (!a.cbf_out && !a.cost) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.cus_stride * (a.height >> 2)) return;
-  const int sy = i / a.cus_stride, sx = i - sy * a.cus_stride;
-  int cu_x, cu_y, leaf;
-  if (!inter_cu_at(a, 4 * sx, 4 * sy, cu_x, cu_y, leaf)) return;
-  if (a.cbf_out) a.cbf_out[i] = 0;
-  if (a.cost && cu_x == 4 * sx && cu_y == 4 * sy) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
-  }
+  zero_cu_outputs(a, i, inter_cu_rule());
 }
 
 }  // namespace

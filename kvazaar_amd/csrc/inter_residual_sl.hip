@@ -20,7 +20,11 @@ int kvz_hip_inter_residual_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixe
     if (params && params->scaling_list != 0) return kvzhip::invalid_arg(__func__);
     return kvz_hip_inter_residual_frame_qp(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, params, s);
   }
-  return residual_frame<true>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, tables, params, s);
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (!packed) return kvzhip::invalid_arg(__func__);
+  return residual_frame<true>(__func__, p, tables, s);
 }
 
 }  // extern "C"

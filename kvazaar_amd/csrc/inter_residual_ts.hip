@@ -25,15 +25,14 @@ int kvz_hip_inter_residual_frame_ts(const kvz_hip_ref_picture *src, kvz_hip_pixe
     return kvz_hip_inter_residual_frame_sl(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, tables,
                                            params, s);
   }
-  if (!tr_skip_out || !params || (!ts->lcu_bit_cost && ts->bit_cost < 0) || ((uintptr_t)ts->lcu_bit_cost & 3)) return kvzhip::invalid_arg(__func__);
-  const ts_source skip = { ts->lcu_bit_cost, tr_skip_out, ts->bit_cost, params->qp };
-  if (tables)
-    return residual_frame<true, true>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, tables,
-                                      params, s, &skip);
-  // what the _sl entry refuses without tables is refused here
-  if (params->scaling_list != 0) return kvzhip::invalid_arg(__func__);
-  return residual_frame<false, true>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, nullptr,
-                                     params, s, &skip);
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (!packed || !chain_trskip_ok(ts, tr_skip_out)) return kvzhip::invalid_arg(__func__);
+  const ts_source skip = { ts->lcu_bit_cost, tr_skip_out, ts->bit_cost, p.params.qp };
+  // without tables, what the _sl entry refuses without them is refused: scaling_list says whether tables are given
+  if (tables) return residual_frame<true, true>(__func__, p, tables, s, &skip);
+  return residual_frame<false, true>(__func__, p, nullptr, s, &skip);
 }
 
 }  // extern "C"

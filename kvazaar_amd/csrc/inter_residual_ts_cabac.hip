@@ -22,17 +22,15 @@ int kvz_hip_inter_residual_frame_ts_cabac(const kvz_hip_ref_picture *src, kvz_hi
     return kvz_hip_inter_residual_frame_ts(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, tables, ts,
                                            tr_skip_out, params, s);
   }
-  if (coeff_pricing_why(pricing, ts)) return kvzhip::invalid_arg(__func__);
-  if (!tr_skip_out || !params || (!ts->lcu_bit_cost && ts->bit_cost < 0) || ((uintptr_t)ts->lcu_bit_cost & 3)) return kvzhip::invalid_arg(__func__);
-  const ts_source skip = { ts->lcu_bit_cost, tr_skip_out, ts->bit_cost, params->qp };
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (coeff_pricing_why(pricing, ts) || !packed || !chain_trskip_ok(ts, tr_skip_out)) return kvzhip::invalid_arg(__func__);
+  const ts_source skip = { ts->lcu_bit_cost, tr_skip_out, ts->bit_cost, p.params.qp };
   const cabac_source price = { pricing->ctx_sets, pricing->lcu_ctx, pricing->n_sets, pricing->fast_limit };
-  if (tables)
-    return residual_frame<true, true, true>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp,
-                                            tables, params, s, &skip, &price);
-  // what the _sl entry refuses without tables is refused here
-  if (params->scaling_list != 0) return kvzhip::invalid_arg(__func__);
-  return residual_frame<false, true, true>(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp,
-                                           nullptr, params, s, &skip, &price);
+  // without tables, what the _sl entry refuses without them is refused: scaling_list says whether tables are given
+  if (tables) return residual_frame<true, true, true>(__func__, p, tables, s, &skip, &price);
+  return residual_frame<false, true, true>(__func__, p, nullptr, s, &skip, &price);
 }
 
 }  // extern "C"

@@ -32,7 +32,11 @@ int kvz_hip_intra_recon_frame(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec
                               kvz_hip_inter_residual_cost *costs, const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s);
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         nullptr, params);
+  if (!packed) return kvzhip::invalid_arg(__func__);
+  return intra_frame(__func__, p, s);
 }
 
 }  // extern "C"

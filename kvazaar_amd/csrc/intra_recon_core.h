@@ -10,6 +10,7 @@
 #include "transform_core.h"
 #include "quant_core.h"
 #include "lcu_layout.h"
+#include "frame_sources.h"
 #include "intra_core.h"
 #include "tile_grid.h"
 #include "coeff_cabac_core.h"
@@ -117,19 +118,20 @@ __device__ __forceinline__ bool intra_cu_of(u32 head, int x, int y, int width, i
   return cu_x + size <= width && cu_y + size <= height;
 }
 
-// Outputs that TUs of three planes accumulate into start from zero inside the intra CUs (and keep their contents elsewhere).
+// the rule as the init kernels ask it (zero_cu_outputs, frame_sources.h): SCU i of picture a, which lies at luma (x, y)
+struct intra_cu_rule {
+  template <typename PIC> __device__ __forceinline__ bool operator()(const PIC &a, int i, int x, int y, int &cu_x, int &cu_y, int &leaf) const
+  {
+    return intra_cu_of(a.cus[(size_t)i * 5], x, y, a.width, a.height, cu_x, cu_y, leaf);
+  }
+};
+
+// cbf_out and costs start from zero inside the intra CUs
 __global__ __launch_bounds__(256) void intra_recon_init_kernel(intra_args a, int n_scu)
 {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_scu) return;
-  const int sy = i / a.cus_stride, sx = i - sy * a.cus_stride;
-  int cu_x, cu_y, leaf;
-  if (!intra_cu_of(a.cus[(size_t)i * 5], 4 * sx, 4 * sy, a.width, a.height, cu_x, cu_y, leaf)) return;
-  if (a.cbf_out) a.cbf_out[i] = 0;
-  if (a.cost && cu_x == 4 * sx && cu_y == 4 * sy) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
-  }
+  zero_cu_outputs(a, i, intra_cu_rule());
 }
 
 struct tu_pos {
@@ -149,7 +151,6 @@ struct lds_view { i16 *p; int ld, n; __device__ i16 &operator[](int i) const { r
 struct ts_lcu { int qp; u32 bit_cost; u8 *out; };
 // CABAC pricing of the two trials: the LCU's context set, and whether its QP is at or above cfg.fast_residual_cost_limit (rdo.c:214)
 struct cabac_lcu { const kvz_hip_coeff_ctx *set; bool on; };
-struct cabac_lds_coeffs { const i16 *p; int ld; __device__ __forceinline__ int at(int x, int y) const { return p[y * ld + x]; } };
 struct cabac_lds_ctx {
   u8 *p;
   __device__ __forceinline__ u32 get(int i) const { return p[i]; }
@@ -485,54 +486,25 @@ __device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const t
   __syncthreads();                                                              // the tile is complete for the next TU
 }
 
-// A QP per LCU (kvz_hip_intra_recon_frame_qp): the array and what else the constants depend on.  A workgroup is one LCU of one
-// plane, so the QP is one value per workgroup: loaded once, made wave-uniform, and the sets of the four sizes derived before the walk
-// with the function the host uses (flat_consts, quant_core.h); they stay in scalar registers.  The kernel takes it as an optional
-// trailing argument: without it (one QP per call, the sets in intra_args) the instantiation is the kernel as it was.  Each of the two
-// instantiations is alone in its translation unit (intra_recon.hip, intra_recon_qp.hip): a second one in the same module changes the
-// code the compiler emits for the first, and the one-QP kernel is to stay as it was measured.
-struct lcu_qp_source { const int8_t *lcu_qp; int slice_is_intra, signhide; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q) { return q; }
-// A tiled picture (kvz_hip_intra_recon_frame_tiles) is a second trailing argument after the QP source: the grid, and the QP of
-// every LCU where the source's array is NULL.  Again an instantiation of its own in a translation unit of its own
-// (intra_recon_tiles.hip); the two above compile to the code they were.
+// The trailing sources of the kernel below (frame_sources.h), in their order.  Each of them selects an instantiation that is alone in
+// its translation unit: a second one in the same module changes the code the compiler emits for the first, and the kernels that were
+// there before an option are to stay as they were measured.
+// A QP per LCU (kvz_hip_intra_recon_frame_qp, intra_recon_qp.hip) is lcu_qp_source.  A workgroup is one LCU of one plane, so the QP is
+// one value per workgroup: loaded once, made wave-uniform, and the sets of the four sizes derived before the walk; they stay in scalar
+// registers.  Without it (intra_recon.hip) the sets come in intra_args.
+// A tiled picture (kvz_hip_intra_recon_frame_tiles, intra_recon_tiles.hip) is a second trailing argument after the QP source: the
+// grid, and the QP of every LCU where the source's array is NULL.
 struct tile_source { kvz_hip_tile_grid grid; int qp; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &) { return q; }
-__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t) { return t; }
-// Scaling lists (kvz_hip_intra_recon_frame_sl) are a third trailing argument after the grid: the two packed arrays.  The workgroup
-// derives the sets of the four sizes of its LCU and plane with their table pointers (sl_consts, quant_core.h) where the others derive
-// the flat sets.  Once more an instantiation of its own in a translation unit of its own (intra_recon_sl.hip).
+// Scaling lists (kvz_hip_intra_recon_frame_sl, intra_recon_sl.hip) are a third trailing argument after the grid: the two packed arrays.
+// The workgroup derives the sets of the four sizes of its LCU and plane with their table pointers (sl_consts, quant_core.h) where the
+// others derive the flat sets.
 struct sl_source { const int32_t *quant, *dequant; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &) { return q; }
-__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &) { return t; }
-__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l) { return l; }
-// Transform skip (kvz_hip_intra_recon_frame_ts) is the last trailing argument, after the grid or after the lists: the bit cost, one
-// value or one per LCU, and the array of choices.  The workgroup reads its LCU's value once, next to the QP.  Two instantiations, flat
-// lists and tables, in a translation unit of their own (intra_recon_ts.hip).
+// Transform skip (kvz_hip_intra_recon_frame_ts, intra_recon_ts.hip) comes after the grid or after the lists: the bit cost, one value or
+// one per LCU, and the array of choices.  The workgroup reads its LCU's value once, next to the QP.  Two instantiations, flat lists and
+// tables.
 struct ts_source { const int32_t *lcu_bit_cost; u8 *tr_skip_out; int bit_cost; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const ts_source &) { return q; }
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &, const ts_source &) { return q; }
-__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const ts_source &) { return t; }
-__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &, const ts_source &) { return t; }
-__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l, const ts_source &) { return l; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const ts_source &t) { return t; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &t) { return t; }
-// CABAC pricing of the two trials (kvz_hip_intra_recon_frame_ts_cabac) is one more trailing argument after the transform-skip source:
-// the context sets, a set index per LCU (or nullptr: set 0) and cfg.fast_residual_cost_limit.  The workgroup picks its LCU's set
-// once, next to the QP.  Two instantiations in a translation unit of their own (intra_recon_ts_cabac.hip).
-struct cabac_source { const kvz_hip_coeff_ctx *sets; const uint16_t *lcu_ctx; u32 n_sets; int fast_limit; };
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const ts_source &, const cabac_source &) { return q; }
-__device__ __forceinline__ const lcu_qp_source &only(const lcu_qp_source &q, const tile_source &, const sl_source &, const ts_source &, const cabac_source &) { return q; }
-__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const ts_source &, const cabac_source &) { return t; }
-__host__ __device__ __forceinline__ const tile_source &tiles_of(const lcu_qp_source &, const tile_source &t, const sl_source &, const ts_source &, const cabac_source &) { return t; }
-__device__ __forceinline__ const sl_source &lists_of(const lcu_qp_source &, const tile_source &, const sl_source &l, const ts_source &, const cabac_source &) { return l; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const ts_source &t, const cabac_source &) { return t; }
-__device__ __forceinline__ const ts_source &skip_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &t, const cabac_source &) { return t; }
-__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const tile_source &, const ts_source &, const cabac_source &c) { return c; }
-__device__ __forceinline__ const cabac_source &cabac_of(const lcu_qp_source &, const tile_source &, const sl_source &, const ts_source &, const cabac_source &c) { return c; }
-template <typename T, typename U> struct same_type { static constexpr bool value = false; };
-template <typename T> struct same_type<T, T> { static constexpr bool value = true; };
-template <typename T, typename... P> constexpr bool pack_has = (same_type<T, P>::value || ...);
+// CABAC pricing of the two trials (kvz_hip_intra_recon_frame_ts_cabac, intra_recon_ts_cabac.hip) is cabac_source, after the
+// transform-skip source.  The workgroup picks its LCU's set once, next to the QP.  Two instantiations again.
 template <bool LCU_QP> struct lcu_sets {};                                   // what a workgroup derives from its LCU's QP: nothing with one QP per call,
 template <> struct lcu_sets<true> { quant_consts k[4]; };                    // else the sets of the four sizes, [log2 N - 2]
 
@@ -599,7 +571,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
     tr = { 64 * cx0, 64 * ry0, min(64 * cx1, (int)a.width), min(64 * ry1, (int)a.height) };
   } else if constexpr (TILES) {
     // wave-uniform: scalar loads of the grid, scalar compares and selects
-    const kvz_hip_tile_grid &g = tiles_of(per_lcu...).grid;
+    const kvz_hip_tile_grid &g = source_of<tile_source>(per_lcu...).grid;
     const int cols = g.cols, col = (int)blockIdx.x % cols;
     int cx0, cx1, ry0, ry1;
     lcu_y = (int)blockIdx.x / cols;
@@ -664,23 +636,27 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
       skip = { qp, (u32)max(v, 0), a.tr_skip_out };
     }
   } else if constexpr (LCU_QP) {
-    const lcu_qp_source &q = only(per_lcu...);
+    const lcu_qp_source &q = source_of<lcu_qp_source>(per_lcu...);
     int qp;
-    if constexpr (TILES) qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(q.lcu_qp ? (int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x] : tiles_of(per_lcu...).qp)));
+    if constexpr (TILES) qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(q.lcu_qp ? (int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x] : source_of<tile_source>(per_lcu...).qp)));
     else qp = clip_lcu_qp((int)__builtin_amdgcn_readfirstlane((u32)(int)q.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       // (a chroma plane has no 32x32 TU: that set is derived and not used)
-      if constexpr (SL) own.k[i] = sl_consts(qp, 2 + i, plane, 1, q.slice_is_intra, q.signhide, lists_of(per_lcu...).quant, lists_of(per_lcu...).dequant);
-      else own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, q.slice_is_intra, q.signhide);
+      if constexpr (SL) {
+        const sl_source &lists = source_of<sl_source>(per_lcu...);
+        own.k[i] = sl_consts(qp, 2 + i, plane, 1, q.slice_is_intra, q.signhide, lists.quant, lists.dequant);
+      } else {
+        own.k[i] = flat_consts(qp, 2 + i, plane ? 1 : 0, q.slice_is_intra, q.signhide);
+      }
     }
     if constexpr (TS) {
-      const ts_source &ts = skip_of(per_lcu...);
+      const ts_source &ts = source_of<ts_source>(per_lcu...);
       const int v = (int)__builtin_amdgcn_readfirstlane((u32)(ts.lcu_bit_cost ? ts.lcu_bit_cost[(size_t)lcu_y * a.lcus_x + lcu_x] : ts.bit_cost));
       skip = { qp, (u32)max(v, 0), ts.tr_skip_out };
     }
     if constexpr (CABAC) {
-      const cabac_source &cb = cabac_of(per_lcu...);
+      const cabac_source &cb = source_of<cabac_source>(per_lcu...);
       const u32 want = __builtin_amdgcn_readfirstlane(cb.lcu_ctx ? (u32)cb.lcu_ctx[(size_t)lcu_y * a.lcus_x + lcu_x] : 0u);
       price = { cb.sets + min(want, cb.n_sets - 1u), qp >= cb.fast_limit };   // an index beyond the table is its last set
     }
@@ -732,36 +708,38 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
   }
 }
 
-// the four entries; per_lcu: nothing (one QP per call, params->qp), one lcu_qp_source, that and a tile_source, or those and an
-// sl_source (the only one that takes, and requires, params->scaling_list != 0)
-template <typename... PER_LCU>
-int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
-                kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes, kvz_hip_coeff *coeff_y,
-                kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
-                const kvz_hip_inter_residual_params *params, kvz_hip_stream s, PER_LCU... per_lcu)
+// the tile source of a record and its grid; -> false for a malformed grid and for what the one-QP entry refuses
+inline bool tile_source_make(const kvz_hip_chain_picture &p, const kvz_hip_tile_grid *grid, tile_source *tiles)
 {
-  if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, costs, params, true,
-                           pack_has<sl_source, PER_LCU...>))
-    return kvzhip::invalid_arg(entry);
-  const int width = src->width, height = src->height, chroma = params->chroma ? 1 : 0;
-  const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
+  tiles->qp = p.params.qp;
+  return chain_one_qp_ok(p) && tile_grid_make(grid, p.src.width, p.src.height, &tiles->grid);
+}
+
+// the single-picture entries on their record (chain_picture_pack); per_lcu: nothing (one QP per call, params.qp), or the trailing
+// sources of the kernel.  An sl_source among them takes, and requires, params.scaling_list != 0
+template <typename... PER_LCU>
+int intra_frame(const char *entry, const kvz_hip_chain_picture &p, kvz_hip_stream s, PER_LCU... per_lcu)
+{
+  if (!chain_picture_args_ok(p, true, pack_has<sl_source, PER_LCU...>)) return kvzhip::invalid_arg(entry);
+  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+  const kvz_hip_quant_params qp = { p.params.qp, p.params.slice_is_intra, p.params.signhide, 0, nullptr, nullptr };
   intra_args a;
   // quant uses type 0 / 2, dequant 0 / 2 / 3 (quant-generic.c:224, :244); flat lists: U and V share their constants.  The shift of
   // the transform depends on the size: a set of constants per size
   __builtin_memset(a.k, 0, sizeof a.k);                                        // not read with a QP array
   for (int i = 0; i < 4 && sizeof...(PER_LCU) == 0; ++i)
     if (!make_consts(&qp, 4 << i, 0, 0, &a.k[0][i]) || !make_consts(&qp, 4 << i, 2, 2, &a.k[1][i])) return kvzhip::invalid_arg(entry);
-  a.src[0] = src->y; a.src[1] = chroma ? src->u : nullptr; a.src[2] = chroma ? src->v : nullptr;
-  a.rec[0] = rec_y; a.rec[1] = chroma ? rec_u : nullptr; a.rec[2] = chroma ? rec_v : nullptr;
-  a.src_stride[0] = src->stride_y; a.src_stride[1] = a.src_stride[2] = src->stride_c;
-  a.rec_stride[0] = stride_y; a.rec_stride[1] = a.rec_stride[2] = stride_c;
-  a.coeff[0] = coeff_y; a.coeff[1] = chroma ? coeff_u : nullptr; a.coeff[2] = chroma ? coeff_v : nullptr;
-  a.cus = (u32 *)cus; a.modes = intra_modes; a.cbf_out = cbf_out; a.cost = (u32 *)costs;
+  a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
+  a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
+  a.src_stride[0] = p.src.stride_y; a.src_stride[1] = a.src_stride[2] = p.src.stride_c;
+  a.rec_stride[0] = p.stride_y; a.rec_stride[1] = a.rec_stride[2] = p.stride_c;
+  a.coeff[0] = p.coeff_y; a.coeff[1] = chroma ? p.coeff_u : nullptr; a.coeff[2] = chroma ? p.coeff_v : nullptr;
+  a.cus = (u32 *)p.cus; a.modes = p.intra_modes; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs;
   a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
   a.width = width; a.height = height;
   const int lcus_y = (height + 63) >> 6;
   hipStream_t st = ctx_stream(s);
-  if (cbf_out || costs) {
+  if (p.cbf_out || p.costs) {
     const int n_scu = (width >> 2) * (height >> 2);
     hipLaunchKernelGGL(intra_recon_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
     KVZ_CHECK_LAUNCH("intra_recon_init_kernel");
@@ -770,7 +748,7 @@ int intra_frame(const char *entry, const kvz_hip_ref_picture *src, kvz_hip_pixel
   int waves = a.lcus_x + 2 * (lcus_y - 1), groups = lcus_y;
   if constexpr (sizeof...(PER_LCU) >= 2) {
     // and on the grid: the largest tile's count of waves, a workgroup per LCU row and tile column
-    const kvz_hip_tile_grid &g = tiles_of(per_lcu...).grid;
+    const kvz_hip_tile_grid &g = source_of<tile_source>(per_lcu...).grid;
     waves = tile_grid_waves(g);
     groups = lcus_y * g.cols;
   }

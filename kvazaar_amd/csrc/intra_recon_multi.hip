@@ -19,14 +19,7 @@ __global__ __launch_bounds__(256) void intra_recon_init_multi_kernel(intra_batch
   if (!a.cbf_out && !a.cost) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= a.cus_stride * (a.height >> 2)) return;
-  const int sy = i / a.cus_stride, sx = i - sy * a.cus_stride;
-  int cu_x, cu_y, leaf;
-  if (!intra_cu_of(a.cus[(size_t)i * 5], 4 * sx, 4 * sy, a.width, a.height, cu_x, cu_y, leaf)) return;
-  if (a.cbf_out) a.cbf_out[i] = 0;
-  if (a.cost && cu_x == 4 * sx && cu_y == 4 * sy) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
-  }
+  zero_cu_outputs(a, i, intra_cu_rule());
 }
 
 }  // namespace

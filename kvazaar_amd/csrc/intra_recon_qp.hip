@@ -14,10 +14,11 @@ int kvz_hip_intra_recon_frame_qp(const kvz_hip_ref_picture *src, kvz_hip_pixel *
   // without the array it is the old entry, launching the old entry's kernel
   if (!lcu_qp) return kvz_hip_intra_recon_frame(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s);
   KVZ_CHECK_CTX();
-  if (!params) return kvzhip::invalid_arg(__func__);
-  const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
-  return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s,
-                     per_lcu);
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (!packed) return kvzhip::invalid_arg(__func__);
+  return intra_frame(__func__, p, s, qp_source_of(p));
 }
 
 }  // extern "C"

@@ -20,16 +20,13 @@ int kvz_hip_intra_recon_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixel *
     return kvz_hip_intra_recon_frame_tiles(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
                                            lcu_qp, grid, params, s);
   }
-  if (!params || !src || !tables->quant || !tables->dequant || (((uintptr_t)tables->quant | (uintptr_t)tables->dequant) & 15))
-    return kvzhip::invalid_arg(__func__);
+  kvz_hip_chain_picture p;
   tile_source tiles;
-  if (!tile_grid_make(grid, src->width, src->height, &tiles.grid)) return kvzhip::invalid_arg(__func__);
-  tiles.qp = params->qp;
-  if (!lcu_qp && params->qp < 0) return kvzhip::invalid_arg(__func__);       // one QP per call: what the one-QP entry refuses
-  const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (!packed || !chain_tables_ok(*tables) || !tile_source_make(p, grid, &tiles)) return kvzhip::invalid_arg(__func__);
   const sl_source lists = { tables->quant, tables->dequant };
-  return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s,
-                     per_lcu, tiles, lists);
+  return intra_frame(__func__, p, s, qp_source_of(p), tiles, lists);
 }
 
 }  // extern "C"

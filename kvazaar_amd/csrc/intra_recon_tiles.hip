@@ -18,19 +18,12 @@ int kvz_hip_intra_recon_frame_tiles(const kvz_hip_ref_picture *src, kvz_hip_pixe
                                     const kvz_hip_inter_residual_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!params || !src) return kvzhip::invalid_arg(__func__);
+  kvz_hip_chain_picture p;
   tile_source tiles;
-  if (!tile_grid_make(grid, src->width, src->height, &tiles.grid)) return kvzhip::invalid_arg(__func__);
-  tiles.qp = params->qp;
-  if (!lcu_qp) {
-    // one QP per call: what the one-QP entry refuses is refused here
-    const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
-    quant_consts k;
-    if (!make_consts(&qp, 4, 0, 0, &k) || !make_consts(&qp, 4, 2, 2, &k)) return kvzhip::invalid_arg(__func__);
-  }
-  const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
-  return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s,
-                     per_lcu, tiles);
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (!packed || !tile_source_make(p, grid, &tiles)) return kvzhip::invalid_arg(__func__);
+  return intra_frame(__func__, p, s, qp_source_of(p), tiles);
 }
 
 }  // extern "C"

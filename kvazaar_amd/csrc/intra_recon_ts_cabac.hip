@@ -22,29 +22,20 @@ int kvz_hip_intra_recon_frame_ts_cabac(const kvz_hip_ref_picture *src, kvz_hip_p
     return kvz_hip_intra_recon_frame_ts(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp,
                                         grid, tables, ts, tr_skip_out, params, s);
   }
-  if (coeff_pricing_why(pricing, ts)) return kvzhip::invalid_arg(__func__);
-  if (!tr_skip_out || !params || !src || (!ts->lcu_bit_cost && ts->bit_cost < 0) || ((uintptr_t)ts->lcu_bit_cost & 3))
-    return kvzhip::invalid_arg(__func__);
-  if (tables && (!tables->quant || !tables->dequant || (((uintptr_t)tables->quant | (uintptr_t)tables->dequant) & 15))) return kvzhip::invalid_arg(__func__);
+  kvz_hip_chain_picture p;
   tile_source tiles;
-  if (!tile_grid_make(grid, src->width, src->height, &tiles.grid)) return kvzhip::invalid_arg(__func__);
-  tiles.qp = params->qp;
-  if (!lcu_qp) {
-    // one QP per call: what the one-QP entry refuses is refused here
-    const kvz_hip_quant_params qp = { params->qp, params->slice_is_intra, params->signhide, 0, nullptr, nullptr };
-    quant_consts k;
-    if (!make_consts(&qp, 4, 0, 0, &k) || !make_consts(&qp, 4, 2, 2, &k)) return kvzhip::invalid_arg(__func__);
-  }
-  const lcu_qp_source per_lcu = { lcu_qp, params->slice_is_intra ? 1 : 0, params->signhide };
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         lcu_qp, params);
+  if (coeff_pricing_why(pricing, ts) || !packed || !chain_trskip_ok(ts, tr_skip_out) || (tables && !chain_tables_ok(*tables)) ||
+      !tile_source_make(p, grid, &tiles))
+    return kvzhip::invalid_arg(__func__);
   const ts_source skip = { ts->lcu_bit_cost, tr_skip_out, ts->bit_cost };
   const cabac_source price = { pricing->ctx_sets, pricing->lcu_ctx, pricing->n_sets, pricing->fast_limit };
   if (tables) {
     const sl_source lists = { tables->quant, tables->dequant };
-    return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s,
-                       per_lcu, tiles, lists, skip, price);
+    return intra_frame(__func__, p, s, qp_source_of(p), tiles, lists, skip, price);
   }
-  return intra_frame(__func__, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, params, s,
-                     per_lcu, tiles, skip, price);
+  return intra_frame(__func__, p, s, qp_source_of(p), tiles, skip, price);
 }
 
 }  // extern "C"

@@ -305,25 +305,21 @@ __global__ __launch_bounds__(LL_WG) void lossless_lcu_kernel(ll_args a, kvz_hip_
   }
 }
 
-int lossless_frame(const char *entry, bool intra, const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
-                   kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes, kvz_hip_coeff *coeff_y,
-                   kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out, kvz_hip_inter_residual_cost *costs,
-                   const kvz_hip_tile_grid *tiles, const kvz_hip_lossless *ll, kvz_hip_stream s)
+// p: the entry's arguments as a record (chain_picture_pack), whose params hold ll->chroma and nothing else
+int lossless_frame(const char *entry, bool intra, const kvz_hip_chain_picture &p, const kvz_hip_tile_grid *tiles, const kvz_hip_lossless *ll,
+                   kvz_hip_stream s)
 {
-  if (!ll || ll->reserved[0] || ll->reserved[1]) return kvzhip::invalid_arg(entry);
-  const kvz_hip_inter_residual_params flat = { 0, 0, 0, 0, ll->chroma, 0 };     // what the check of the arguments reads of them
-  if (!chain_frame_args_ok(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, costs, &flat, intra, false))
-    return kvzhip::invalid_arg(entry);
-  const int width = src->width, height = src->height, chroma = ll->chroma ? 1 : 0;
+  if (ll->reserved[0] || ll->reserved[1] || !chain_picture_args_ok(p, intra, false)) return kvzhip::invalid_arg(entry);
+  const int width = p.src.width, height = p.src.height, chroma = ll->chroma ? 1 : 0;
   kvz_hip_tile_grid grid;
   if (!tile_grid_make(intra ? tiles : nullptr, width, height, &grid)) return kvzhip::invalid_arg(entry);
   ll_args a;
-  a.src[0] = src->y; a.src[1] = chroma ? src->u : nullptr; a.src[2] = chroma ? src->v : nullptr;
-  a.rec[0] = rec_y; a.rec[1] = chroma ? rec_u : nullptr; a.rec[2] = chroma ? rec_v : nullptr;
-  a.src_stride[0] = src->stride_y; a.src_stride[1] = a.src_stride[2] = src->stride_c;
-  a.rec_stride[0] = stride_y; a.rec_stride[1] = a.rec_stride[2] = stride_c;
-  a.coeff[0] = coeff_y; a.coeff[1] = chroma ? coeff_u : nullptr; a.coeff[2] = chroma ? coeff_v : nullptr;
-  a.cus = (u32 *)cus; a.modes = intra_modes; a.cbf_out = cbf_out; a.cost = (u32 *)costs;
+  a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
+  a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
+  a.src_stride[0] = p.src.stride_y; a.src_stride[1] = a.src_stride[2] = p.src.stride_c;
+  a.rec_stride[0] = p.stride_y; a.rec_stride[1] = a.rec_stride[2] = p.stride_c;
+  a.coeff[0] = p.coeff_y; a.coeff[1] = chroma ? p.coeff_u : nullptr; a.coeff[2] = chroma ? p.coeff_v : nullptr;
+  a.cus = (u32 *)p.cus; a.modes = p.intra_modes; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs;
   a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
   a.width = width; a.height = height;
   a.chroma = chroma; a.rdpcm = ll->implicit_rdpcm ? 1 : 0;
@@ -346,8 +342,12 @@ int kvz_hip_inter_residual_frame_lossless(const kvz_hip_ref_picture *src, kvz_hi
                                           kvz_hip_inter_residual_cost *costs, const kvz_hip_lossless *ll, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  return lossless_frame(__func__, false, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
-                        nullptr, ll, s);
+  if (!ll) return kvzhip::invalid_arg(__func__);
+  const kvz_hip_inter_residual_params flat = { 0, 0, 0, 0, ll->chroma, 0 };     // what the check of the arguments reads of them
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         nullptr, &flat);
+  return packed ? lossless_frame(__func__, false, p, nullptr, ll, s) : kvzhip::invalid_arg(__func__);
 }
 
 int kvz_hip_intra_recon_frame_lossless(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
@@ -357,8 +357,12 @@ int kvz_hip_intra_recon_frame_lossless(const kvz_hip_ref_picture *src, kvz_hip_p
                                        kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  return lossless_frame(__func__, true, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
-                        tiles, ll, s);
+  if (!ll) return kvzhip::invalid_arg(__func__);
+  const kvz_hip_inter_residual_params flat = { 0, 0, 0, 0, ll->chroma, 0 };     // what the check of the arguments reads of them
+  kvz_hip_chain_picture p;
+  const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
+                                         nullptr, &flat);
+  return packed ? lossless_frame(__func__, true, p, tiles, ll, s) : kvzhip::invalid_arg(__func__);
 }
 
 }  // extern "C"

@@ -9,7 +9,14 @@ program does not depend on what else the process has loaded, and run as a child 
 
 The expected indices of the defects that tests/test_gpu_chain_multi.py and tests/test_gpu_chain_multi_ts.py plant are the ones those tests
 assert; the expected reasons are the message strings of the entries as they stood before the checks moved into the header, copied here
-as literals."""
+as literals.
+
+The same program runs the named checks of the options -- tables, the transform-skip source with its output, the one-QP rule -- which
+the single-picture entries and the record checks share, and the packing of a single-picture entry's loose arguments into a record.
+The one-QP rule is held against what make_consts (quant_core.h, which this program cannot include) decided for the probe that the
+tiled intra entries used to make, make_consts(4, 0, 0) and make_consts(4, 2, 2): a host program that includes quant_core.h printed
+that table once for every QP in -64..127, intra and inter slices, with and without sign hiding: refused below 0, accepted from 0."""
+import functools
 import os
 import subprocess
 
@@ -124,6 +131,64 @@ static void ts_case(const char *name, int n, bool lists, bool skip, const std::f
   ts_records(name, n, r);
 }
 
+// ---- the named checks of the options, and the record of a single-picture entry ----
+static void option(const std::string &name, bool ok) { printf("option %s: %s\n", name.c_str(), ok ? "accepted" : "refused"); }
+template <typename T> static T *plus(T *p, int bytes) { return (T *)((uintptr_t)p + (unsigned)bytes); }
+
+// the fields of a record as the loose arguments of an entry, packed again
+static bool packs_to_itself(const kvz_hip_chain_picture &c)
+{
+  kvz_hip_chain_picture p;
+  memset(&p, 0xa5, sizeof p);
+  if (!chain_picture_pack(&p, &c.src, c.rec_y, c.stride_y, c.rec_u, c.rec_v, c.stride_c, c.cus, c.intra_modes, c.coeff_y, c.coeff_u, c.coeff_v, c.cbf_out,
+                          c.costs, c.lcu_qp, &c.params))
+    return false;
+  return p.src.y == c.src.y && p.src.u == c.src.u && p.src.v == c.src.v && p.src.stride_y == c.src.stride_y && p.src.stride_c == c.src.stride_c &&
+         p.src.width == c.src.width && p.src.height == c.src.height && p.rec_y == c.rec_y && p.rec_u == c.rec_u && p.rec_v == c.rec_v &&
+         p.stride_y == c.stride_y && p.stride_c == c.stride_c && p.cus == c.cus && p.intra_modes == c.intra_modes && p.coeff_y == c.coeff_y &&
+         p.coeff_u == c.coeff_u && p.coeff_v == c.coeff_v && p.cbf_out == c.cbf_out && p.costs == c.costs && p.lcu_qp == c.lcu_qp &&
+         p.params.qp == c.params.qp && p.params.slice_is_intra == c.params.slice_is_intra && p.params.signhide == c.params.signhide &&
+         p.params.scaling_list == c.params.scaling_list && p.params.chroma == c.params.chroma;
+}
+
+static void option_cases()
+{
+  static kvz_hip_trskip negative_cost = { -1, 0, nullptr }, negative_with_array = { -1, 0, fake<int32_t>(9, 0) },
+                        misaligned_array = { 5, 0, plus(fake<int32_t>(9, 0), 2) };
+  const int32_t *q = fake<int32_t>(0, 13), *d = fake<int32_t>(0, 14);
+  uint8_t *out = fake<uint8_t>(0, 15);
+  option("tables both", chain_tables_ok({ q, d }));
+  option("tables without quant", chain_tables_ok({ nullptr, d }));
+  option("tables without dequant", chain_tables_ok({ q, nullptr }));
+  option("tables quant + 4", chain_tables_ok({ plus(q, 4), d }));
+  option("tables quant + 8", chain_tables_ok({ plus(q, 8), d }));
+  option("tables dequant + 4", chain_tables_ok({ q, plus(d, 4) }));
+  option("tables dequant + 8", chain_tables_ok({ q, plus(d, 8) }));
+  option("ts with tr_skip_out", chain_trskip_ok(&skip_by_cost, out));
+  option("ts without tr_skip_out", chain_trskip_ok(&skip_by_cost, nullptr));
+  option("ts bit_cost -1", chain_trskip_ok(&negative_cost, out));
+  option("ts bit_cost -1 with lcu_bit_cost", chain_trskip_ok(&negative_with_array, out));
+  option("ts lcu_bit_cost + 2", chain_trskip_ok(&misaligned_array, out));
+  for (int qp = -64; qp <= 127; ++qp) {
+    kvz_hip_chain_picture p = clean(0);
+    p.params.qp = qp;
+    option("one qp " + std::to_string(qp), chain_one_qp_ok(p));
+    p.lcu_qp = fake<int8_t>(0, 16);
+    option("lcu_qp beside qp " + std::to_string(qp), chain_one_qp_ok(p));
+  }
+  for (int i = 0; i < 2; ++i) {
+    kvz_hip_chain_picture c = clean(i);
+    if (i) { c.lcu_qp = fake<int8_t>(i, 16); c.params.slice_is_intra = 1; c.params.signhide = 1; c.params.scaling_list = 1; }
+    option("record " + std::to_string(i) + " packed from its fields", packs_to_itself(c));
+  }
+  const kvz_hip_chain_picture c = clean(0);
+  kvz_hip_chain_picture p;
+  option("pack without src", chain_picture_pack(&p, nullptr, c.rec_y, c.stride_y, c.rec_u, c.rec_v, c.stride_c, c.cus, c.intra_modes, c.coeff_y, c.coeff_u,
+                                                c.coeff_v, c.cbf_out, c.costs, c.lcu_qp, &c.params));
+  option("pack without params", chain_picture_pack(&p, &c.src, c.rec_y, c.stride_y, c.rec_u, c.rec_v, c.stride_c, c.cus, c.intra_modes, c.coeff_y, c.coeff_u,
+                                                   c.coeff_v, c.cbf_out, c.costs, c.lcu_qp, nullptr));
+}
+
 static kvz_hip_tile_grid grid_of(int cols, int rows, int lcus_x, int lcus_y)
 {
   kvz_hip_tile_grid g;
@@ -230,6 +295,7 @@ int main()
   ts_case("qp before shared", 3, true, false, [](R *r) { r[2].pic.params.qp = -1; r[2].pic.rec_y = r[0].pic.rec_y; });
   ts_case("grid before shared", 3, false, true, [](R *r) { r[2].grid = &short_grid; r[2].pic.rec_y = r[0].pic.rec_y; });
   ts_case("record 1 before record 2", 3, true, true, [](R *r) { r[1].pic.cus = r[0].pic.cus; r[2].ts = nullptr; });
+  option_cases();
   return 0;
 }
 """
@@ -302,21 +368,66 @@ EXPECTED = {
 }
 
 
-def test_record_checks_report_the_first_refused_record_and_its_reason(tmp_path):
-    src, exe = tmp_path / "chain_host_checks.cpp", tmp_path / "chain_host_checks"
-    src.write_text(PROGRAM)
-    cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-           "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "kvazaar_amd", "csrc"), str(src), "-o", str(exe)]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert r.returncode == 0, r.stdout
-    got = {}
+# the named checks and the packing: True where accepted
+OPTIONS = {
+    "tables both": True,
+    "tables without quant": False,
+    "tables without dequant": False,
+    "tables quant + 4": False,
+    "tables quant + 8": False,
+    "tables dequant + 4": False,
+    "tables dequant + 8": False,
+    "ts with tr_skip_out": True,
+    "ts without tr_skip_out": False,
+    "ts bit_cost -1": False,
+    "ts bit_cost -1 with lcu_bit_cost": True,
+    "ts lcu_bit_cost + 2": False,
+    "record 0 packed from its fields": True,
+    "record 1 packed from its fields": True,
+    "pack without src": False,
+    "pack without params": False,
+}
+# what make_consts decided for the probe of the one-QP rule (the module's docstring): refused below 0, accepted from 0
+OPTIONS.update({"one qp %d" % qp: qp >= 0 for qp in range(-64, 128)})
+OPTIONS.update({"lcu_qp beside qp %d" % qp: True for qp in range(-64, 128)})
+
+
+@functools.lru_cache(maxsize=None)
+def program_output():
+    """the program's lines, compiled and run once: ({case: {stage: verdict}}, {option: accepted})"""
+    import tempfile
+    with tempfile.TemporaryDirectory() as tmp:
+        src, exe = os.path.join(tmp, "chain_host_checks.cpp"), os.path.join(tmp, "chain_host_checks")
+        with open(src, "w") as f:
+            f.write(PROGRAM)
+        cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+               "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "kvazaar_amd", "csrc"), src, "-o", exe]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+        r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert r.returncode == 0, r.stdout
+    got, options = {}, {}
     for line in r.stdout.splitlines():
         case, _, verdict = line.partition(": ")
+        if case.startswith("option "):
+            assert verdict in ("accepted", "refused"), line
+            options[case[len("option "):]] = verdict == "accepted"
+            continue
         name, _, stage = case.rpartition("/")
         index, _, reason = verdict.partition(" ")
         got.setdefault(name, {})[stage] = None if verdict == "ok" else (int(index), reason)
+    return got, options
+
+
+def test_record_checks_report_the_first_refused_record_and_its_reason():
+    got, _ = program_output()
     assert sorted(got) == sorted(EXPECTED)
     for name, (inter, intra) in EXPECTED.items():
         assert got[name] == {"inter": inter, "intra": intra}, name
+
+
+def test_option_checks_and_the_record_of_a_single_picture_entry():
+    _, options = program_output()
+    assert sorted(options) == sorted(OPTIONS)
+    for name, accepted in OPTIONS.items():
+        assert options[name] == accepted, name
