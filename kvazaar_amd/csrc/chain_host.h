@@ -1,14 +1,14 @@
-// chain_host.h -- the host side that the multi-picture entries of the picture chain share (kvz_hip_*_frames, kvz_hip_*_frames_ts and the
-// filter stages' kvz_hip_cu_qp_frames, kvz_hip_deblock_frames, kvz_hip_sao_stats_frames, kvz_hip_sao_frames, kvz_hip_inter_recon_frames):
-// the refusal that names a record, the prologue on the record count, what every residual-stage entry requires of one picture's
-// arguments and of each option (the single-picture entries pack their arguments into a record and ask the same checks), the checks of
-// a kvz_hip_chain_picture / kvz_hip_chain_picture_ts record, the tile grid on the host with the pool of
-// boundaries that the grids of a call share, and the record checks of the hash stage (kvz_hip_picture_hash_frame(s),
-// kvz_hip_array_checksum_batch; tests/test_picture_hash_abi.py runs those without a device).
+// chain_host.h -- the host side that the entries of the picture chain share, single-picture and multi-picture alike: the residual
+// stages (kvz_hip_inter_residual_*, kvz_hip_intra_recon_*), the filter stages (kvz_hip_cu_qp_*, kvz_hip_deblock_*, kvz_hip_sao_stats_*,
+// kvz_hip_sao_*), motion compensation (kvz_hip_inter_recon_*) and the hash stage (kvz_hip_picture_hash_frame(s),
+// kvz_hip_array_checksum_batch): the refusal that names a record, the prologue on the record count, the size and plane rules, the tile
+// grid on the host with the pool of boundaries of a call, and per stage the rules of one picture as predicates on the stage's record,
+// the pack of a single-picture entry's arguments into that record, and why a record of a call is refused.  Each rule is written once.
 //
 // Host only: pointer and integer arithmetic on the structs of kvz_hip.h, which compare pointers and never follow them (a
-// kvz_hip_tile_grid and a kvz_hip_trskip are host memory and are read).  No device code and no HIP call, so a plain C++17 compiler
-// takes this header with kvz_hip.h alone (tests/test_chain_host_checks.py runs the record checks that way, without a device).
+// kvz_hip_tile_grid, a kvz_hip_trskip and the pool of reference pictures are host memory and are read).  No device code and no HIP call,
+// so a plain C++17 compiler takes this header with kvz_hip.h alone (tests/test_chain_host_checks.py, test_filter_host_checks.py and
+// test_picture_hash_abi.py run the record checks that way, without a device).
 #pragma once
 
 #include <stddef.h>
@@ -23,20 +23,34 @@ void set_error_msg(const char *what);           // api.hip
 
 namespace {
 
-// ---- refusing record i of a call ----
+// ---- refusing record i of a call; i < 0 (refuse_entry): a single-picture entry's refusal under a text of its own ----
 inline int refuse_picture(const char *entry, int i, const char *why)
 {
   char msg[200];
-  snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (%s)", entry, i, why);
+  if (i < 0) snprintf(msg, sizeof msg, "%s: %s", entry, why);
+  else snprintf(msg, sizeof msg, "%s: invalid argument in picture %d (%s)", entry, i, why);
   kvzhip::set_error_msg(msg);
   return KVZ_HIP_ERR_INVALID;
 }
+inline int refuse_entry(const char *entry, const char *why) { return refuse_picture(entry, -1, why); }
 
 // How every multi-picture entry begins: a context, no pictures is a no-op, and the count in range (KVZ_CHECK_CTX, kvz_hip_internal.h)
 #define KVZ_CHAIN_PROLOGUE(pictures, n_pictures)                                                                               \
   KVZ_CHECK_CTX();                                                                                                             \
   if ((n_pictures) == 0) return KVZ_HIP_OK;                                                                                    \
   if (!(pictures) || (n_pictures) < 0 || (n_pictures) > KVZ_HIP_MAX_CHAIN_PICTURES) return kvzhip::invalid_arg(__func__)
+
+// ---- the size rule and the plane rule ----
+// no upper bound: the single deblocking entries and motion compensation, which carry a size in an int and never in a record's 16 bits
+inline bool picture_ok_any_size(int width, int height) { return width >= 8 && height >= 8 && !((width | height) & 7); }
+// width / height: multiples of 8 (the minimum CU) in 8..16384
+inline bool picture_ok(int width, int height) { return picture_ok_any_size(width, height) && width <= 16384 && height <= 16384; }
+// no alignment: motion compensation, whose kernels read their windows at any byte offset and so ask nothing of a plane's base
+inline bool plane_ok_unaligned(const void *p, uint32_t stride, int w) { return p && stride >= (uint32_t)w; }
+// a plane that is read or written by the dword: 4-byte aligned base and stride, stride >= the width
+inline bool plane_ok(const void *p, uint32_t stride, int w) { return plane_ok_unaligned(p, stride, w) && !((uintptr_t)p & 3) && !(stride & 3); }
+// the u and v planes of a 4:2:0 picture, which share a stride
+inline bool chroma_planes_ok(const void *u, const void *v, uint32_t stride_c, int w) { return plane_ok(u, stride_c, w >> 1) && plane_ok(v, stride_c, w >> 1); }
 
 // ---- the tile grid on the host ----
 static_assert(sizeof(kvz_hip_tile_grid) == 392 && KVZ_HIP_MAX_TILES_PER_DIM == 48, "layout documented in kvz_hip.h");
@@ -118,8 +132,7 @@ inline bool chain_picture_args_ok(const kvz_hip_chain_picture &p, bool intra, bo
       ((uintptr_t)p.costs & 3))
     return false;
   const int width = p.src.width, height = p.src.height;
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || p.stride_y < (uint32_t)width ||
-      p.src.stride_y < (uint32_t)width || (p.params.scaling_list != 0) != lists)
+  if (!picture_ok(width, height) || p.stride_y < (uint32_t)width || p.src.stride_y < (uint32_t)width || (p.params.scaling_list != 0) != lists)
     return false;
   if (p.params.chroma && (!p.rec_u || !p.rec_v || !p.coeff_u || !p.coeff_v || !p.src.u || !p.src.v || p.stride_c < (uint32_t)(width >> 1) ||
                           p.src.stride_c < (uint32_t)(width >> 1) || (((uintptr_t)p.coeff_u | (uintptr_t)p.coeff_v) & 15)))
@@ -202,26 +215,19 @@ inline const char *chain_record_ts_shared(const kvz_hip_chain_picture_ts *pictur
 static_assert(sizeof(kvz_hip_lcu_hash) == 24 && sizeof(kvz_hip_picture_hash) == 40 && sizeof(kvz_hip_hash_picture) == 104 &&
               sizeof(kvz_hip_hash_plane) == 24, "layout documented in kvz_hip.h");
 
-// the plane rule of the whole-picture SAO entries: 4-byte aligned base and stride, stride >= the width
-inline bool hash_plane_ok(const void *p, uint32_t stride, int w)
-{
-  return p && !((uintptr_t)p & 3) && !(stride & 3) && stride >= (uint32_t)w;
-}
-
 // kvz_hip_picture_hash_frames, and kvz_hip_picture_hash_frame with its arguments as record 0
 inline const char *hash_record_why(const kvz_hip_hash_picture *pictures, int i)
 {
   const kvz_hip_hash_picture &p = pictures[i];
   const int width = p.width, height = p.height;
   if (!p.lcu_out || !p.out || ((uintptr_t)p.lcu_out & 3) || ((uintptr_t)p.out & 7)) return "lcu_out or out is null or misaligned";
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384 || !hash_plane_ok(p.rec_y, p.stride_y, width))
+  if (!picture_ok(width, height) || !plane_ok(p.rec_y, p.stride_y, width))
     return "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8";
-  if (p.chroma && (!hash_plane_ok(p.rec_u, p.stride_c, width >> 1) || !hash_plane_ok(p.rec_v, p.stride_c, width >> 1)))
+  if (p.chroma && !chroma_planes_ok(p.rec_u, p.rec_v, p.stride_c, width))
     return "a chroma plane is null or misaligned, or its stride is";
   if (p.src.y) {
     if (p.src.width != width || p.src.height != height) return "src.width / src.height differ from width / height";
-    if (!hash_plane_ok(p.src.y, p.src.stride_y, width) ||
-        (p.chroma && (!hash_plane_ok(p.src.u, p.src.stride_c, width >> 1) || !hash_plane_ok(p.src.v, p.src.stride_c, width >> 1))))
+    if (!plane_ok(p.src.y, p.src.stride_y, width) || (p.chroma && !chroma_planes_ok(p.src.u, p.src.v, p.src.stride_c, width)))
       return "a src plane is null or misaligned, or its stride is";
   }
   for (int j = 0; j < i; ++j)
@@ -240,6 +246,178 @@ inline const char *hash_plane_why(const kvz_hip_hash_plane &p)
   if (!p.data) return "data is null";
   if (!hash_plane_blocks(p.width, p.height)) return "width or height outside 1..65536";
   if (p.stride < (uint32_t)p.width) return "stride below the width";
+  return nullptr;
+}
+
+// ---- the filter stages: the QP map, deblocking, the SAO statistics and SAO, on a kvz_hip_filter_picture ----
+// A single-picture entry packs its loose arguments into the record that kvz_hip.h says they are (-> false without an argument that is
+// copied) and composes the predicates of its stage under its own messages.  A multi-picture entry asks filter_records_why with the
+// stage's X_record_why and X_output_shared: the order of the checks is part of the interface (tests/test_filter_host_checks.py).
+typedef kvz_hip_filter_picture filter_pic;
+inline const char *const PLANES_AND_STRIDES = "planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8";
+inline const char *filter_chroma_why(const filter_pic &p) { return p.deblock.chroma != p.chroma ? "deblock.chroma differs from chroma" : nullptr; }
+
+// The records of a call, all checked before anything is launched: per record its own checks (why), for a stage that takes tiles its
+// grid into the pool of boundaries (tiles[i]; tiles == NULL: the stage takes none), then its outputs against those of the earlier
+// records (shared).  -> the reason, with *at the record that is refused, or nullptr
+template <typename WHY, typename SHARED>
+inline const char *filter_records_why(const filter_pic *pictures, int n, WHY why, SHARED shared, uint16_t *bounds, int &used, pic_tiles *tiles, int *at)
+{
+  for (int &i = *at = 0; i < n; ++i) {
+    const filter_pic &p = pictures[i];
+    kvz_hip_tile_grid g;
+    if (const char *w = why(p)) return w;
+    if (tiles && !tile_grid_make(p.grid, p.width, p.height, &g)) return "invalid tile grid";
+    if (tiles && !tile_pool_add(p.grid, g, bounds, used, &tiles[i])) return "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record";
+    for (int j = 0; j < i; ++j)
+      if (shared(p, pictures[j])) return "an output shared with another picture";
+  }
+  return nullptr;
+}
+
+// -- the QP map.  kvz_hip_cu_qp_frame has raster runs for chains, which a record cannot say: it packs chain_rows 0 and keeps chain_lcus
+inline bool cu_qp_pack(filter_pic *p, kvz_hip_cu_info *cus, const uint8_t *cbf, int width, int height, const int8_t *lcu_qp, int8_t *lcu_last_qp,
+                       const kvz_hip_tile_grid *grid, const kvz_hip_cu_qp_tiles_params *params)
+{
+  if (params) *p = { .width = width, .height = height, .cus = cus, .cbf = cbf, .lcu_qp = lcu_qp, .lcu_last_qp = lcu_last_qp, .grid = grid, .cu_qp = *params };
+  return params != nullptr;
+}
+inline bool cu_qp_arrays_ok(const filter_pic &p) { return p.cus && p.cbf && p.lcu_qp && p.lcu_last_qp && !((uintptr_t)p.cus & 3); }
+inline bool cu_qp_chains_ok(const filter_pic &p) { return p.cu_qp.start_qp >= 0 && p.cu_qp.start_qp <= 51 && (p.cu_qp.chain_rows == 0 || p.cu_qp.chain_rows == 1); }
+inline const char *cu_qp_record_why(const filter_pic &p)
+{
+  if (!cu_qp_arrays_ok(p)) return "a null pointer or a misaligned cus";
+  if (!picture_ok(p.width, p.height)) return "width / height must be multiples of 8 in 8..16384";
+  if (!cu_qp_chains_ok(p)) return "start_qp outside 0..51 or chain_rows other than 0 and 1";
+  return filter_chroma_why(p);
+}
+inline bool cu_qp_output_shared(const filter_pic &p, const filter_pic &o) { return p.cus == o.cus || p.lcu_last_qp == o.lcu_last_qp; }
+
+// -- deblocking.  The single entries carry the size in an int and set no upper bound; the record check adds picture_ok, because the
+// kernel's record stores width and height in 16 bits
+inline bool deblock_pack(filter_pic *p, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, int width,
+                         int height, const kvz_hip_cu_info *cus, const kvz_hip_tile_grid *grid, const kvz_hip_deblock_params *params)
+{
+  if (params) *p = { .width = width, .height = height, .chroma = params->chroma, .rec_y = rec_y, .rec_u = rec_u, .rec_v = rec_v, .stride_y = stride_y,
+                     .stride_c = stride_c, .cus = const_cast<kvz_hip_cu_info *>(cus), .grid = grid, .deblock = *params };
+  return params != nullptr;
+}
+inline bool deblock_luma_ok(const filter_pic &p) { return picture_ok_any_size(p.width, p.height) && plane_ok(p.rec_y, p.stride_y, p.width) && p.cus && !((uintptr_t)p.cus & 3); }
+inline bool deblock_chroma_ok(const filter_pic &p) { return !p.chroma || chroma_planes_ok(p.rec_u, p.rec_v, p.stride_c, p.width); }
+inline const char *deblock_record_why(const filter_pic &p)
+{
+  if (const char *why = filter_chroma_why(p)) return why;
+  if (picture_ok(p.width, p.height) && deblock_luma_ok(p) && deblock_chroma_ok(p)) return nullptr;
+  return "planes and the SCU map must be 4-byte aligned, width / height multiples of 8 in 8..16384, strides >= the width";
+}
+inline bool deblock_output_shared(const filter_pic &p, const filter_pic &o) { return p.rec_y == o.rec_y; }
+
+// -- the SAO statistics
+inline bool sao_stats_pack(filter_pic *p, const kvz_hip_ref_picture *src, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u,
+                           const kvz_hip_pixel *rec_v, uint32_t stride_c, int chroma, kvz_hip_sao_lcu_stats *stats, kvz_hip_sao_lcu_cand *cands)
+{
+  if (src) *p = { .width = src->width, .height = src->height, .chroma = chroma, .src = *src, .rec_y = const_cast<kvz_hip_pixel *>(rec_y),
+                  .rec_u = const_cast<kvz_hip_pixel *>(rec_u), .rec_v = const_cast<kvz_hip_pixel *>(rec_v), .stride_y = stride_y, .stride_c = stride_c,
+                  .stats = stats, .cands = cands };
+  return src != nullptr;
+}
+inline bool sao_stats_out_ok(const filter_pic &p) { return p.stats && !((uintptr_t)p.stats & 3) && !((uintptr_t)p.cands & 3); }
+inline bool sao_stats_luma_ok(const filter_pic &p) { return picture_ok(p.width, p.height) && plane_ok(p.src.y, p.src.stride_y, p.width) && plane_ok(p.rec_y, p.stride_y, p.width); }
+inline bool sao_stats_chroma_ok(const filter_pic &p)
+{
+  return !p.chroma || (chroma_planes_ok(p.src.u, p.src.v, p.src.stride_c, p.width) && chroma_planes_ok(p.rec_u, p.rec_v, p.stride_c, p.width));
+}
+inline const char *sao_stats_record_why(const filter_pic &p)
+{
+  if (const char *why = filter_chroma_why(p)) return why;
+  if (p.src.width != p.width || p.src.height != p.height) return "src.width / src.height differ from width / height";
+  if (!sao_stats_out_ok(p)) return "stats is null, or stats or cands misaligned";
+  if (!sao_stats_luma_ok(p)) return PLANES_AND_STRIDES;
+  return sao_stats_chroma_ok(p) ? nullptr : "a chroma plane is null or misaligned, or its stride is";
+}
+inline bool sao_stats_output_shared(const filter_pic &p, const filter_pic &o) { return p.stats == o.stats || (p.cands && p.cands == o.cands); }
+
+// -- SAO: nothing that is copied, so its pack refuses nothing
+inline void sao_pack(filter_pic *p, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u, const kvz_hip_pixel *rec_v, uint32_t stride_c,
+                     kvz_hip_pixel *dst_y, uint32_t dst_stride_y, kvz_hip_pixel *dst_u, kvz_hip_pixel *dst_v, uint32_t dst_stride_c, int width, int height,
+                     const kvz_hip_sao_info *sao_luma, const kvz_hip_sao_info *sao_chroma, int chroma, const kvz_hip_tile_grid *grid)
+{
+  *p = { .width = width, .height = height, .chroma = chroma, .rec_y = const_cast<kvz_hip_pixel *>(rec_y), .rec_u = const_cast<kvz_hip_pixel *>(rec_u),
+         .rec_v = const_cast<kvz_hip_pixel *>(rec_v), .stride_y = stride_y, .stride_c = stride_c, .dst_y = dst_y, .dst_u = dst_u, .dst_v = dst_v,
+         .dst_stride_y = dst_stride_y, .dst_stride_c = dst_stride_c, .sao_luma = sao_luma, .sao_chroma = sao_chroma, .grid = grid };
+}
+inline bool sao_luma_info_ok(const filter_pic &p) { return p.sao_luma && !((uintptr_t)p.sao_luma & 3) && p.dst_y != p.rec_y; }
+inline bool sao_luma_planes_ok(const filter_pic &p) { return picture_ok(p.width, p.height) && plane_ok(p.rec_y, p.stride_y, p.width) && plane_ok(p.dst_y, p.dst_stride_y, p.width); }
+inline bool sao_chroma_ok(const filter_pic &p)
+{
+  return !p.chroma || (p.sao_chroma && !((uintptr_t)p.sao_chroma & 3) && p.dst_u != p.rec_u && p.dst_v != p.rec_v &&
+                       chroma_planes_ok(p.rec_u, p.rec_v, p.stride_c, p.width) && chroma_planes_ok(p.dst_u, p.dst_v, p.dst_stride_c, p.width));
+}
+inline const char *sao_record_why(const filter_pic &p)
+{
+  if (const char *why = filter_chroma_why(p)) return why;
+  if (!sao_luma_info_ok(p)) return "sao_luma is null or misaligned, or dst_y is rec_y";
+  if (!sao_luma_planes_ok(p)) return PLANES_AND_STRIDES;
+  return sao_chroma_ok(p) ? nullptr : "sao_chroma or a chroma plane is null or misaligned, a chroma stride is, or a dst plane is its rec plane";
+}
+inline bool sao_output_shared(const filter_pic &p, const filter_pic &o) { return p.dst_y == o.dst_y; }
+
+// ---- motion compensation, on a kvz_hip_recon_picture with its pool of reference pictures: no aligned planes, no size cap ----
+// a table entry as the entries take it for a picture of width x height: chroma = the picture is 4:2:0
+inline bool ref_ok(const kvz_hip_ref_picture &r, int chroma, int width, int height)
+{
+  if (r.width != width || r.height != height || !plane_ok_unaligned(r.y, r.stride_y, width)) return false;
+  return !chroma || (plane_ok_unaligned(r.u, r.stride_c, width >> 1) && plane_ok_unaligned(r.v, r.stride_c, width >> 1));
+}
+inline bool refs_ok(const kvz_hip_ref_picture *refs, int n_refs, int chroma, int width, int height)
+{
+  for (int i = 0; i < n_refs; ++i)
+    if (!ref_ok(refs[i], chroma, width, height)) return false;
+  return true;
+}
+// kvz_hip_inter_recon_frame: its table is the pool, and reference i is pool picture i
+inline bool recon_pack(kvz_hip_recon_picture *p, kvz_hip_pixel *pred_y, uint32_t stride_y, kvz_hip_pixel *pred_u, kvz_hip_pixel *pred_v, uint32_t stride_c,
+                       int width, int height, const kvz_hip_cu_info *cus, const kvz_hip_ref_picture *refs, const kvz_hip_inter_recon_params *params)
+{
+  if (refs && params) *p = { .pred_y = pred_y, .pred_u = pred_u, .pred_v = pred_v, .stride_y = stride_y, .stride_c = stride_c, .width = width, .height = height,
+                             .cus = cus, .refs = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15 }, .params = *params };
+  return refs && params;
+}
+inline bool recon_arrays_ok(const kvz_hip_recon_picture &p) { return p.pred_y && p.cus && !((uintptr_t)p.cus & 3); }
+inline bool recon_luma_ok(const kvz_hip_recon_picture &p) { return picture_ok_any_size(p.width, p.height) && plane_ok_unaligned(p.pred_y, p.stride_y, p.width); }
+inline bool recon_n_refs_ok(const kvz_hip_recon_picture &p) { return p.params.n_refs >= 1 && p.params.n_refs <= KVZ_HIP_MAX_REF_PICTURES; }
+inline bool recon_chroma_ok(const kvz_hip_recon_picture &p)
+{
+  return !p.params.chroma || (plane_ok_unaligned(p.pred_u, p.stride_c, p.width >> 1) && plane_ok_unaligned(p.pred_v, p.stride_c, p.width >> 1));
+}
+// The records of kvz_hip_inter_recon_frames, all checked before anything is launched, then the pass over the destinations.  named[r]:
+// a record names pool picture r; first_wg[i]: the workgroups in front of record i, four 16 x 16 tiles each; groups: all of them.
+// -> the reason, with *at the record that is refused, or nullptr
+inline const char *recon_records_why(const kvz_hip_recon_picture *pictures, int n, const kvz_hip_ref_picture *pool, int n_pool, bool *named, int *first_wg,
+                                     unsigned long long &groups, int *at)
+{
+  for (int &i = *at = 0; i < n; ++i) {
+    const kvz_hip_recon_picture &p = pictures[i];
+    if (!recon_arrays_ok(p)) return "pred_y or cus is null, or cus misaligned";
+    if (!recon_luma_ok(p)) return "width / height must be multiples of 8, stride_y >= the width";
+    if (!recon_n_refs_ok(p)) return "n_refs outside 1..16";
+    if (!recon_chroma_ok(p)) return "a chroma plane is null, or stride_c below half the width";
+    for (int r = 0; r < p.params.n_refs; ++r) {
+      if (p.refs[r] >= n_pool) return "a reference index outside the pool";
+      if (!ref_ok(pool[p.refs[r]], p.params.chroma, p.width, p.height)) return "a named pool picture of another size, with a missing plane or a short stride";
+      named[p.refs[r]] = true;
+    }
+    for (int j = 0; j < i; ++j)
+      if (p.pred_y == pictures[j].pred_y) return "pred_y shared with another picture";
+    first_wg[i] = (int)groups;
+    groups += ((unsigned long long)((p.width + 15) >> 4) * (unsigned long long)((p.height + 15) >> 4) + 3) / 4;
+    if (groups > 0x7fffffffull) return "the pictures of the call exceed the grid";
+  }
+  // no destination may be a plane of a pool picture that some record names
+  for (int &i = *at = 0; i < n; ++i)
+    for (int r = 0; r < n_pool; ++r)
+      if (const kvz_hip_recon_picture &p = pictures[i]; named[r] && (p.pred_y == pool[r].y || (p.params.chroma && (p.pred_u == pool[r].u || p.pred_v == pool[r].v))))
+        return "a destination plane is a named pool plane";
   return nullptr;
 }
 

@@ -24,24 +24,17 @@ int kvz_hip_cu_qp_frame(kvz_hip_cu_info *cus, const uint8_t *cbf, int width, int
                         const kvz_hip_cu_qp_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!cus || !cbf || !lcu_qp || !lcu_last_qp || !params || ((uintptr_t)cus & 3)) return kvzhip::invalid_arg(__func__);
-  if (width < 8 || height < 8 || ((width | height) & 7) || width > 16384 || height > 16384) return kvzhip::invalid_arg(__func__);
-  const int lcus_x = (width + 63) >> 6, lcus_y = (height + 63) >> 6, n_lcu = lcus_x * lcus_y;
-  if (params->start_qp < 0 || params->start_qp > 51 || params->chain_lcus < 0 || params->chain_lcus % lcus_x) return kvzhip::invalid_arg(__func__);
+  if (!params) return kvzhip::invalid_arg(__func__);
+  // the chains of this entry alone, which the record cannot say: raster runs of chain_lcus LCUs, whole LCU rows
+  const kvz_hip_cu_qp_tiles_params rows = { params->start_qp, 0 };
+  kvz_hip_filter_picture p;
+  if (!cu_qp_pack(&p, cus, cbf, width, height, lcu_qp, lcu_last_qp, nullptr, &rows) || !cu_qp_arrays_ok(p) || !picture_ok(width, height) || !cu_qp_chains_ok(p))
+    return kvzhip::invalid_arg(__func__);
+  const int lcus_x = (width + 63) >> 6, n_lcu = lcus_x * ((height + 63) >> 6);
+  if (params->chain_lcus < 0 || params->chain_lcus % lcus_x) return kvzhip::invalid_arg(__func__);
   const int chain = params->chain_lcus ? params->chain_lcus : n_lcu;
-  cu_qp_args a;
-  a.cus = (u32 *)cus; a.cbf = cbf; a.lcu_qp = lcu_qp; a.lcu_last_qp = lcu_last_qp;
-  a.cus_stride = width >> 2; a.lcus_x = lcus_x;
-  a.width = width; a.height = height;
-  hipStream_t st = ctx_stream(s);
   // the launch sequence depends on width, height and chain_lcus alone
-  hipLaunchKernelGGL(cu_qp_first_kernel, dim3((unsigned)lcus_x, (unsigned)lcus_y), dim3(256), 0, st, a);
-  KVZ_CHECK_LAUNCH("cu_qp_first_kernel");
-  hipLaunchKernelGGL(cu_qp_chain_kernel<>, dim3((unsigned)((n_lcu + chain - 1) / chain)), dim3(256), 0, st, lcu_last_qp, n_lcu, chain, params->start_qp);
-  KVZ_CHECK_LAUNCH("cu_qp_chain_kernel");
-  hipLaunchKernelGGL(cu_qp_write_kernel, dim3((unsigned)lcus_x, (unsigned)lcus_y), dim3(256), 0, st, a);
-  KVZ_CHECK_LAUNCH("cu_qp_write_kernel");
-  return KVZ_HIP_OK;
+  return cu_qp_launch(p, s, dim3((unsigned)((n_lcu + chain - 1) / chain)), n_lcu, chain);
 }
 
 }  // extern "C"

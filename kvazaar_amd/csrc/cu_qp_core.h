@@ -21,6 +21,13 @@ struct cu_qp_args {
   int cus_stride, lcus_x;
   int width, height;
 };
+// host: the argument of one picture, for the three entries
+inline void cu_qp_fill(cu_qp_args &a, const kvz_hip_filter_picture &p)
+{
+  a.cus = (u32 *)p.cus; a.cbf = p.cbf; a.lcu_qp = p.lcu_qp; a.lcu_last_qp = p.lcu_last_qp;
+  a.cus_stride = p.width >> 2; a.lcus_x = (p.width + 63) >> 6;
+  a.width = p.width; a.height = p.height;
+}
 
 __device__ __forceinline__ int wave_min(int v)
 {
@@ -177,6 +184,24 @@ __global__ __launch_bounds__(256) void cu_qp_write_kernel(cu_qp_args a)
 {
   __shared__ int s_min[4];
   cu_qp_write(a, blockIdx.x, blockIdx.y, s_min);
+}
+
+// kvz_hip_cu_qp_frame and kvz_hip_cu_qp_frame_tiles: launches 1 and 3 around the entry's scan.  chains: the grid of the scan; n_lcu,
+// chain_lcus and tiles (nothing or the tile_chains): what its kernel takes beside the record's lcu_last_qp and start_qp
+template <typename... TILES>
+int cu_qp_launch(const kvz_hip_filter_picture &p, kvz_hip_stream s, dim3 chains, int n_lcu, int chain_lcus, TILES... tiles)
+{
+  cu_qp_args a;
+  cu_qp_fill(a, p);
+  const dim3 lcus((unsigned)a.lcus_x, (unsigned)((p.height + 63) >> 6));
+  hipStream_t st = ctx_stream(s);
+  hipLaunchKernelGGL(cu_qp_first_kernel, lcus, dim3(256), 0, st, a);
+  KVZ_CHECK_LAUNCH("cu_qp_first_kernel");
+  hipLaunchKernelGGL(cu_qp_chain_kernel<TILES...>, chains, dim3(256), 0, st, p.lcu_last_qp, n_lcu, chain_lcus, p.cu_qp.start_qp, tiles...);
+  KVZ_CHECK_LAUNCH(sizeof...(TILES) ? "cu_qp_chain_kernel<tiles>" : "cu_qp_chain_kernel");
+  hipLaunchKernelGGL(cu_qp_write_kernel, lcus, dim3(256), 0, st, a);
+  KVZ_CHECK_LAUNCH("cu_qp_write_kernel");
+  return KVZ_HIP_OK;
 }
 
 }  // namespace

@@ -35,31 +35,21 @@ int kvz_hip_cu_qp_frames(const kvz_hip_filter_picture *pictures, int n_pictures,
   cu_qp_batch b;
   __builtin_memset(&b, 0, sizeof b);
   uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
-  int used = 0, lcus_x = 0, lcus_y = 0, chains_x = 0, chains_y = 0;
+  pic_tiles tiles[KVZ_HIP_MAX_CHAIN_PICTURES];
+  int used = 0, at = 0, lcus_x = 0, lcus_y = 0, chains_x = 0, chains_y = 0;
   // every record is checked before anything is launched: a refused call writes nothing
+  if (const char *why = filter_records_why(pictures, n_pictures, cu_qp_record_why, cu_qp_output_shared, bounds, used, tiles, &at))
+    return refuse_picture(__func__, at, why);
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_filter_picture &p = pictures[i];
-    if (!p.cus || !p.cbf || !p.lcu_qp || !p.lcu_last_qp || ((uintptr_t)p.cus & 3)) return refuse_picture(__func__, i, "a null pointer or a misaligned cus");
-    if (p.width < 8 || p.height < 8 || ((p.width | p.height) & 7) || p.width > 16384 || p.height > 16384)
-      return refuse_picture(__func__, i, "width / height must be multiples of 8 in 8..16384");
-    if (p.cu_qp.start_qp < 0 || p.cu_qp.start_qp > 51 || (p.cu_qp.chain_rows != 0 && p.cu_qp.chain_rows != 1))
-      return refuse_picture(__func__, i, "start_qp outside 0..51 or chain_rows other than 0 and 1");
-    if (p.deblock.chroma != p.chroma) return refuse_picture(__func__, i, "deblock.chroma differs from chroma");
-    kvz_hip_tile_grid g;
-    if (!tile_grid_make(p.grid, p.width, p.height, &g)) return refuse_picture(__func__, i, "invalid tile grid");
     cu_qp_pic &r = b.p[i];
-    if (!tile_pool_add(p.grid, g, bounds, used, &r.tiles))
-      return refuse_picture(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
-    for (int j = 0; j < i; ++j)
-      if (p.cus == pictures[j].cus || p.lcu_last_qp == pictures[j].lcu_last_qp) return refuse_picture(__func__, i, "an output shared with another picture");
-    r.a.cus = (u32 *)p.cus; r.a.cbf = p.cbf; r.a.lcu_qp = p.lcu_qp; r.a.lcu_last_qp = p.lcu_last_qp;
-    r.a.cus_stride = p.width >> 2; r.a.lcus_x = r.tiles.lcus_x;
-    r.a.width = p.width; r.a.height = p.height;
+    r.tiles = tiles[i];
+    cu_qp_fill(r.a, p);
     r.chain_rows = (u8)p.cu_qp.chain_rows; r.start_qp = (u8)p.cu_qp.start_qp;
     lcus_x = max(lcus_x, (int)r.tiles.lcus_x);
     lcus_y = max(lcus_y, (int)r.tiles.lcus_y);
-    chains_x = max(chains_x, g.cols);
-    chains_y = max(chains_y, p.cu_qp.chain_rows ? (int)r.tiles.lcus_y : g.rows);
+    chains_x = max(chains_x, (int)r.tiles.cols);
+    chains_y = max(chains_y, p.cu_qp.chain_rows ? (int)r.tiles.lcus_y : (int)r.tiles.rows);
   }
   tile_pool_pack(bounds, used, b.pool.bd);
   hipStream_t st = ctx_stream(s);

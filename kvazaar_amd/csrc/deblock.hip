@@ -21,6 +21,7 @@ extern "C" int kvz_hip_deblock_frame(kvz_hip_pixel *rec_y, uint32_t stride_y, kv
                                      kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!deblock_args_ok(__func__, rec_y, stride_y, rec_u, rec_v, stride_c, width, height, cus, params)) return KVZ_HIP_ERR_INVALID;
-  return deblock_launch(rec_y, stride_y, rec_u, rec_v, stride_c, width, height, cus, params, s);
+  kvz_hip_filter_picture p;
+  if (const int rc = deblock_refusal(__func__, deblock_pack(&p, rec_y, stride_y, rec_u, rec_v, stride_c, width, height, cus, nullptr, params) ? &p : nullptr)) return rc;
+  return deblock_launch(p, s);
 }

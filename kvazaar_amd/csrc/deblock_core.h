@@ -5,7 +5,6 @@
 
 #include "kvz_hip_internal.h"
 #include "tile_grid.h"
-#include <string>
 
 using namespace kvzhip;
 
@@ -285,33 +284,26 @@ __global__ __launch_bounds__(256) void deblock_pass_kernel(u8 *__restrict__ rec_
 }
 
 
-bool deblock_args_ok(const char *entry, const void *rec_y, uint32_t stride_y, const void *rec_u, const void *rec_v, uint32_t stride_c, int width,
-                     int height, const void *cus, const kvz_hip_deblock_params *params)
+// both single entries: what they refuse, under their own messages, or 0.  p: the packed record, NULL where deblock_pack refused
+int deblock_refusal(const char *entry, const kvz_hip_filter_picture *p)
 {
-  if (!rec_y || !cus || !params || width < 8 || height < 8 || ((width | height) & 7) || (stride_y & 3) || ((uintptr_t)rec_y & 3) ||
-      ((uintptr_t)cus & 3) || stride_y < (uint32_t)width) {
-    set_error_msg((std::string(entry) + ": planes and the SCU map must be 4-byte aligned, width / height multiples of 8 (the minimum CU)").c_str());
-    return false;
-  }
-  if (params->chroma && (!rec_u || !rec_v || stride_c < (uint32_t)(width >> 1) || (stride_c & 3) || (((uintptr_t)rec_u | (uintptr_t)rec_v) & 3))) {
-    kvzhip::invalid_arg(entry);
-    return false;
-  }
-  return true;
+  if (!p || !deblock_luma_ok(*p)) return refuse_entry(entry, "planes and the SCU map must be 4-byte aligned, width / height multiples of 8 (the minimum CU)");
+  return deblock_chroma_ok(*p) ? 0 : kvzhip::invalid_arg(entry);
 }
 
-// both entries; tiles: nothing or the grid
+// both single entries; tiles: nothing or the grid
 template <typename... TILES>
-int deblock_launch(kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, int width, int height,
-                   const kvz_hip_cu_info *cus, const kvz_hip_deblock_params *params, kvz_hip_stream s, TILES... tiles)
+int deblock_launch(const kvz_hip_filter_picture &p, kvz_hip_stream s, TILES... tiles)
 {
-  const frame_t f = { (const u32 *)cus, (width + 3) >> 2, width, height };
-  const size_t threads = (size_t)(width >> 3) * (size_t)(height >> 3) * 2;
+  const frame_t f = { (const u32 *)p.cus, (p.width + 3) >> 2, p.width, p.height };
+  const size_t threads = (size_t)(p.width >> 3) * (size_t)(p.height >> 3) * 2;
   const unsigned grid = (unsigned)((threads + 255) / 256);
   hipStream_t st = ctx_stream(s);
-  hipLaunchKernelGGL((deblock_pass_kernel<0, TILES...>), dim3(grid), dim3(256), 0, st, rec_y, stride_y, rec_u, rec_v, stride_c, f, *params, tiles...);
+  hipLaunchKernelGGL((deblock_pass_kernel<0, TILES...>), dim3(grid), dim3(256), 0, st, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, f, p.deblock,
+                     tiles...);
   KVZ_CHECK_LAUNCH("deblock_pass_kernel<vertical edges>");
-  hipLaunchKernelGGL((deblock_pass_kernel<1, TILES...>), dim3(grid), dim3(256), 0, st, rec_y, stride_y, rec_u, rec_v, stride_c, f, *params, tiles...);
+  hipLaunchKernelGGL((deblock_pass_kernel<1, TILES...>), dim3(grid), dim3(256), 0, st, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, f, p.deblock,
+                     tiles...);
   KVZ_CHECK_LAUNCH("deblock_pass_kernel<horizontal edges>");
   return KVZ_HIP_OK;
 }

@@ -17,22 +17,16 @@ extern "C" int kvz_hip_deblock_frames(const kvz_hip_filter_picture *pictures, in
   deblock_batch b;
   __builtin_memset(&b, 0, sizeof b);
   uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
-  int used = 0;
+  pic_tiles tiles[KVZ_HIP_MAX_CHAIN_PICTURES];
+  int used = 0, at = 0;
   size_t threads = 0;
   // every record is checked before anything is launched: a refused call writes nothing
+  if (const char *why = filter_records_why(pictures, n_pictures, deblock_record_why, deblock_output_shared, bounds, used, tiles, &at))
+    return refuse_picture(__func__, at, why);
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_filter_picture &p = pictures[i];
-    if (p.deblock.chroma != p.chroma) return refuse_picture(__func__, i, "deblock.chroma differs from chroma");
-    if (p.width > 16384 || p.height > 16384 ||
-        !deblock_args_ok(__func__, p.rec_y, p.stride_y, p.rec_u, p.rec_v, p.stride_c, p.width, p.height, p.cus, &p.deblock))
-      return refuse_picture(__func__, i, "planes and the SCU map must be 4-byte aligned, width / height multiples of 8 in 8..16384, strides >= the width");
-    kvz_hip_tile_grid g;
-    if (!tile_grid_make(p.grid, p.width, p.height, &g)) return refuse_picture(__func__, i, "invalid tile grid");
     deblock_pic &r = b.p[i];
-    if (!tile_pool_add(p.grid, g, bounds, used, &r.tiles))
-      return refuse_picture(__func__, i, "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record");
-    for (int j = 0; j < i; ++j)
-      if (p.rec_y == pictures[j].rec_y) return refuse_picture(__func__, i, "an output shared with another picture");
+    r.tiles = tiles[i];
     r.cus = (const u32 *)p.cus;
     r.rec_y = p.rec_y; r.rec_u = p.chroma ? p.rec_u : nullptr; r.rec_v = p.chroma ? p.rec_v : nullptr;
     r.stride_y = p.stride_y; r.stride_c = p.stride_c;

@@ -11,8 +11,9 @@ extern "C" int kvz_hip_deblock_frame_tiles(kvz_hip_pixel *rec_y, uint32_t stride
                                            const kvz_hip_deblock_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!deblock_args_ok(__func__, rec_y, stride_y, rec_u, rec_v, stride_c, width, height, cus, params)) return KVZ_HIP_ERR_INVALID;
+  kvz_hip_filter_picture p;
+  if (const int rc = deblock_refusal(__func__, deblock_pack(&p, rec_y, stride_y, rec_u, rec_v, stride_c, width, height, cus, grid, params) ? &p : nullptr)) return rc;
   kvz_hip_tile_grid g;
   if (!tile_grid_make(grid, width, height, &g)) return kvzhip::invalid_arg(__func__);
-  return deblock_launch(rec_y, stride_y, rec_u, rec_v, stride_c, width, height, cus, params, s, g);
+  return deblock_launch(p, s, g);
 }

@@ -123,13 +123,6 @@ __global__ __launch_bounds__(256) void inter_recon_frame_kernel(recon_args a, co
   }
 }
 
-bool refs_ok(const kvz_hip_ref_picture *refs, int n_refs, int chroma, int width, int height)
-{
-  for (int i = 0; i < n_refs; ++i)
-    if (!ref_ok(refs[i], chroma, width, height)) return false;
-  return true;
-}
-
 void fill_args(recon_args &a, const kvz_hip_ref_picture *refs, int n_refs, kvz_hip_pixel *pred_y, uint32_t stride_y,
                kvz_hip_pixel *pred_u, kvz_hip_pixel *pred_v, uint32_t stride_c, int width, int height, int chroma)
 {
@@ -153,7 +146,7 @@ int kvz_hip_inter_recon_batch(const kvz_hip_ref_picture *refs, int n_refs, const
   if (!refs || n_refs < 1 || n_refs > KVZ_HIP_MAX_REF_PICTURES || !pred_y || (chroma && (!pred_u || !pred_v)) || (count && !pus))
     return kvzhip::invalid_arg(__func__);
   const int width = refs[0].width, height = refs[0].height;
-  if (width < 8 || height < 8 || ((width | height) & 7) || stride_y < (uint32_t)width || (chroma && stride_c < (uint32_t)(width >> 1)) ||
+  if (!picture_ok_any_size(width, height) || stride_y < (uint32_t)width || (chroma && stride_c < (uint32_t)(width >> 1)) ||
       !refs_ok(refs, n_refs, chroma, width, height) || count > 0x7fffffffu)
     return kvzhip::invalid_arg(__func__);
   if (count == 0) return KVZ_HIP_OK;
@@ -169,12 +162,11 @@ int kvz_hip_inter_recon_frame(kvz_hip_pixel *pred_y, uint32_t stride_y, kvz_hip_
                               const kvz_hip_inter_recon_params *params, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!pred_y || !cus || !refs || !params || ((uintptr_t)cus & 3) || width < 8 || height < 8 || ((width | height) & 7) || stride_y < (uint32_t)width)
+  kvz_hip_recon_picture p;
+  if (!recon_pack(&p, pred_y, stride_y, pred_u, pred_v, stride_c, width, height, cus, refs, params) || !recon_arrays_ok(p) || !recon_luma_ok(p) ||
+      !recon_n_refs_ok(p) || !recon_chroma_ok(p) || !refs_ok(refs, params->n_refs, params->chroma, width, height))
     return kvzhip::invalid_arg(__func__);
   const int chroma = params->chroma, n_refs = params->n_refs;
-  if (n_refs < 1 || n_refs > KVZ_HIP_MAX_REF_PICTURES || (chroma && (!pred_u || !pred_v || stride_c < (uint32_t)(width >> 1))) ||
-      !refs_ok(refs, n_refs, chroma, width, height))
-    return kvzhip::invalid_arg(__func__);
   recon_args a;
   fill_args(a, refs, n_refs, pred_y, stride_y, pred_u, pred_v, stride_c, width, height, chroma);
   const int tiles_x = (width + 15) >> 4, n_tiles = tiles_x * ((height + 15) >> 4);

@@ -11,11 +11,12 @@
 //   width, height          luma size of the picture (= of every reference picture it names)
 //   chroma                 0 = 4:0:0
 // recon_args (inter_recon.hip) is such a view with the table inside it; recon_view (inter_recon_multi.hip) points at the pool.
-// Host code: ref_ok, the rule for one reference picture of a table.
+// The host side -- ref_ok, the rule for one reference picture of a table, and the checks of a record -- is in chain_host.h.
 #pragma once
 
 #include "kvz_hip_internal.h"
 #include "frac_core.h"
+#include "chain_host.h"
 
 using namespace kvzhip;
 
@@ -323,14 +324,6 @@ __device__ __forceinline__ void predict_tile(int lane, u8 *lds, const A &a, cons
     predict_rect(lane, lds, a, m, rx, ry, rxe - rx, rye - ry);
     todo &= ~__ballot(lane < 16 && px >= rx && px < rxe && py >= ry && py < rye);
   }
-}
-
-// a table entry as the entries take it for a picture of width x height: chroma = the picture is 4:2:0
-inline bool ref_ok(const kvz_hip_ref_picture &r, int chroma, int width, int height)
-{
-  if (!r.y || r.width != width || r.height != height || r.stride_y < (uint32_t)width) return false;
-  if (chroma && (!r.u || !r.v || r.stride_c < (uint32_t)(width >> 1))) return false;
-  return true;
 }
 
 }  // namespace

@@ -75,44 +75,23 @@ int kvz_hip_inter_recon_frames(const kvz_hip_recon_picture *pictures, int n_pict
   k.n_pictures = n_pictures;
   k.n_pool = n_pool;
   bool named[KVZ_HIP_RECON_POOL_PICTURES] = { false };
+  int first_wg[KVZ_HIP_MAX_CHAIN_PICTURES], at = 0;
   unsigned long long groups = 0;
   // every record is checked before anything is launched: a refused call writes nothing
+  if (const char *why = recon_records_why(pictures, n_pictures, pool, n_pool, named, first_wg, groups, &at)) return refuse_picture(__func__, at, why);
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_recon_picture &p = pictures[i];
-    const int width = p.width, height = p.height, chroma = p.params.chroma, n_refs = p.params.n_refs;
-    if (!p.pred_y || !p.cus || ((uintptr_t)p.cus & 3)) return refuse_picture(__func__, i, "pred_y or cus is null, or cus misaligned");
-    if (width < 8 || height < 8 || ((width | height) & 7) || p.stride_y < (uint32_t)width)
-      return refuse_picture(__func__, i, "width / height must be multiples of 8, stride_y >= the width");
-    if (n_refs < 1 || n_refs > KVZ_HIP_MAX_REF_PICTURES) return refuse_picture(__func__, i, "n_refs outside 1..16");
-    if (chroma && (!p.pred_u || !p.pred_v || p.stride_c < (uint32_t)(width >> 1)))
-      return refuse_picture(__func__, i, "a chroma plane is null, or stride_c below half the width");
-    for (int r = 0; r < n_refs; ++r) {
-      if (p.refs[r] >= n_pool) return refuse_picture(__func__, i, "a reference index outside the pool");
-      if (!ref_ok(pool[p.refs[r]], chroma, width, height))
-        return refuse_picture(__func__, i, "a named pool picture of another size, with a missing plane or a short stride");
-      named[p.refs[r]] = true;
-    }
-    for (int j = 0; j < i; ++j)
-      if (p.pred_y == pictures[j].pred_y) return refuse_picture(__func__, i, "pred_y shared with another picture");
+    const int chroma = p.params.chroma, n_refs = p.params.n_refs;
     multi_pic &a = k.p[i];
     a.y = p.pred_y; a.u = chroma ? p.pred_u : nullptr; a.v = chroma ? p.pred_v : nullptr;
     a.cus = (const u32 *)p.cus;
     a.stride_y = p.stride_y; a.stride_c = p.stride_c;
-    a.width = width; a.height = height;
+    a.width = p.width; a.height = p.height;
     a.chroma = chroma ? 1 : 0;
-    a.first_wg = (int)groups;
+    a.first_wg = first_wg[i];
     for (int l = 0; l < 2; ++l)
       for (int r = 0; r < 16; ++r) a.pool_of[l][r] = p.params.ref_LX[l][r] < n_refs ? p.refs[p.params.ref_LX[l][r]] : 255;
-    groups += ((unsigned long long)((width + 15) >> 4) * (unsigned long long)((height + 15) >> 4) + 3) / 4;
-    if (groups > 0x7fffffffull) return refuse_picture(__func__, i, "the pictures of the call exceed the grid");
   }
-  // no destination may be a plane of a pool picture that some record names
-  for (int i = 0; i < n_pictures; ++i)
-    for (int r = 0; r < n_pool; ++r) {
-      if (!named[r]) continue;
-      const kvz_hip_ref_picture &q = pool[r];
-      if (k.p[i].y == q.y || (k.p[i].u && (k.p[i].u == q.u || k.p[i].v == q.v))) return refuse_picture(__func__, i, "a destination plane is a named pool plane");
-    }
   for (int r = 0; r < n_pool; ++r)
     if (named[r]) k.pool[r] = pool[r];
   // the launch depends on the sizes alone

@@ -24,24 +24,12 @@ int kvz_hip_sao_stats_frame(const kvz_hip_ref_picture *src, const kvz_hip_pixel 
                             kvz_hip_sao_lcu_cand *cands, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  if (!src || !stats || ((uintptr_t)stats & 3) || ((uintptr_t)cands & 3)) return kvzhip::invalid_arg(__func__);
-  const int width = src->width, height = src->height;
-  if (!picture_ok(width, height) || !plane_ok(src->y, src->stride_y, width) || !plane_ok(rec_y, stride_y, width)) {
-    set_error_msg("kvz_hip_sao_stats_frame: planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8");
-    return KVZ_HIP_ERR_INVALID;
-  }
-  if (chroma && (!plane_ok(src->u, src->stride_c, width >> 1) || !plane_ok(src->v, src->stride_c, width >> 1) ||
-                 !plane_ok(rec_u, stride_c, width >> 1) || !plane_ok(rec_v, stride_c, width >> 1)))
-    return kvzhip::invalid_arg(__func__);
+  kvz_hip_filter_picture p;
+  if (!sao_stats_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, chroma, stats, cands) || !sao_stats_out_ok(p)) return kvzhip::invalid_arg(__func__);
+  if (!sao_stats_luma_ok(p)) return refuse_entry(__func__, PLANES_AND_STRIDES);
+  if (!sao_stats_chroma_ok(p)) return kvzhip::invalid_arg(__func__);
   stats_args a;
-  a.src[0] = src->y; a.src[1] = chroma ? src->u : nullptr; a.src[2] = chroma ? src->v : nullptr;
-  a.rec[0] = rec_y; a.rec[1] = chroma ? rec_u : nullptr; a.rec[2] = chroma ? rec_v : nullptr;
-  a.src_stride[0] = src->stride_y; a.src_stride[1] = src->stride_c;
-  a.rec_stride[0] = stride_y; a.rec_stride[1] = stride_c;
-  a.width = width; a.height = height;
-  a.lcus_x = (width + 63) >> 6;
-  a.n_lcu = a.lcus_x * ((height + 63) >> 6);
-  a.stats = (int *)stats; a.cands = (int *)cands;
+  sao_stats_fill(a, p);
   hipLaunchKernelGGL(sao_stats_frame_kernel<>, dim3((unsigned)(a.n_lcu * (chroma ? 3 : 1))), dim3(256), 0, ctx_stream(s), a);
   KVZ_CHECK_LAUNCH("sao_stats_frame_kernel");
   return KVZ_HIP_OK;
@@ -53,8 +41,9 @@ int kvz_hip_sao_frame(const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_h
                       kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
-  return sao_frame_launch(__func__, rec_y, stride_y, rec_u, rec_v, stride_c, dst_y, dst_stride_y, dst_u, dst_v, dst_stride_c, width, height, sao_luma,
-                          sao_chroma, chroma, s);
+  kvz_hip_filter_picture p;
+  sao_pack(&p, rec_y, stride_y, rec_u, rec_v, stride_c, dst_y, dst_stride_y, dst_u, dst_v, dst_stride_c, width, height, sao_luma, sao_chroma, chroma, nullptr);
+  return sao_frame_launch(__func__, p, s);
 }
 
 }  // extern "C"

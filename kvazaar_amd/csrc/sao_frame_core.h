@@ -3,8 +3,6 @@
 // instantiates one kernel.  The algorithm is described in sao_frame.hip.
 #pragma once
 
-#include <string>
-
 #include "kvz_hip_internal.h"
 #include "tile_grid.h"
 
@@ -26,6 +24,20 @@ struct frame_args {
   int width, height, lcus_x, tiles_y, tiles_c;
   const kvz_hip_sao_info *sao[2];         // [0] luma, [1] chroma records
 };
+// host: the argument of one picture, for the two single entries and a record of kvz_hip_sao_frames
+inline void sao_frame_fill(frame_args &a, const kvz_hip_filter_picture &p)
+{
+  const bool chroma = p.chroma != 0;
+  a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
+  a.dst[0] = p.dst_y; a.dst[1] = chroma ? p.dst_u : nullptr; a.dst[2] = chroma ? p.dst_v : nullptr;
+  a.rec_stride[0] = p.stride_y; a.rec_stride[1] = p.stride_c;
+  a.dst_stride[0] = p.dst_stride_y; a.dst_stride[1] = p.dst_stride_c;
+  a.width = p.width; a.height = p.height;
+  a.lcus_x = (p.width + 63) >> 6;
+  a.tiles_y = a.lcus_x * ((p.height + 15) >> 4);
+  a.tiles_c = chroma ? a.lcus_x * ((p.height + 63) >> 6) : 0;
+  a.sao[0] = p.sao_luma; a.sao[1] = chroma ? p.sao_chroma : nullptr;
+}
 
 // the tile of a tiled picture in pixels of the plane: what stands for the plane where an edge-offset pixel asks for its neighbours
 struct px_rect { int x0, y0, x1, y1; };
@@ -171,43 +183,15 @@ __global__ __launch_bounds__(256) void sao_frame_kernel(frame_args a, TILES... t
   *(u32 *)(dst + (size_t)gy * ds + gx) = out;
 }
 
-bool picture_ok(int width, int height)
-{
-  return width >= 8 && height >= 8 && !((width | height) & 7) && width <= 16384 && height <= 16384;
-}
-
-bool plane_ok(const void *p, uint32_t stride, int w)
-{
-  return p && !((uintptr_t)p & 3) && !(stride & 3) && stride >= (uint32_t)w;
-}
-
-
-// both entries; tiles: nothing or the grid
+// both single entries, behind their sao_pack; tiles: nothing or the grid
 template <typename... TILES>
-int sao_frame_launch(const char *entry, const kvz_hip_pixel *rec_y, uint32_t stride_y, const kvz_hip_pixel *rec_u, const kvz_hip_pixel *rec_v,
-                     uint32_t stride_c, kvz_hip_pixel *dst_y, uint32_t dst_stride_y, kvz_hip_pixel *dst_u, kvz_hip_pixel *dst_v, uint32_t dst_stride_c,
-                     int width, int height, const kvz_hip_sao_info *sao_luma, const kvz_hip_sao_info *sao_chroma, int chroma, kvz_hip_stream s,
-                     TILES... tiles)
+int sao_frame_launch(const char *entry, const kvz_hip_filter_picture &p, kvz_hip_stream s, TILES... tiles)
 {
-  if (!sao_luma || ((uintptr_t)sao_luma & 3) || dst_y == rec_y) return kvzhip::invalid_arg(entry);
-  if (!picture_ok(width, height) || !plane_ok(rec_y, stride_y, width) || !plane_ok(dst_y, dst_stride_y, width)) {
-    set_error_msg((std::string(entry) + ": planes and strides must be 4-byte aligned, strides >= the width, width / height multiples of 8").c_str());
-    return KVZ_HIP_ERR_INVALID;
-  }
-  if (chroma && (!sao_chroma || ((uintptr_t)sao_chroma & 3) || dst_u == rec_u || dst_v == rec_v ||
-                 !plane_ok(rec_u, stride_c, width >> 1) || !plane_ok(rec_v, stride_c, width >> 1) ||
-                 !plane_ok(dst_u, dst_stride_c, width >> 1) || !plane_ok(dst_v, dst_stride_c, width >> 1)))
-    return kvzhip::invalid_arg(entry);
+  if (!sao_luma_info_ok(p)) return kvzhip::invalid_arg(entry);
+  if (!sao_luma_planes_ok(p)) return refuse_entry(entry, PLANES_AND_STRIDES);
+  if (!sao_chroma_ok(p)) return kvzhip::invalid_arg(entry);
   frame_args a;
-  a.rec[0] = rec_y; a.rec[1] = chroma ? rec_u : nullptr; a.rec[2] = chroma ? rec_v : nullptr;
-  a.dst[0] = dst_y; a.dst[1] = chroma ? dst_u : nullptr; a.dst[2] = chroma ? dst_v : nullptr;
-  a.rec_stride[0] = stride_y; a.rec_stride[1] = stride_c;
-  a.dst_stride[0] = dst_stride_y; a.dst_stride[1] = dst_stride_c;
-  a.width = width; a.height = height;
-  a.lcus_x = (width + 63) >> 6;
-  a.tiles_y = a.lcus_x * ((height + 15) >> 4);
-  a.tiles_c = chroma ? a.lcus_x * ((height + 63) >> 6) : 0;
-  a.sao[0] = sao_luma; a.sao[1] = chroma ? sao_chroma : nullptr;
+  sao_frame_fill(a, p);
   hipLaunchKernelGGL(sao_frame_kernel<TILES...>, dim3((unsigned)(a.tiles_y + 2 * a.tiles_c)), dim3(256), 0, ctx_stream(s), a, tiles...);
   KVZ_CHECK_LAUNCH("sao_frame_kernel");
   return KVZ_HIP_OK;

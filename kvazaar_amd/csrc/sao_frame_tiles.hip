@@ -10,8 +10,9 @@ extern "C" int kvz_hip_sao_frame_tiles(const kvz_hip_pixel *rec_y, uint32_t stri
                                        const kvz_hip_sao_info *sao_chroma, int chroma, const kvz_hip_tile_grid *grid, kvz_hip_stream s)
 {
   KVZ_CHECK_CTX();
+  kvz_hip_filter_picture p;
   kvz_hip_tile_grid g;
+  sao_pack(&p, rec_y, stride_y, rec_u, rec_v, stride_c, dst_y, dst_stride_y, dst_u, dst_v, dst_stride_c, width, height, sao_luma, sao_chroma, chroma, grid);
   if (!picture_ok(width, height) || !tile_grid_make(grid, width, height, &g)) return kvzhip::invalid_arg(__func__);
-  return sao_frame_launch(__func__, rec_y, stride_y, rec_u, rec_v, stride_c, dst_y, dst_stride_y, dst_u, dst_v, dst_stride_c, width, height, sao_luma,
-                          sao_chroma, chroma, s, g);
+  return sao_frame_launch(__func__, p, s, g);
 }

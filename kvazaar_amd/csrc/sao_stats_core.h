@@ -15,6 +15,19 @@ struct stats_args {
   int width, height, lcus_x, n_lcu;
   int *stats, *cands;                     // 104 / 30 int32 per record; cands may be NULL
 };
+// host: the argument of one picture, for kvz_hip_sao_stats_frame and a record of kvz_hip_sao_stats_frames
+inline void sao_stats_fill(stats_args &a, const kvz_hip_filter_picture &p)
+{
+  const bool chroma = p.chroma != 0;
+  a.src[0] = p.src.y; a.src[1] = chroma ? p.src.u : nullptr; a.src[2] = chroma ? p.src.v : nullptr;
+  a.rec[0] = p.rec_y; a.rec[1] = chroma ? p.rec_u : nullptr; a.rec[2] = chroma ? p.rec_v : nullptr;
+  a.src_stride[0] = p.src.stride_y; a.src_stride[1] = p.src.stride_c;
+  a.rec_stride[0] = p.stride_y; a.rec_stride[1] = p.stride_c;
+  a.width = p.width; a.height = p.height;
+  a.lcus_x = (p.width + 63) >> 6;
+  a.n_lcu = a.lcus_x * ((p.height + 63) >> 6);
+  a.stats = (int *)p.stats; a.cands = (int *)p.cands;
+}
 
 // offset of one category or band: the mean error rounded to nearest with C's truncating division, clipped to SAO_ABS_OFFSET_MAX
 // at bit depth 8 (sao.c:205-206, :381-382)

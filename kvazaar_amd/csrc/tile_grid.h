@@ -1,7 +1,7 @@
 // tile_grid.h -- kvz_hip_tile_grid on the device, for the four *_tiles entries of the picture chain (intra_recon_tiles.hip,
 // cu_qp_tiles.hip, deblock_tiles.hip, sao_frame_tiles.hip); its host side (tile_grid_make, tile_grid_waves) is in chain_host.h.  At the
 // end: the grids of the pictures of a multi-picture call, which share one pool of boundaries (cu_qp_multi.hip, deblock_multi.hip,
-// sao_frame_multi.hip; filled on the host by tile_pool_add and tile_pool_pack, chain_host.h).
+// sao_frame_multi.hip; filled on the host by tile_pool_add and tile_pool_pack, chain_host.h, inside the record checks).
 //
 // The grid travels to every kernel by value (392 bytes of kernel arguments).  The lookups below index it with constants only --
 // the loops are fully unrolled and select -- because a dynamically indexed kernel argument array is copied to scratch; with a
