@@ -13,11 +13,13 @@
 // are called concurrently from all threadqueue workers, encoderstate.c:781) but
 // launch-latency bound -- throughput comes from the batched entries.
 #include "kvz_hip_internal.h"
+#include "dropin_stage.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 using namespace kvzhip;
 
@@ -99,59 +101,107 @@ void die(const char *what, int rc)
 #define MUST(call) do { int rc__ = (call); if (rc__ != KVZ_HIP_OK) die(#call, rc__); } while (0)
 #define HMUST(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { set_error(#call, e__); die(#call, KVZ_HIP_ERR_RUNTIME); } } while (0)
 
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline int clampi_host(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 std::atomic<unsigned long long> g_dropin_calls{0};
-
-// bump allocator over the staging buffer; one per strategy call that reaches the GPU
-struct stage {
-  call_ctx &c;
-  size_t off = 0;
-  explicit stage(call_ctx &cc) : c(cc) { g_dropin_calls.fetch_add(1, std::memory_order_relaxed); }
-  size_t take(size_t bytes)
-  {
-    size_t o = off;
-    off = up16(off + bytes);
-    if (off > c.cap) die("staging buffer overflow", KVZ_HIP_ERR_INVALID);
-    return o;
-  }
-  void h2d(size_t o, size_t bytes) { if (!c.zero_copy) HMUST(hipMemcpyAsync(c.d + o, c.h + o, bytes, hipMemcpyHostToDevice, c.st)); }
-  void d2h(size_t o, size_t bytes) { if (!c.zero_copy) HMUST(hipMemcpyAsync(c.h + o, c.d + o, bytes, hipMemcpyDeviceToHost, c.st)); }
-  void sync() { HMUST(hipStreamSynchronize(c.st)); }
-};
 
 void pack_rows(u8 *dst, const u8 *src, int w, int h, size_t stride)
 {
   for (int y = 0; y < h; ++y) std::memcpy(dst + (size_t)y * w, src + (size_t)y * stride, (size_t)w);
 }
 
+template <typename T> using slot = stage_slot<T>;
+
+// One strategy call that reaches the GPU: the thread's staging context and the layout of this call's slots in it, by the rules
+// of dropin_stage.h.  A strategy function takes its slots, uploads, launches on c.st with the typed device pointers, downloads
+// and copies out.
+struct dropin_call {
+  call_ctx &c;
+  stage_layout lay;
+  dropin_call() : c(tls()), lay(c.cap) { g_dropin_calls.fetch_add(1, std::memory_order_relaxed); }
+
+  template <typename T> T *host(const slot<T> &s) const { return s.host(c.h); }
+  template <typename T> T *dev(const slot<T> &s) const { return s.dev(c.d); }
+
+  // input slots: n elements to fill, a contiguous host array, the w x h rows of a strided one, one record by value
+  template <typename T> slot<T> in(size_t n) { slot<T> s; check(lay.in(n, &s)); return s; }
+  template <typename T> slot<T> in(const T *src, size_t n) { slot<T> s = in<T>(n); std::memcpy(host(s), src, s.bytes()); return s; }
+  slot<u8> in_rows(const u8 *src, int w, int h, size_t stride) { slot<u8> s = in<u8>((size_t)w * h); pack_rows(host(s), src, w, h, stride); return s; }
+  template <typename T> slot<T> in_record(const T &v) { return in(&v, 1); }
+  template <typename T> slot<T> out(size_t n) { slot<T> s; check(lay.out(n, &s)); return s; }
+  void next_phase() { lay.next_phase(); }
+
+  // the copies happen only where the kernels do not use the pinned buffer itself; download() returns with the results on the host
+  void upload()
+  {
+    const stage_range r = lay.upload();
+    const size_t o = r.off, bytes = r.bytes;
+    if (!c.zero_copy) HMUST(hipMemcpyAsync(c.d + o, c.h + o, bytes, hipMemcpyHostToDevice, c.st));
+  }
+  template <typename A, typename B> void download(const slot<A> &first, const slot<B> &last)
+  {
+    const stage_range r = stage_layout::download(first, last);
+    const size_t o = r.off, bytes = r.bytes;
+    if (!c.zero_copy) HMUST(hipMemcpyAsync(c.h + o, c.d + o, bytes, hipMemcpyDeviceToHost, c.st));
+    HMUST(hipStreamSynchronize(c.st));
+  }
+  template <typename T> void download(const slot<T> &only) { download(only, only); }
+
+ private:
+  static void check(stage_status st)
+  {
+    if (st == STAGE_OVERFLOW) die("staging buffer overflow", KVZ_HIP_ERR_INVALID);
+    if (st != STAGE_OK) die("staging input after an output", KVZ_HIP_ERR_INVALID);
+  }
+};
+
 // ---------------- picture group ----------------
-unsigned hip_reg_sad(const kvz_hip_pixel *d1, const kvz_hip_pixel *d2, int w, int h, unsigned s1, unsigned s2)
+// reg_sad, satd_any_size, pixels_calc_ssd: two strided w x h blocks staged packed, one descriptor that puts both at the origin,
+// one cost back
+template <typename F>
+unsigned block_pair_cost(const kvz_hip_pixel *b1, size_t s1, const kvz_hip_pixel *b2, size_t s2, int w, int h, F entry)
 {
   if (w <= 0 || h <= 0) return 0;
-  call_ctx &c = tls(); stage s(c);
-  size_t oa = s.take((size_t)w * h), ob = s.take((size_t)w * h), od = s.take(sizeof(kvz_hip_block_pair)), in_end = s.off, oc = s.take(4);
-  pack_rows(c.h + oa, d1, w, h, s1); pack_rows(c.h + ob, d2, w, h, s2);
-  kvz_hip_block_pair bp = { 0, 0, 0, 0, w, h };
-  std::memcpy(c.h + od, &bp, sizeof(bp));
-  s.h2d(0, in_end);
-  MUST(kvz_hip_reg_sad_batch(c.d + oa, (u32)w, c.d + ob, (u32)w, (const kvz_hip_block_pair *)(c.d + od), 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 4); s.sync();
-  return *(u32 *)(c.h + oc);
+  dropin_call k;
+  auto a = k.in_rows(b1, w, h, s1), b = k.in_rows(b2, w, h, s2);
+  auto bp = k.in_record(kvz_hip_block_pair{ 0, 0, 0, 0, w, h });
+  auto cost = k.out<u32>(1);
+  k.upload();
+  entry(k.dev(a), k.dev(b), k.dev(bp), k.dev(cost), k.c.st);
+  k.download(cost);
+  return *k.host(cost);
+}
+
+unsigned hip_reg_sad(const kvz_hip_pixel *d1, const kvz_hip_pixel *d2, int w, int h, unsigned s1, unsigned s2)
+{
+  return block_pair_cost(d1, s1, d2, s2, w, h, [=](const u8 *a, const u8 *b, const kvz_hip_block_pair *bp, u32 *cost, hipStream_t st) {
+    MUST(kvz_hip_reg_sad_batch(a, (u32)w, b, (u32)w, bp, 1, cost, st)); });
+}
+
+unsigned hip_satd_any_size(int w, int h, const kvz_hip_pixel *b1, int s1, const kvz_hip_pixel *b2, int s2)
+{
+  // both planes are the packed blocks themselves: clamp extents == block => never clamps
+  return block_pair_cost(b1, (size_t)s1, b2, (size_t)s2, w, h, [=](const u8 *a, const u8 *b, const kvz_hip_block_pair *bp, u32 *cost, hipStream_t st) {
+    MUST(kvz_hip_image_calc_satd_batch(a, (u32)w, b, (u32)w, w, h, bp, 1, cost, st)); });
+}
+
+unsigned hip_pixels_calc_ssd(const kvz_hip_pixel *ref, const kvz_hip_pixel *rec, const int ref_stride, const int rec_stride, const int width)
+{
+  const int w = width;
+  return block_pair_cost(ref, (size_t)ref_stride, rec, (size_t)rec_stride, w, w, [=](const u8 *a, const u8 *b, const kvz_hip_block_pair *bp, u32 *cost, hipStream_t st) {
+    MUST(kvz_hip_pixels_calc_ssd_batch(a, (u32)w, b, (u32)w, bp, 1, cost, st)); });
 }
 
 template <int N, bool SATD>
 unsigned hip_cost_nxn(const kvz_hip_pixel *b1, const kvz_hip_pixel *b2)
 {
-  call_ctx &c = tls(); stage s(c);
-  size_t oa = s.take(N * N), ob = s.take(N * N), in_end = s.off, oc = s.take(4);
-  std::memcpy(c.h + oa, b1, N * N); std::memcpy(c.h + ob, b2, N * N);
-  s.h2d(0, in_end);
-  if (SATD) MUST(kvz_hip_satd_nxn_batch(N, c.d + oa, c.d + ob, 1, (u32 *)(c.d + oc), c.st));
-  else MUST(kvz_hip_sad_nxn_batch(N, c.d + oa, c.d + ob, 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 4); s.sync();
-  return *(u32 *)(c.h + oc);
+  dropin_call k;
+  auto a = k.in(b1, (size_t)N * N), b = k.in(b2, (size_t)N * N);
+  auto cost = k.out<u32>(1);
+  k.upload();
+  MUST((SATD ? kvz_hip_satd_nxn_batch : kvz_hip_sad_nxn_batch)(N, k.dev(a), k.dev(b), 1, k.dev(cost), k.c.st));
+  k.download(cost);
+  return *k.host(cost);
 }
 
 // cost_pixel_nxn_multi_func: preds is kvz_pixel (*)[32*32]; preds[1] is 1024 bytes after preds[0]
@@ -159,31 +209,15 @@ template <int N, bool SATD>
 void hip_cost_nxn_dual(const kvz_hip_pixel (*preds)[32 * 32], const kvz_hip_pixel *orig, unsigned num_modes, unsigned *costs_out)
 {
   (void)num_modes;
-  call_ctx &c = tls(); stage s(c);
+  dropin_call k;
   // N == 64 overlaps the two predictions in the reference's buffer (64*64 > 1024); copy what the generic code reads
   const size_t pbytes = 1024 + (size_t)N * N;
-  size_t op = s.take(pbytes), oo = s.take(N * N), in_end = s.off, oc = s.take(8);
-  std::memcpy(c.h + op, preds, pbytes); std::memcpy(c.h + oo, orig, N * N);
-  s.h2d(0, in_end);
-  if (SATD) MUST(kvz_hip_satd_nxn_dual_batch(N, c.d + op, 1024, up16(pbytes), c.d + oo, 1, (u32 *)(c.d + oc), c.st));
-  else MUST(kvz_hip_sad_nxn_dual_batch(N, c.d + op, 1024, up16(pbytes), c.d + oo, 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 8); s.sync();
-  costs_out[0] = ((u32 *)(c.h + oc))[0]; costs_out[1] = ((u32 *)(c.h + oc))[1];
-}
-
-unsigned hip_satd_any_size(int w, int h, const kvz_hip_pixel *b1, int s1, const kvz_hip_pixel *b2, int s2)
-{
-  if (w <= 0 || h <= 0) return 0;
-  call_ctx &c = tls(); stage s(c);
-  size_t oa = s.take((size_t)w * h), ob = s.take((size_t)w * h), od = s.take(sizeof(kvz_hip_block_pair)), in_end = s.off, oc = s.take(4);
-  pack_rows(c.h + oa, b1, w, h, (size_t)s1); pack_rows(c.h + ob, b2, w, h, (size_t)s2);
-  kvz_hip_block_pair bp = { 0, 0, 0, 0, w, h };
-  std::memcpy(c.h + od, &bp, sizeof(bp));
-  s.h2d(0, in_end);
-  // both planes are the packed blocks themselves: clamp extents == block => never clamps
-  MUST(kvz_hip_image_calc_satd_batch(c.d + oa, (u32)w, c.d + ob, (u32)w, w, h, (const kvz_hip_block_pair *)(c.d + od), 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 4); s.sync();
-  return *(u32 *)(c.h + oc);
+  auto p = k.in(&preds[0][0], pbytes), o = k.in(orig, (size_t)N * N);
+  auto costs = k.out<u32>(2);
+  k.upload();
+  MUST((SATD ? kvz_hip_satd_nxn_dual_batch : kvz_hip_sad_nxn_dual_batch)(N, k.dev(p), 1024, stage_align_up(pbytes), k.dev(o), 1, k.dev(costs), k.c.st));
+  k.download(costs);
+  costs_out[0] = k.host(costs)[0]; costs_out[1] = k.host(costs)[1];
 }
 
 void hip_satd_any_size_quad(int w, int h, const kvz_hip_pixel **preds, const int stride, const kvz_hip_pixel *orig,
@@ -192,32 +226,17 @@ void hip_satd_any_size_quad(int w, int h, const kvz_hip_pixel **preds, const int
   (void)num_modes; (void)valid;
   costs_out[0] = costs_out[1] = costs_out[2] = costs_out[3] = 0;
   if (w <= 0 || h <= 0) return;
-  call_ctx &c = tls(); stage s(c);
-  const size_t bsz = up16((size_t)w * h);
-  size_t op = s.take(bsz * 4), oo = s.take((size_t)w * h), od = s.take(sizeof(kvz_hip_block_pair)), in_end = s.off, oc = s.take(16);
-  for (int k = 0; k < 4; ++k) pack_rows(c.h + op + k * bsz, preds[k], w, h, (size_t)stride);
-  pack_rows(c.h + oo, orig, w, h, (size_t)orig_stride);
-  kvz_hip_block_pair bp = { 0, 0, 0, 0, w, h };
-  std::memcpy(c.h + od, &bp, sizeof(bp));
-  s.h2d(0, in_end);
-  MUST(kvz_hip_satd_any_size_quad_batch(c.d + op, (u32)w, bsz, c.d + oo, (u32)w, (const kvz_hip_block_pair *)(c.d + od), 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 16); s.sync();
-  for (int k = 0; k < 4; ++k) costs_out[k] = ((u32 *)(c.h + oc))[k];
-}
-
-unsigned hip_pixels_calc_ssd(const kvz_hip_pixel *ref, const kvz_hip_pixel *rec, const int ref_stride, const int rec_stride, const int width)
-{
-  if (width <= 0) return 0;
-  call_ctx &c = tls(); stage s(c);
-  const int w = width;
-  size_t oa = s.take((size_t)w * w), ob = s.take((size_t)w * w), od = s.take(sizeof(kvz_hip_block_pair)), in_end = s.off, oc = s.take(4);
-  pack_rows(c.h + oa, ref, w, w, (size_t)ref_stride); pack_rows(c.h + ob, rec, w, w, (size_t)rec_stride);
-  kvz_hip_block_pair bp = { 0, 0, 0, 0, w, w };
-  std::memcpy(c.h + od, &bp, sizeof(bp));
-  s.h2d(0, in_end);
-  MUST(kvz_hip_pixels_calc_ssd_batch(c.d + oa, (u32)w, c.d + ob, (u32)w, (const kvz_hip_block_pair *)(c.d + od), 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 4); s.sync();
-  return *(u32 *)(c.h + oc);
+  dropin_call k;
+  const size_t bsz = stage_align_up((size_t)w * h);
+  auto p = k.in<u8>(bsz * 4);
+  for (int i = 0; i < 4; ++i) pack_rows(k.host(p) + i * bsz, preds[i], w, h, (size_t)stride);
+  auto o = k.in_rows(orig, w, h, (size_t)orig_stride);
+  auto bp = k.in_record(kvz_hip_block_pair{ 0, 0, 0, 0, w, h });
+  auto costs = k.out<u32>(4);
+  k.upload();
+  MUST(kvz_hip_satd_any_size_quad_batch(k.dev(p), (u32)w, bsz, k.dev(o), (u32)w, k.dev(bp), 1, k.dev(costs), k.c.st));
+  k.download(costs);
+  for (int i = 0; i < 4; ++i) costs_out[i] = k.host(costs)[i];
 }
 
 // ---------------- dct group ----------------
@@ -225,13 +244,13 @@ template <int KIND, int N>
 unsigned hip_transform(int8_t bitdepth, const int16_t *input, int16_t *output)
 {
   (void)bitdepth;           // registered for bitdepth 8 only
-  call_ctx &c = tls(); stage s(c);
-  size_t oi = s.take(N * N * 2), in_end = s.off, oo = s.take(N * N * 2);
-  std::memcpy(c.h + oi, input, N * N * 2);
-  s.h2d(0, in_end);
-  MUST(kvz_hip_transform_batch(KIND, N, (const int16_t *)(c.d + oi), (int16_t *)(c.d + oo), 1, c.st));
-  s.d2h(oo, N * N * 2); s.sync();
-  std::memcpy(output, c.h + oo, N * N * 2);
+  dropin_call k;
+  auto in = k.in(input, (size_t)N * N);
+  auto out = k.out<int16_t>((size_t)N * N);
+  k.upload();
+  MUST(kvz_hip_transform_batch(KIND, N, k.dev(in), k.dev(out), 1, k.c.st));
+  k.download(out);
+  std::memcpy(output, k.host(out), out.bytes());
   return 0;
 }
 
@@ -240,7 +259,7 @@ unsigned hip_transform(int8_t bitdepth, const int16_t *input, int16_t *output)
 int log2w(int w) { int l = 0; while ((1 << l) < w) ++l; return l; }
 
 // stages the per-coefficient tables when the scaling list is enabled; returns params with DEVICE table pointers
-kvz_hip_quant_params flatten_state(const void *state, int width, int type_q, int type_dq, int block_is_intra, stage &s, call_ctx &c)
+kvz_hip_quant_params flatten_state(const void *state, int width, int type_q, int type_dq, int block_is_intra, dropin_call &k)
 {
   kvz_hip_quant_params p;
   std::memset(&p, 0, sizeof(p));
@@ -254,62 +273,58 @@ kvz_hip_quant_params flatten_state(const void *state, int width, int type_q, int
       33,33,34,34,35,35,36,36,37,37,38,39,40,41,42,43,44,45,46,47,48,49,50,51 };
     auto sqp = [&](int type) { if (type == 0) return p.qp; int q = p.qp < 0 ? 0 : (p.qp > 57 ? 57 : p.qp); return (int)chroma_scale[q]; };
     static const int map[4] = { 0, 3, 1, 2 };        // "\0\3\1\2"[type], quant-generic.c:46
-    const size_t bytes = (size_t)width * width * 4;
+    const size_t n = (size_t)width * width;
     const int l2 = log2w(width);
     const int32_t *qt = g_acc.quant_coeff(state, l2, (block_is_intra ? 0 : 3) + map[type_q], sqp(type_q) % 6);
     const int32_t *dt = g_acc.dequant_coeff(state, l2, (block_is_intra ? 0 : 3) + map[type_dq], sqp(type_dq) % 6);
-    size_t oq = s.take(bytes), odq = s.take(bytes);
-    std::memcpy(c.h + oq, qt, bytes); std::memcpy(c.h + odq, dt, bytes);
-    p.quant_coeff = (const int32_t *)(c.d + oq);
-    p.dequant_coeff = (const int32_t *)(c.d + odq);
+    p.quant_coeff = k.dev(k.in(qt, n));
+    p.dequant_coeff = k.dev(k.in(dt, n));
   }
   return p;
+}
+
+// quant and dequant: the state's tables, then width x width coefficients in and as many out
+template <typename F>
+unsigned quant_call(const void *state, const kvz_hip_coeff *src, kvz_hip_coeff *dst, int width, int type, int block_type, F entry)
+{
+  dropin_call k;
+  const int intra = (block_type == 1);          // CU_INTRA == 1 (cu.h:39-41)
+  kvz_hip_quant_params p = flatten_state(state, width, type, type, intra, k);
+  auto in = k.in(src, (size_t)width * width);
+  auto out = k.out<kvz_hip_coeff>((size_t)width * width);
+  k.upload();
+  entry(&p, k.dev(in), k.dev(out), k.c.st);
+  k.download(out);
+  std::memcpy(dst, k.host(out), out.bytes());
+  return 0;
 }
 
 unsigned hip_quant(const void *state, kvz_hip_coeff *coef, kvz_hip_coeff *q_coef, int32_t width, int32_t height,
                    int8_t type, int8_t scan_idx, int8_t block_type)
 {
   (void)height;
-  call_ctx &c = tls(); stage s(c);
-  const size_t bytes = (size_t)width * width * 2;
-  const int intra = (block_type == 1);          // CU_INTRA == 1 (cu.h:39-41)
-  kvz_hip_quant_params p = flatten_state(state, width, type, type, intra, s, c);
-  size_t oi = s.take(bytes), in_end = s.off, oo = s.take(bytes);
-  std::memcpy(c.h + oi, coef, bytes);
-  s.h2d(0, in_end);
-  MUST(kvz_hip_quant_batch(&p, (const kvz_hip_coeff *)(c.d + oi), (kvz_hip_coeff *)(c.d + oo), width, type, scan_idx, 1, c.st));
-  s.d2h(oo, bytes); s.sync();
-  std::memcpy(q_coef, c.h + oo, bytes);
-  return 0;
+  return quant_call(state, coef, q_coef, width, type, block_type, [=](const kvz_hip_quant_params *p, const kvz_hip_coeff *in, kvz_hip_coeff *out, hipStream_t st) {
+    MUST(kvz_hip_quant_batch(p, in, out, width, type, scan_idx, 1, st)); });
 }
 
 unsigned hip_dequant(const void *state, kvz_hip_coeff *q_coef, kvz_hip_coeff *coef, int32_t width, int32_t height,
                      int8_t type, int8_t block_type)
 {
   (void)height;
-  call_ctx &c = tls(); stage s(c);
-  const size_t bytes = (size_t)width * width * 2;
-  const int intra = (block_type == 1);
-  kvz_hip_quant_params p = flatten_state(state, width, type, type, intra, s, c);
-  size_t oi = s.take(bytes), in_end = s.off, oo = s.take(bytes);
-  std::memcpy(c.h + oi, q_coef, bytes);
-  s.h2d(0, in_end);
-  MUST(kvz_hip_dequant_batch(&p, (const kvz_hip_coeff *)(c.d + oi), (kvz_hip_coeff *)(c.d + oo), width, type, 1, c.st));
-  s.d2h(oo, bytes); s.sync();
-  std::memcpy(coef, c.h + oo, bytes);
-  return 0;
+  return quant_call(state, q_coef, coef, width, type, block_type, [=](const kvz_hip_quant_params *p, const kvz_hip_coeff *in, kvz_hip_coeff *out, hipStream_t st) {
+    MUST(kvz_hip_dequant_batch(p, in, out, width, type, 1, st)); });
 }
 
 uint32_t hip_coeff_abs_sum(const kvz_hip_coeff *coeffs, size_t length)
 {
   if (length == 0) return 0;
-  call_ctx &c = tls(); stage s(c);
-  size_t oi = s.take(length * 2), in_end = s.off, oc = s.take(4);
-  std::memcpy(c.h + oi, coeffs, length * 2);
-  s.h2d(0, in_end);
-  MUST(kvz_hip_coeff_abs_sum_batch((const kvz_hip_coeff *)(c.d + oi), length, 1, (u32 *)(c.d + oc), c.st));
-  s.d2h(oc, 4); s.sync();
-  return *(u32 *)(c.h + oc);
+  dropin_call k;
+  auto in = k.in(coeffs, length);
+  auto sum = k.out<u32>(1);
+  k.upload();
+  MUST(kvz_hip_coeff_abs_sum_batch(k.dev(in), length, 1, k.dev(sum), k.c.st));
+  k.download(sum);
+  return *k.host(sum);
 }
 
 // quant_residual_func; color_t and coeff_scan_order_t are int-sized enums
@@ -318,57 +333,58 @@ unsigned hip_quantize_residual(void *state, const void *cur_cu, const int width,
                                const kvz_hip_pixel *ref_in, const kvz_hip_pixel *pred_in, kvz_hip_pixel *rec_out,
                                kvz_hip_coeff *coeff_out)
 {
-  call_ctx &c = tls(); stage s(c);
+  dropin_call k;
+  hipStream_t st = k.c.st;
   const int w = width;
+  const size_t n = (size_t)w * w;
   const int intra = g_acc.cu_is_intra(cur_cu);
   const int tq = color == 0 ? 0 : 2, tdq = color == 0 ? 0 : (color == 1 ? 2 : 3);
+  kvz_hip_quant_params p = flatten_state(state, w, tq, tdq, intra, k);
+  auto ref = k.in_rows(ref_in, w, w, (size_t)in_stride), pred = k.in_rows(pred_in, w, w, (size_t)in_stride);
   if (g_acc.rdoq_enable && g_acc.rdoq_enable(state) && (w > 4 || !(g_acc.rdoq_skip && g_acc.rdoq_skip(state)))) {
     // quant-generic.c:214-221: the quantiser is the host's kvz_rdoq (CABAC-context dependent control plane, called
     // by every strategy's quantize_residual); residual, transforms, dequantisation and reconstruction stay on the GPU
     // (registration guarantees the four rdoq accessors: kvz_strategy_register_quant_hip)
-    const size_t n = (size_t)w * w;
     const bool dst = (w == 4 && color == 0 && intra);               // strategies-dct.c:66-85
     // quant-generic.c:206-212: transform skip replaces the transform pair, RDOQ still quantises
     const int fwd_kind = use_trskip ? KVZ_HIP_TRSKIP : (dst ? KVZ_HIP_DST : KVZ_HIP_DCT);
     const int inv_kind = use_trskip ? KVZ_HIP_ITRSKIP : (dst ? KVZ_HIP_IDST : KVZ_HIP_IDCT);
-    kvz_hip_quant_params p = flatten_state(state, w, tq, tdq, intra, s, c);
-    size_t orf = s.take(n), opr = s.take(n), in_end = s.off;
-    size_t ors = s.take(n * 2), oco = s.take(n * 2);
-    pack_rows(c.h + orf, ref_in, w, w, (size_t)in_stride); pack_rows(c.h + opr, pred_in, w, w, (size_t)in_stride);
-    s.h2d(0, in_end);
-    MUST(kvz_hip_residual_batch(c.d + orf, c.d + opr, (kvz_hip_coeff *)(c.d + ors), n, c.st));
-    MUST(kvz_hip_transform_batch(fwd_kind, w, (const kvz_hip_coeff *)(c.d + ors), (kvz_hip_coeff *)(c.d + oco), 1, c.st));
-    s.d2h(oco, n * 2); s.sync();
-    g_acc.rdoq(state, (kvz_hip_coeff *)(c.h + oco), coeff_out, w, w, (int8_t)tq, (int8_t)scan_order, (int8_t)g_acc.cu_type(cur_cu),
+    auto res = k.out<kvz_hip_coeff>(n), coef = k.out<kvz_hip_coeff>(n);
+    k.upload();
+    MUST(kvz_hip_residual_batch(k.dev(ref), k.dev(pred), k.dev(res), n, st));
+    MUST(kvz_hip_transform_batch(fwd_kind, w, k.dev(res), k.dev(coef), 1, st));
+    k.download(coef);
+    g_acc.rdoq(state, k.host(coef), coeff_out, w, w, (int8_t)tq, (int8_t)scan_order, (int8_t)g_acc.cu_type(cur_cu),
                (int8_t)g_acc.cu_rdoq_tr_depth(cur_cu));
     int has = 0;
     for (size_t i = 0; i < n; ++i) has |= coeff_out[i] != 0;
     if (has) {
-      size_t oq = s.take(n * 2), q_end = s.off, odq = s.take(n * 2), ore = s.take(n);
-      std::memcpy(c.h + oq, coeff_out, n * 2);
-      s.h2d(oq, q_end - oq);
-      MUST(kvz_hip_dequant_batch(&p, (const kvz_hip_coeff *)(c.d + oq), (kvz_hip_coeff *)(c.d + odq), w, tdq, 1, c.st));
-      MUST(kvz_hip_transform_batch(inv_kind, w, (const kvz_hip_coeff *)(c.d + odq), (kvz_hip_coeff *)(c.d + ors), 1, c.st));
-      MUST(kvz_hip_reconstruct_batch((const kvz_hip_coeff *)(c.d + ors), c.d + opr, c.d + ore, n, c.st));
-      s.d2h(ore, n); s.sync();
-      for (int y = 0; y < w; ++y) std::memcpy(rec_out + (size_t)y * out_stride, c.h + ore + (size_t)y * w, (size_t)w);
+      // second phase: the levels the host chose go up; the tables, the prediction and the residual slot are on the device already
+      k.next_phase();
+      auto q = k.in<kvz_hip_coeff>(coeff_out, n);
+      auto dq = k.out<kvz_hip_coeff>(n);
+      auto rec = k.out<u8>(n);
+      k.upload();
+      MUST(kvz_hip_dequant_batch(&p, k.dev(q), k.dev(dq), w, tdq, 1, st));
+      MUST(kvz_hip_transform_batch(inv_kind, w, k.dev(dq), k.dev(res), 1, st));
+      MUST(kvz_hip_reconstruct_batch(k.dev(res), k.dev(pred), k.dev(rec), n, st));
+      k.download(rec);
+      for (int y = 0; y < w; ++y) std::memcpy(rec_out + (size_t)y * out_stride, k.host(rec) + (size_t)y * w, (size_t)w);
     } else if (rec_out != pred_in) {
       for (int y = 0; y < w; ++y) std::memcpy(rec_out + (size_t)y * out_stride, pred_in + (size_t)y * in_stride, (size_t)w);
     }
     return (unsigned)has;
   }
-  kvz_hip_quant_params p = flatten_state(state, w, tq, tdq, intra, s, c);
-  size_t orf = s.take((size_t)w * w), opr = s.take((size_t)w * w), in_end = s.off;
-  size_t ore = s.take((size_t)w * w), oco = s.take((size_t)w * w * 2), oha = s.take(4), out_end = s.off;
-  pack_rows(c.h + orf, ref_in, w, w, (size_t)in_stride); pack_rows(c.h + opr, pred_in, w, w, (size_t)in_stride);
-  s.h2d(0, in_end);
-  MUST(kvz_hip_quantize_residual_batch(&p, intra, w, color, scan_order, use_trskip, c.d + orf, c.d + opr, c.d + ore,
-                                       (kvz_hip_coeff *)(c.d + oco), (int32_t *)(c.d + oha), 1, c.st));
-  s.d2h(ore, out_end - ore); s.sync();
-  const int has = *(int32_t *)(c.h + oha);
-  std::memcpy(coeff_out, c.h + oco, (size_t)w * w * 2);
+  auto rec = k.out<u8>(n);
+  auto coef = k.out<kvz_hip_coeff>(n);
+  auto has_out = k.out<int32_t>(1);
+  k.upload();
+  MUST(kvz_hip_quantize_residual_batch(&p, intra, w, color, scan_order, use_trskip, k.dev(ref), k.dev(pred), k.dev(rec), k.dev(coef), k.dev(has_out), 1, st));
+  k.download(rec, has_out);
+  const int has = *k.host(has_out);
+  std::memcpy(coeff_out, k.host(coef), coef.bytes());
   if (has || rec_out != pred_in)
-    for (int y = 0; y < w; ++y) std::memcpy(rec_out + (size_t)y * out_stride, c.h + ore + (size_t)y * w, (size_t)w);
+    for (int y = 0; y < w; ++y) std::memcpy(rec_out + (size_t)y * out_stride, k.host(rec) + (size_t)y * w, (size_t)w);
   return (unsigned)has;
 }
 
@@ -379,22 +395,18 @@ void hip_sample(const void *encoder, kvz_hip_pixel *src, int16_t src_stride, int
 {
   (void)encoder; (void)hor_flag; (void)ver_flag;
   constexpr int TAPS = LUMA ? 8 : 4, OFF = TAPS / 2 - 1;
-  call_ctx &c = tls(); stage s(c);
+  using out_t = std::conditional_t<OUT14, int16_t, kvz_hip_pixel>;
+  dropin_call k;
   const int ww = width + TAPS - 1, wh = height + TAPS - 1;
-  size_t ow = s.take((size_t)ww * wh), ob = s.take(sizeof(kvz_hip_ipol_block)), oof = s.take(8), in_end = s.off;
-  const size_t obytes = (size_t)width * height * (OUT14 ? 2 : 1);
-  size_t oo = s.take(obytes);
-  pack_rows(c.h + ow, src - (ptrdiff_t)OFF * src_stride - OFF, ww, wh, (size_t)src_stride);
-  kvz_hip_ipol_block b = { OFF, OFF, mv[0] & (LUMA ? 3 : 7), mv[1] & (LUMA ? 3 : 7), width, height };
-  std::memcpy(c.h + ob, &b, sizeof(b));
-  uint64_t zero = 0; std::memcpy(c.h + oof, &zero, 8);
-  s.h2d(0, in_end);
-  if (LUMA) MUST(kvz_hip_sample_luma_batch(c.d + ow, (u32)ww, ww, wh, (const kvz_hip_ipol_block *)(c.d + ob), (const uint64_t *)(c.d + oof), 1, OUT14, c.d + oo, c.st));
-  else MUST(kvz_hip_sample_chroma_batch(c.d + ow, (u32)ww, ww, wh, (const kvz_hip_ipol_block *)(c.d + ob), (const uint64_t *)(c.d + oof), 1, OUT14, c.d + oo, c.st));
-  s.d2h(oo, obytes); s.sync();
-  const size_t esz = OUT14 ? 2 : 1;
+  auto win = k.in_rows(src - (ptrdiff_t)OFF * src_stride - OFF, ww, wh, (size_t)src_stride);
+  auto blk = k.in_record(kvz_hip_ipol_block{ OFF, OFF, mv[0] & (LUMA ? 3 : 7), mv[1] & (LUMA ? 3 : 7), width, height });
+  auto offs = k.in_record(uint64_t{ 0 });
+  auto out = k.out<out_t>((size_t)width * height);
+  k.upload();
+  MUST((LUMA ? kvz_hip_sample_luma_batch : kvz_hip_sample_chroma_batch)(k.dev(win), (u32)ww, ww, wh, k.dev(blk), k.dev(offs), 1, OUT14, k.dev(out), k.c.st));
+  k.download(out);
   for (int y = 0; y < height; ++y)
-    std::memcpy((u8 *)dst + (size_t)y * dst_stride * esz, c.h + oo + (size_t)y * width * esz, (size_t)width * esz);
+    std::memcpy((out_t *)dst + (size_t)y * dst_stride, k.host(out) + (size_t)y * width, (size_t)width * sizeof(out_t));
 }
 
 // epol_func (strategies-ipol.h:41-42), kvz_get_extended_block_generic (ipol-generic.c:731-784): a window that lies inside the
@@ -427,13 +439,13 @@ unsigned hip_get_extended_block(int xpos, int ypos, int mv_x, int mv_y, int off_
   const int cy0 = clampi_host(min_y, 0, ref_height - 1), cy1 = clampi_host(min_y + nrows - 1, 0, ref_height - 1);
   const int cx0 = clampi_host(min_x, 0, ref_width - 1), cx1 = clampi_host(min_x + ncols - 1, 0, ref_width - 1);
   const int rw = cx1 - cx0 + 1, rh = cy1 - cy0 + 1;
-  call_ctx &c = tls(); stage s(c);
-  size_t oi = s.take((size_t)rw * rh), in_end = s.off, oo = s.take((size_t)ncols * nrows);
-  pack_rows(c.h + oi, ref + (size_t)cy0 * ref_width + cx0, rw, rh, (size_t)ref_width);
-  s.h2d(0, in_end);
-  MUST(launch_extend_block(c.d + oi, rw, rh, cx0 - min_x, cy0 - min_y, c.d + oo, ncols, nrows, c.st));
-  s.d2h(oo, (size_t)ncols * nrows); s.sync();
-  for (int y = 0; y < nrows; ++y) std::memcpy(out->buffer + (size_t)y * out->stride, c.h + oo + (size_t)y * ncols, (size_t)ncols);
+  dropin_call k;
+  auto rect = k.in_rows(ref + (size_t)cy0 * ref_width + cx0, rw, rh, (size_t)ref_width);
+  auto win = k.out<u8>((size_t)ncols * nrows);
+  k.upload();
+  MUST(launch_extend_block(k.dev(rect), rw, rh, cx0 - min_x, cy0 - min_y, k.dev(win), ncols, nrows, k.c.st));
+  k.download(win);
+  for (int y = 0; y < nrows; ++y) std::memcpy(out->buffer + (size_t)y * out->stride, k.host(win) + (size_t)y * ncols, (size_t)ncols);
   return 0;
 }
 
@@ -446,19 +458,19 @@ void hip_filter_step(const void *encoder, kvz_hip_pixel *src, int16_t src_stride
 {
   (void)encoder;
   const int w = width, h = height, ph = h + 8, pw = w + 9;
-  call_ctx &c = tls(); stage s(c);
-  size_t ow = s.take((size_t)pw * ph), in_end = s.off;
-  size_t of = s.take((size_t)4 * w * h), oh = s.take((size_t)2 * ph * w * 2), oc = s.take((size_t)2 * ph * 2), out_end = s.off;
-  pack_rows(c.h + ow, src - (ptrdiff_t)3 * src_stride - 3, pw, ph, (size_t)src_stride);
-  s.h2d(0, in_end);
-  MUST(launch_frac_step(c.d + ow, w, h, STEP, fme_level, hpel_off_x, hpel_off_y, c.d + of, (i16 *)(c.d + oh), (i16 *)(c.d + oc), c.st));
-  s.d2h(of, out_end - of); s.sync();
-  for (int k = 0; k < 4; ++k)
-    for (int y = 0; y < h; ++y) std::memcpy(&filtered[k][y * 64], c.h + of + ((size_t)k * h + y) * w, (size_t)w);
+  dropin_call k;
+  auto win = k.in_rows(src - (ptrdiff_t)3 * src_stride - 3, pw, ph, (size_t)src_stride);
+  auto filt = k.out<u8>((size_t)4 * w * h);
+  auto hor = k.out<i16>((size_t)2 * ph * w), cols = k.out<i16>((size_t)2 * ph);
+  k.upload();
+  MUST(launch_frac_step(k.dev(win), w, h, STEP, fme_level, hpel_off_x, hpel_off_y, k.dev(filt), k.dev(hor), k.dev(cols), k.c.st));
+  k.download(filt, cols);
+  for (int i = 0; i < 4; ++i)
+    for (int y = 0; y < h; ++y) std::memcpy(&filtered[i][y * 64], k.host(filt) + ((size_t)i * h + y) * w, (size_t)w);
   if (STEP == 0 || STEP == 2) {
     // step 0 fills hor_intermediate[0],[1] and hor_first_cols[0],[2]; step 2 fills [3],[4] and [1],[3]
     const int hslot[2] = { STEP == 0 ? 0 : 3, STEP == 0 ? 1 : 4 }, cslot[2] = { STEP == 0 ? 0 : 1, STEP == 0 ? 2 : 3 };
-    const i16 *hsrc = (const i16 *)(c.h + oh), *csrc = (const i16 *)(c.h + oc);
+    const i16 *hsrc = k.host(hor), *csrc = k.host(cols);
     for (int p = 0; p < 2; ++p) {
       const int first_y = (STEP == 0 && p == 1 && fme_level <= 1) ? 1 : 0;
       for (int y = first_y; y < ph; ++y) {
@@ -475,18 +487,18 @@ void hip_filter_step(const void *encoder, kvz_hip_pixel *src, int16_t src_stride
 void intra_call(int log2_width, int mode, const kvz_hip_pixel *ref_above, const kvz_hip_pixel *ref_left, kvz_hip_pixel *dst)
 {
   const int n = 1 << log2_width;
-  call_ctx &c = tls(); stage s(c);
-  size_t orf = s.take(sizeof(kvz_hip_intra_ref)), in_end = s.off, oo = s.take((size_t)n * n);
+  dropin_call k;
   kvz_hip_intra_ref r;
   std::memset(&r, 0, sizeof(r));
   std::memcpy(r.left, ref_left, (size_t)2 * n + 1);
   std::memcpy(r.top, ref_above, (size_t)2 * n + 1);
-  std::memcpy(c.h + orf, &r, sizeof(r));
-  s.h2d(0, in_end);
+  auto ref = k.in_record(r);
+  auto out = k.out<u8>((size_t)n * n);
+  k.upload();
   const int8_t m = (int8_t)mode;
-  MUST(kvz_hip_intra_predict_batch(log2_width, KVZ_HIP_INTRA_RAW, (const kvz_hip_intra_ref *)(c.d + orf), 1, &m, 1, c.d + oo, c.st));
-  s.d2h(oo, (size_t)n * n); s.sync();
-  std::memcpy(dst, c.h + oo, (size_t)n * n);
+  MUST(kvz_hip_intra_predict_batch(log2_width, KVZ_HIP_INTRA_RAW, k.dev(ref), 1, &m, 1, k.dev(out), k.c.st));
+  k.download(out);
+  std::memcpy(dst, k.host(out), out.bytes());
 }
 
 void hip_angular_pred(const int_fast8_t log2_width, const int_fast8_t intra_mode, const kvz_hip_pixel *const in_ref_above,
@@ -508,12 +520,20 @@ void hip_intra_pred_planar(const int_fast8_t log2_width, const kvz_hip_pixel *co
 // against the compiled reference)
 struct sao_info_mirror { int type, eo_class, ddistortion, merge_left_flag, merge_up_flag, band_position[2], offsets[10]; };
 
-// orig / rec are contiguous bw x bh blocks (sao-generic.c:46-109)
-static void sao_stage_pair(call_ctx &c, stage &s, const kvz_hip_pixel *orig, const kvz_hip_pixel *rec, int n, size_t &oo, size_t &orr)
+// The three statistics: orig / rec are contiguous bw x bh blocks (sao-generic.c:46-109), n_prm ints of parameters follow them
+// (none for calc_sao_edge_dir), n_out ints come back.  Returns the results in k's host buffer.
+template <typename F>
+const int32_t *sao_stats(dropin_call &k, const kvz_hip_pixel *orig, const kvz_hip_pixel *rec, int bw, int bh, const int32_t *prm, size_t n_prm,
+                         size_t n_out, F entry)
 {
-  oo = s.take((size_t)n); orr = s.take((size_t)n);
-  std::memcpy(c.h + oo, orig, (size_t)n);
-  std::memcpy(c.h + orr, rec, (size_t)n);
+  auto o = k.in(orig, (size_t)(bw * bh)), r = k.in(rec, (size_t)(bw * bh));
+  slot<int32_t> p;
+  if (n_prm) p = k.in(prm, n_prm);
+  auto d = k.out<int32_t>(n_out);
+  k.upload();
+  entry(k.dev(o), k.dev(r), k.dev(p), k.dev(d), k.c.st);
+  k.download(d);
+  return k.host(d);
 }
 
 int hip_sao_edge_ddistortion(const kvz_hip_pixel *orig_data, const kvz_hip_pixel *rec_data, int block_width, int block_height,
@@ -521,17 +541,11 @@ int hip_sao_edge_ddistortion(const kvz_hip_pixel *orig_data, const kvz_hip_pixel
 {
   if (block_width < 1 || block_height < 1 || block_width > 64 || block_height > 64 || eo_class < 0 || eo_class > 3)
     die("sao_edge_ddistortion: bad arguments", KVZ_HIP_ERR_INVALID);
-  call_ctx &c = tls(); stage s(c);
-  size_t oo, orr;
-  sao_stage_pair(c, s, orig_data, rec_data, block_width * block_height, oo, orr);
-  size_t of = s.take(80), in_end = s.off, od = s.take(16);
+  dropin_call k;
   int32_t offs[20] = { 0 };
-  for (int k = 0; k < 5; ++k) offs[eo_class * 5 + k] = offsets[k];
-  std::memcpy(c.h + of, offs, sizeof(offs));
-  s.h2d(0, in_end);
-  MUST(kvz_hip_sao_edge_ddistortion_batch(c.d + oo, c.d + orr, block_width, block_height, 1, (const int32_t *)(c.d + of), (int32_t *)(c.d + od), c.st));
-  s.d2h(od, 16); s.sync();
-  return ((const int32_t *)(c.h + od))[eo_class];
+  for (int i = 0; i < 5; ++i) offs[eo_class * 5 + i] = offsets[i];
+  return sao_stats(k, orig_data, rec_data, block_width, block_height, offs, 20, 4, [=](const u8 *o, const u8 *r, const int32_t *prm, int32_t *d, hipStream_t st) {
+    MUST(kvz_hip_sao_edge_ddistortion_batch(o, r, block_width, block_height, 1, prm, d, st)); })[eo_class];
 }
 
 void hip_calc_sao_edge_dir(const kvz_hip_pixel *orig_data, const kvz_hip_pixel *rec_data, int eo_class, int block_width, int block_height,
@@ -539,15 +553,10 @@ void hip_calc_sao_edge_dir(const kvz_hip_pixel *orig_data, const kvz_hip_pixel *
 {
   if (block_width < 1 || block_height < 1 || block_width > 64 || block_height > 64 || eo_class < 0 || eo_class > 3)
     die("calc_sao_edge_dir: bad arguments", KVZ_HIP_ERR_INVALID);
-  call_ctx &c = tls(); stage s(c);
-  size_t oo, orr;
-  sao_stage_pair(c, s, orig_data, rec_data, block_width * block_height, oo, orr);
-  size_t in_end = s.off, od = s.take(160);
-  s.h2d(0, in_end);
-  MUST(kvz_hip_sao_edge_stats_batch(c.d + oo, c.d + orr, block_width, block_height, 1, (int32_t *)(c.d + od), c.st));
-  s.d2h(od, 160); s.sync();
-  const int32_t *r = (const int32_t *)(c.h + od) + eo_class * 10;
-  for (int k = 0; k < 5; ++k) { cat_sum_cnt[0][k] += r[k]; cat_sum_cnt[1][k] += r[5 + k]; }   // the reference accumulates
+  dropin_call k;
+  const int32_t *r = sao_stats(k, orig_data, rec_data, block_width, block_height, nullptr, 0, 40, [=](const u8 *o, const u8 *rec, const int32_t *, int32_t *d, hipStream_t st) {
+    MUST(kvz_hip_sao_edge_stats_batch(o, rec, block_width, block_height, 1, d, st)); }) + eo_class * 10;
+  for (int i = 0; i < 5; ++i) { cat_sum_cnt[0][i] += r[i]; cat_sum_cnt[1][i] += r[5 + i]; }   // the reference accumulates
 }
 
 int hip_sao_band_ddistortion(const void *state, const kvz_hip_pixel *orig_data, const kvz_hip_pixel *rec_data, int block_width,
@@ -555,17 +564,10 @@ int hip_sao_band_ddistortion(const void *state, const kvz_hip_pixel *orig_data, 
 {
   (void)state;                                         // only encoder_control->bitdepth is read; the hooks register for 8 bits
   if (block_width < 1 || block_height < 1 || block_width > 64 || block_height > 64) die("sao_band_ddistortion: bad arguments", KVZ_HIP_ERR_INVALID);
-  call_ctx &c = tls(); stage s(c);
-  size_t oo, orr;
-  sao_stage_pair(c, s, orig_data, rec_data, block_width * block_height, oo, orr);
-  size_t ob = s.take(32), in_end = s.off, od = s.take(16);
-  int32_t v[5] = { band_pos, sao_bands[0], sao_bands[1], sao_bands[2], sao_bands[3] };
-  std::memcpy(c.h + ob, v, sizeof(v));
-  s.h2d(0, in_end);
-  MUST(kvz_hip_sao_band_ddistortion_batch(c.d + oo, c.d + orr, block_width, block_height, 1, (const int32_t *)(c.d + ob),
-                                          (const int32_t *)(c.d + ob) + 1, (int32_t *)(c.d + od), c.st));
-  s.d2h(od, 16); s.sync();
-  return *(const int32_t *)(c.h + od);
+  dropin_call k;
+  const int32_t v[5] = { band_pos, sao_bands[0], sao_bands[1], sao_bands[2], sao_bands[3] };
+  return *sao_stats(k, orig_data, rec_data, block_width, block_height, v, 5, 4, [=](const u8 *o, const u8 *r, const int32_t *prm, int32_t *d, hipStream_t st) {
+    MUST(kvz_hip_sao_band_ddistortion_batch(o, r, block_width, block_height, 1, prm, prm + 1, d, st)); });
 }
 
 void hip_sao_reconstruct_color(const void *encoder, const kvz_hip_pixel *rec_data, kvz_hip_pixel *new_rec_data, const void *sao_in,
@@ -579,23 +581,20 @@ void hip_sao_reconstruct_color(const void *encoder, const kvz_hip_pixel *rec_dat
   const int band = sao->type == 1, cls = sao->eo_class & 3;
   const int rx = (!band && cls != 1) ? 1 : 0, ry = (!band && cls != 0) ? 1 : 0;
   const int ww = block_width + 2 * rx, wh = block_height + 2 * ry;
-  call_ctx &c = tls(); stage s(c);
-  size_t ow = s.take((size_t)ww * wh), ob = s.take(sizeof(kvz_hip_sao_block)), oi = s.take(sizeof(kvz_hip_sao_info)), in_end = s.off;
-  size_t oo = s.take((size_t)ww * wh);
-  pack_rows(c.h + ow, rec_data - (ptrdiff_t)ry * stride - rx, ww, wh, (size_t)stride);
-  kvz_hip_sao_block b = { rx, ry, block_width, block_height, 0 };
   kvz_hip_sao_info info;
   info.type = band ? 1 : 2; info.eo_class = sao->eo_class;
   info.band_position[0] = sao->band_position[0]; info.band_position[1] = sao->band_position[1];
-  for (int k = 0; k < 10; ++k) info.offsets[k] = sao->offsets[k];
-  std::memcpy(c.h + ob, &b, sizeof(b));
-  std::memcpy(c.h + oi, &info, sizeof(info));
-  s.h2d(0, in_end);
-  MUST(kvz_hip_sao_reconstruct_color_batch(c.d + ow, (u32)ww, ww, wh, c.d + oo, (u32)ww, (const kvz_hip_sao_block *)(c.d + ob), 1,
-                                           (const kvz_hip_sao_info *)(c.d + oi), 1, color_i, c.st));
-  s.d2h(oo, (size_t)ww * wh); s.sync();
+  for (int i = 0; i < 10; ++i) info.offsets[i] = sao->offsets[i];
+  dropin_call k;
+  auto win = k.in_rows(rec_data - (ptrdiff_t)ry * stride - rx, ww, wh, (size_t)stride);
+  auto blk = k.in_record(kvz_hip_sao_block{ rx, ry, block_width, block_height, 0 });
+  auto inf = k.in_record(info);
+  auto out = k.out<u8>((size_t)ww * wh);
+  k.upload();
+  MUST(kvz_hip_sao_reconstruct_color_batch(k.dev(win), (u32)ww, ww, wh, k.dev(out), (u32)ww, k.dev(blk), 1, k.dev(inf), 1, color_i, k.c.st));
+  k.download(out);
   for (int y = 0; y < block_height; ++y)
-    std::memcpy(new_rec_data + (size_t)y * new_stride, c.h + oo + (size_t)(y + ry) * ww + rx, (size_t)block_width);
+    std::memcpy(new_rec_data + (size_t)y * new_stride, k.host(out) + (size_t)(y + ry) * ww + rx, (size_t)block_width);
 }
 
 // inter_recon_bipred_func (strategies-picture.h:117-130, picture-generic.c:538-588): the lcu_t / hi_prec_buf_t
@@ -613,23 +612,27 @@ void hip_inter_recon_bipred(const int hi_prec_luma_rec0, const int hi_prec_luma_
     { hi_prec_chroma_rec0, hi_prec_chroma_rec1, (hp0 ? g_acc.hi_prec_v(hp0) : nullptr), (hp1 ? g_acc.hi_prec_v(hp1) : nullptr), temp_lcu_v, g_acc.lcu_rec_v(lcu), width >> 1, height >> 1, (xpos >> 1) & 31, (ypos >> 1) & 31, 32 } };
   for (const plane &p : pl) {
     if (p.w <= 0 || p.h <= 0) continue;
-    call_ctx &c = tls(); stage s(c);
+    dropin_call k;
     const size_t n = (size_t)p.w * p.h;
-    size_t o0 = s.take(n * 2), o1 = s.take(n * 2), in_end = s.off, od = s.take(n);
+    // a source is 14-bit samples or pixels by its hi flag (the blend entry takes it as void *): the slot holds the wider form
+    auto s0 = k.in<int16_t>(n), s1 = k.in<int16_t>(n);
+    auto dst = k.out<u8>(n);
+    int16_t *w0 = k.host(s0), *w1 = k.host(s1);
+    u8 *b0 = (u8 *)w0, *b1 = (u8 *)w1;
     // the reference wraps coordinates inside the LCU: (pos + t) & (LCU_WIDTH - 1)
     for (int y = 0; y < p.h; ++y)
       for (int x = 0; x < p.w; ++x) {
         const int yy = (p.y + y) & (p.stride - 1), xx = (p.x + x) & (p.stride - 1), i = yy * p.stride + xx;
-        if (p.hi0) ((int16_t *)(c.h + o0))[y * p.w + x] = p.h0[i]; else (c.h + o0)[y * p.w + x] = p.t0[i];
-        if (p.hi1) ((int16_t *)(c.h + o1))[y * p.w + x] = p.h1[i]; else (c.h + o1)[y * p.w + x] = p.rec[i];
+        if (p.hi0) w0[y * p.w + x] = p.h0[i]; else b0[y * p.w + x] = p.t0[i];
+        if (p.hi1) w1[y * p.w + x] = p.h1[i]; else b1[y * p.w + x] = p.rec[i];
       }
-    s.h2d(0, in_end);
-    MUST(kvz_hip_bipred_blend_batch(p.w, p.h, p.hi0, c.d + o0, p.hi1, c.d + o1, c.d + od, 1, c.st));
-    s.d2h(od, n); s.sync();
+    k.upload();
+    MUST(kvz_hip_bipred_blend_batch(p.w, p.h, p.hi0, k.dev(s0), p.hi1, k.dev(s1), k.dev(dst), 1, k.c.st));
+    k.download(dst);
     for (int y = 0; y < p.h; ++y)
       for (int x = 0; x < p.w; ++x) {
         const int yy = (p.y + y) & (p.stride - 1), xx = (p.x + x) & (p.stride - 1);
-        p.rec[yy * p.stride + xx] = (c.h + od)[y * p.w + x];
+        p.rec[yy * p.stride + xx] = k.host(dst)[y * p.w + x];
       }
   }
 }
@@ -645,19 +648,19 @@ void hip_array_checksum(const kvz_hip_pixel *data, const int height, const int w
   u32 sum = 0;
   if (width > 0 && height > 0) {
     if (width > 65536) die("array_checksum: bad arguments", KVZ_HIP_ERR_INVALID);
-    call_ctx &c = tls(); stage s(c);
+    dropin_call k;
     // what a band needs beside its pixels: one value per 64 x 64 block and the result
-    const int fit = (int)((c.cap - (c.cap >> 4)) / (size_t)width), band = fit < height ? fit : height;
-    const size_t blocks = kvz_hip_array_checksum_blocks(width, band);
-    const size_t od = s.take((size_t)width * band), in_end = s.off, ob = s.take(blocks * 4), oc = s.take(4);
+    const int fit = (int)((k.c.cap - (k.c.cap >> 4)) / (size_t)width), band = fit < height ? fit : height;
+    auto rows_in = k.in<u8>((size_t)width * band);
+    auto block_sums = k.out<u32>(kvz_hip_array_checksum_blocks(width, band)), band_sum = k.out<u32>(1);
     for (int y0 = 0; y0 < height; y0 += band) {
       const int rows = height - y0 < band ? height - y0 : band;
-      pack_rows(c.h + od, data + (size_t)y0 * stride, width, rows, (size_t)stride);
-      s.h2d(0, in_end);
-      const kvz_hip_hash_plane p = { c.d + od, width, rows, (u32)width, 0 };
-      MUST(array_checksum_launch(&p, &y0, 1, (u32 *)(c.d + ob), (u32 *)(c.d + oc), c.st, "array_checksum"));
-      s.d2h(oc, 4); s.sync();
-      sum += *(u32 *)(c.h + oc);
+      pack_rows(k.host(rows_in), data + (size_t)y0 * stride, width, rows, (size_t)stride);
+      k.upload();
+      const kvz_hip_hash_plane p = { k.dev(rows_in), width, rows, (u32)width, 0 };
+      MUST(array_checksum_launch(&p, &y0, 1, k.dev(block_sums), k.dev(band_sum), k.c.st, "array_checksum"));
+      k.download(band_sum);
+      sum += *k.host(band_sum);
     }
   }
   checksum_out[0] = (unsigned char)(sum >> 24);

@@ -303,6 +303,139 @@ def test_device_staging_mode_in_a_child_process():
     assert out.returncode == 0 and "child ok" in out.stdout, out.stderr[-2000:]
 
 
+# Every registered drop-in type once with explicit staging copies, at the smallest shapes at which a copy range can be wrong: slot
+# sizes that are no multiple of 16 and more than one output.  eq() compares arrays, tuples of arrays and plain numbers.
+COPY_MODE_CHILD = r"""
+import ctypes as C, os, sys
+sys.path.insert(0, %(tests)r)
+import numpy as np
+import gen_picture_hash_golden as G, ref_lib as R
+L = R.lib(); L.ref_register_hip.restype = C.c_int; L.ref_register_hip.argtypes = [C.c_char_p]
+assert L.ref_register_hip(%(lib)r.encode()) > 0
+H = C.CDLL(%(lib)r, mode=C.RTLD_GLOBAL)
+H.kvz_hip_dropin_calls.restype = C.c_ulonglong
+H.kvz_strategy_register_nal_hip.argtypes = [C.c_void_p, C.c_uint8]
+fns = G.reference_functions()                                # the reference's nal group, then ours beside it
+assert H.kvz_strategy_register_nal_hip(C.c_void_p(L.ref_list()), 8) == 1
+registered = {t for (t, n, _) in R.strategies() if n == "hip"}
+called = set()
+g = np.random.default_rng(12)
+u8 = lambda *shape: g.integers(0, 256, shape, dtype=np.uint8)
+
+def eq(a, b):
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(eq(x, y) for x, y in zip(a, b))
+    return bool(np.array_equal(np.asarray(a), np.asarray(b)))
+
+def both(types, f):
+    # f(name) for "hip" and "generic": equal results, and at least one drop-in call counted
+    before = H.kvz_hip_dropin_calls()
+    got = f("hip")
+    assert H.kvz_hip_dropin_calls() > before, types
+    assert eq(got, f("generic")), (types, got)
+    called.update([types] if isinstance(types, str) else types)
+
+# ---- picture group ----
+a, b = u8(80 * 80), u8(100 * 80)
+for (w, h) in ((3, 5), (65, 2)):
+    both("reg_sad", lambda nm: R.reg_sad(a, b, 3, 7, w, h, 80, 100, nm))
+for n in (4, 8, 16, 32, 64):
+    x, y = u8(1, n * n), u8(1, n * n)
+    preds, orig = R._aligned(u8(1024 + 64 * 64)), R._aligned(y)     # two predictions 1024 bytes apart: 64x64 ones overlap, like the caller's
+    for kind in ("sad", "satd"):
+        both("%%s_%%dx%%d" %% (kind, n, n), lambda nm: R.cost_nxn_batch(kind, n, x, y, nm))
+        def dual(nm):
+            out = np.zeros(2, dtype=np.uint32)
+            L.ref_cost_nxn_dual(("%%s_%%dx%%d_dual" %% (kind, n, n)).encode(), nm.encode(), preds.ctypes.data, orig.ctypes.data, R._p(out, R.u32p))
+            return out
+        both("%%s_%%dx%%d_dual" %% (kind, n, n), dual)
+both("satd_any_size", lambda nm: R.satd_any_size(12, 4, a, 3, 80, b, 7, 100, nm))
+quad = [u8(64 * 72) for _ in range(4)]
+both("satd_any_size_quad", lambda nm: R.satd_any_size_quad(8, 8, quad, 64, b, 11, 100, nm))
+both("pixels_calc_ssd", lambda nm: R.pixels_calc_ssd(a, 2, b, 5, 80, 100, 4, nm))
+hp0 = [g.integers(-2000, 18000, n).astype(np.int16) for n in (4096, 1024, 1024)]
+hp1 = [g.integers(-2000, 18000, n).astype(np.int16) for n in (4096, 1024, 1024)]
+rec, tmp = [u8(n) for n in (4096, 1024, 1024)], [u8(n) for n in (4096, 1024, 1024)]
+for hi in ((1, 1, 1, 1), (0, 1, 1, 0)):                      # one 4x4 PU: chroma 2x2
+    both("inter_recon_bipred", lambda nm: R.bipred(hi, 4, 4, 12, 8, hp0, hp1, rec, tmp, nm))
+
+# ---- dct group ----
+for kind, n in sorted(R._TR_TYPE):
+    x = g.integers(-255, 256, (1, n * n)).astype(np.int16)
+    both(R._TR_TYPE[(kind, n)], lambda nm: R.transform_batch(kind, n, x, nm))
+
+# ---- quant group ----
+c17 = g.integers(-3000, 3001, 17).astype(np.int16)
+both("coeff_abs_sum", lambda nm: R.coeff_abs_sum(c17, nm))
+coef = g.integers(-2500, 2501, (1, 16)).astype(np.int16)
+both("quant", lambda nm: R.quant_batch(coef, 4, 27, 0, 0, 1, 1, 1, 1, nm))
+q = R.quant_batch(coef, 4, 27, 0, 0, 1, 1, 1, 1, "generic")
+assert q.any()
+both("dequant", lambda nm: R.dequant_batch(q, 4, 27, 0, 1, 1, nm))
+for w in (4, 32):
+    ref_in = u8(1, w * w)
+    pred = np.clip(ref_in.astype(int) + g.integers(-30, 31, ref_in.shape), 0, 255).astype(np.uint8)
+    for sl in (0, 1):                                        # the plain route: three outputs, with the two tables in front when sl
+        both("quantize_residual", lambda nm: R.quantize_residual_batch(ref_in, pred, w, 24, 0, 0, 1, 1, 1, 0, nm, sl))
+    assert R.quantize_residual_batch(ref_in, pred, w, 24, 0, 0, 1, 1, 1, 0, "generic")[2].all()
+
+# ---- interpolation group ----
+frame = u8(96, 96)
+for kind, t, (fx, fy) in (("luma", "sample_quarterpel_luma", (1, 3)), ("luma14", "sample_14bit_quarterpel_luma", (3, 2)),
+                          ("chroma", "sample_octpel_chroma", (3, 5)), ("chroma14", "sample_14bit_octpel_chroma", (7, 1))):
+    both(t, lambda nm: R.sample(kind, frame, 12, 10, 5, 3, fx, fy, nm))
+both(("filter_hpel_blocks_hor_ver_luma", "filter_hpel_blocks_diag_luma", "filter_qpel_blocks_hor_ver_luma", "filter_qpel_blocks_diag_luma"),
+     lambda nm: R.filter_frac_steps(frame, 10, 9, 8, 8, (1, -1), 4, nm)[:, :, :8, :8])
+both("get_extended_block", lambda nm: R.get_extended_block(frame, 0, 0, -2, -1, 8, 9, 9, name=nm))     # over the top-left corner
+assert R.get_extended_block(frame, 0, 0, -2, -1, 8, 9, 9, name="hip")[1] == 1
+
+# ---- intra group ----
+top, left = u8(65), u8(65)
+for log2_width in (2, 5):
+    both("angular_pred", lambda nm: R.angular_pred(log2_width, 7, top, left, nm))
+both("intra_pred_planar", lambda nm: R.intra_pred_planar(2, top, left, nm))
+
+# ---- sao group ----
+orig = u8(64 * 64)
+noisy = np.clip(orig.astype(int) + g.integers(-9, 10, orig.shape), 0, 255).astype(np.uint8)
+offs, bands = g.integers(-7, 8, 5), g.integers(-7, 8, 4)
+both("sao_edge_ddistortion", lambda nm: R.sao_edge_ddistortion(orig[:15], noisy[:15], 5, 3, 3, offs, nm))
+both("calc_sao_edge_dir", lambda nm: R.calc_sao_edge_dir(orig[:15], noisy[:15], 2, 5, 3, nm))
+both("sao_band_ddistortion", lambda nm: R.sao_band_ddistortion(orig, noisy, 64, 64, 9, bands, nm))
+edge135 = np.array([2, 2, 0, 0, 0, 3, -2, 1, -4, 0, 0, 0, 0, 0], dtype=np.int32)       # type edge, a diagonal class
+both("sao_reconstruct_color", lambda nm: R.sao_reconstruct_color(frame, 5, 3, 7, 5, edge135, 0, nm))
+
+# ---- nal group, reached as tests/test_gpu_picture_hash.py reaches it ----
+hip_sum = G.CHECKSUM_FN(L.ref_strategy(b"array_checksum", b"hip"))
+for (w, h) in ((13, 7), (2048, 600)):                        # 2048 x 600 exceeds the staging buffer: two bands
+    plane = u8(h, w + 3)
+    both("array_checksum", lambda nm: G.call(hip_sum if nm == "hip" else fns["generic"], plane, w, h))
+
+assert called == registered, (sorted(registered - called), sorted(called - registered))
+
+# ---- the RDOQ route of quantize_residual: ref_lib's per-call helper keeps RDOQ off, so a small encode with it on ----
+frames = R.synthetic_sequence(64, 64, 2)
+opts = "preset=ultrafast,rdoq=1,rdoq-skip=0,signhide=1,qp=27,threads=0"
+gen, _ = R.encode(frames, 64, 64, opts, "generic")
+before = H.kvz_hip_dropin_calls()
+hipb, _ = R.encode(frames, 64, 64, opts, "hip")
+assert H.kvz_hip_dropin_calls() - before > 100 and len(gen) > 100 and hipb == gen, (len(gen), len(hipb))
+print("child ok")
+"""
+
+
+def test_every_dropin_type_with_staging_copies_in_a_child_process():
+    """KVZ_HIP_ZEROCOPY=0 for every registered type (the nal group's included), each against generic through the compiled reference's
+    registry: in this mode alone the upload and download ranges of the staging buffer decide what a kernel reads and what the caller
+    gets back.  The child checks that the types it called are the types registered."""
+    import subprocess
+    import sys
+    code = COPY_MODE_CHILD % {"tests": os.path.join(ROOT, "tests"), "lib": os.path.join(ROOT, "kvazaar_amd", "libkvzhip.so")}
+    env = dict(os.environ, KVZ_HIP_ZEROCOPY="0")
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and "child ok" in out.stdout, (out.stdout[-1000:], out.stderr[-3000:])
+
+
 def test_quant_group_registers_only_what_its_accessors_support():
     """kvz_strategy_register_quant_hip with partial accessor tables: a function whose state accessors are missing is not
     registered (the host keeps its next-best strategy) instead of aborting or diverging at run time.  Own process: the
