@@ -83,28 +83,64 @@ KVZ_HIP_API const char *kvz_hip_device_name(void);   /* of the calling thread's 
                                    4: kvz_hip_me_params.n_cabac (was reserved), the search service, kvz_hip_halo_exchange */
 KVZ_HIP_API int kvz_hip_abi_version(void);
 
-/* Launch-geometry / kernel-selection knobs for A/B runs (tools/bench_all.py --tune key=v1,v2);
- * value < 0 restores the built-in default.  Keys: "{sad,satd8,dct,dct4,idct4,dct16,idct16,dct32,idct32,quant,qr,qr4,qr8,
- * qr16,qr32}_wgs_per_cu" (workgroups per CU of the streaming grids; 0 counts as 1),
- * "qr4_lane_kernel", "qr8_reg_kernel", "qr_tile_kernel" (0: the LDS butterfly kernel instead of the register / matrix-core ones), "dct4_tile" (0: the LDS butterfly kernel for 4x4 transforms), "sao_edge_fast" (0/1),
- * "intra_rough_waves" (4/8 waves per workgroup of the rough search), "pair_wave_kernel" (0/1: one wave per
- * descriptor for frame-level pair batches of up to 4096 descriptors), "wg_chunk_min_wgs" (the workgroup-per-descriptor
- * kernels of the sampling / fractional search entries take up to 64 descriptors per workgroup once the list would give
- * more workgroups than this; 0: always one), "pair_satd_threads" (128 / 256 / 512 threads per workgroup of the
- * descriptor SATD kernel), "qr8_tile_kernel" (0: 8x8 TUs of the fused quantize_residual on the register kernel instead of sixteen to a
- * matrix-core tile), "qr_tile_pipe" (0: the tile kernels' wait on vector memory left to the compiler instead of placed before the
- * iteration's first store), "pipe" / "dct_pipe" (1: the same hand placement in the 4x4 / 8x8 register kernels / the 32x32
- * transform, where it measured slower), "cost_store_nt" (0: the 8x8 SAD and SATD batch kernels store their costs with the
- * default cache policy instead of the nontemporal one), "full_qsad" (0: the search service's exhaustive search prices positions with v_sad_u8 on
- * byte-aligned operands instead of four alignments per v_qsad_pk_u16_u8), "sample8_wave" (0: 8x8 luma blocks of the sampling entry
- * on the general path), "service_workers" (resident workgroups of the search service, 0: a launch per batch), "service_push" (0: the workers read the units from
- * host memory even where the host could write them into device memory through a large BAR), "service_linger_us" /
- * "service_life_ms" (how long they stay without work / at most), "service_inflight" / "service_streams" (batches in the air and
- * launch streams of the launch-per-batch way), "service_spin_us" / "service_spin_crowded_us" / "service_nap_us" (how long a caller polls for its answer
- * before it naps: 100 us with a core per caller, 5 us and naps of 10 us with more callers than cores), "service_ticket_base_k" (tests: first ticket of the ring x 1024); the service reads its knobs when it is created.  KVZ_HIP_SERVICE_DEBUG in the
- * environment: a few lines of the workers' own timing on stderr when a service is destroyed.
- * Returns KVZ_HIP_OK or KVZ_HIP_ERR_INVALID (unknown key).  The environment variable KVZ_HIP_TUNE="key=value,..." presets
- * knobs at kvz_hip_init() for A/B runs of an unmodified host. */
+/* Launch-geometry / kernel-selection knobs for A/B runs (tools/bench_all.py --tune key=v1,v2); value < 0 restores the built-in
+ * default.  Returns KVZ_HIP_OK or KVZ_HIP_ERR_INVALID (unknown key).  The environment variable KVZ_HIP_TUNE="key=value,..." presets
+ * knobs at kvz_hip_init() for A/B runs of an unmodified host.  The keys, each with its default and meaning ("*_wgs_per_cu":
+ * workgroups per CU of a streaming grid, 0 counts as 1; "per site": the kernels behind the key each have their own default):
+ *   "sad_wgs_per_cu"           256       the SAD batch kernels
+ *   "satd8_wgs_per_cu"         256       the 8x8 SATD batch kernel
+ *   "dct32_wgs_per_cu"         4096      the 32x32 forward transform
+ *   "idct32_wgs_per_cu"        96        the 32x32 inverse transform
+ *   "dct_wgs_per_cu"           per site  the LDS butterfly transforms: 8x8 160, 16x16 48, other sizes 16
+ *   "qr32_wgs_per_cu"          8         the 32x32 matrix-core tile kernel of the fused quantize_residual
+ *   "qr_wgs_per_cu"            per site  the LDS butterfly kernel of quantize_residual: 8x8 64, other sizes 16
+ *   "dct16_wgs_per_cu"         128       the 16x16 forward transform
+ *   "idct16_wgs_per_cu"        64        the 16x16 inverse transform
+ *   "qr16_wgs_per_cu"          8         the 16x16 matrix-core tile kernel of quantize_residual
+ *   "qr4_lane_kernel"          1         0: the LDS butterfly kernel instead of the 4x4 lane kernel of quantize_residual
+ *   "sao_edge_fast"            1         0/1: the packed-accumulator kernel of the SAO edge statistics
+ *   "intra_rough_waves"        per site  4/8 waves per workgroup of the rough search: 4x4 8, other sizes 4
+ *   "pair_wave_kernel"         1         0/1: one wave per descriptor for frame-level pair batches of up to 4096 descriptors
+ *   "qr4_wgs_per_cu"           96        the 4x4 lane kernel of quantize_residual
+ *   "quant_wgs_per_cu"         256       quant and dequant
+ *   "qr8_reg_kernel"           1         0: the LDS butterfly kernel instead of the 8x8 register kernel of quantize_residual
+ *   "qr8_wgs_per_cu"           per site  8x8 quantize_residual: the matrix-core tile kernel 8, the register kernel 32
+ *   "qr_tile_kernel"           1         0: the LDS butterfly (8x8: the register) kernel instead of the matrix-core tile kernels
+ *   "dct4_tile"                1         0: the LDS butterfly kernel for 4x4 transforms
+ *   "dct4_wgs_per_cu"          192       the 4x4 forward transform
+ *   "idct4_wgs_per_cu"         64        the 4x4 inverse transform
+ *   "wg_chunk_min_wgs"         4096      the workgroup-per-descriptor kernels of the sampling / fractional search entries take up to 64
+ *                                        descriptors per workgroup once the list would give more workgroups than this; 0: always one
+ *   "pair_satd_threads"        256       128 / 256 / 512 threads per workgroup of the descriptor SATD kernel
+ *   "qr8_tile_kernel"          1         0: 8x8 TUs of the fused quantize_residual on the register kernel instead of sixteen to a
+ *                                        matrix-core tile
+ *   "qr_tile_pipe"             1         0: the tile kernels' wait on vector memory left to the compiler instead of placed before the
+ *                                        iteration's first store
+ *   "pipe"                     0         1: the same hand placement in the 4x4 / 8x8 register kernels, where it measured slower
+ *   "dct_pipe"                 0         1: the same hand placement in the 32x32 transform, where it measured slower
+ *   "sample8_wave"             1         0: 8x8 luma blocks of the sampling entry on the general path
+ *   "full_qsad"                1         0: the search service's exhaustive search prices positions with v_sad_u8 on byte-aligned
+ *                                        operands instead of four alignments per v_qsad_pk_u16_u8
+ *   "service_streams"          8         launch streams of the launch-per-batch way
+ *   "service_inflight"         4         batches in the air of the launch-per-batch way
+ *   "service_workers"          64        resident workgroups of the search service, 0: a launch per batch
+ *   "service_linger_us"        2000      how long the workers stay without work
+ *   "service_life_ms"          20        how long the workers stay at most
+ *   "service_spin_us"          per site  how long a caller polls for its answer before it naps: 100; once set, it holds with more
+ *                                        callers than cores too
+ *   "service_ticket_base_k"    0         tests: first ticket of the ring x 1024
+ *   "service_push"             1         0: the workers read the units from host memory even where the host could write them into
+ *                                        device memory through a large BAR
+ *   "service_nap_us"           10        a caller's nap with more callers than cores
+ *   "service_spin_crowded_us"  5         how long a caller polls before it naps with more callers than cores
+ *   "event_fence"              0         what a record of this ABI's events releases: 0 nothing, 1 to the device, 2 HIP's default (below)
+ *   "event_alias"              1         0: every event record is a packet of its own (below)
+ *   "cost_store_nt"            1         0: the 8x8 SAD and SATD batch kernels store their costs with the default cache policy
+ *                                        instead of the nontemporal one
+ * The search service reads its knobs when it is created.  How long a caller polls for its answer before it naps (the keys
+ * "service_spin_us" / "service_spin_crowded_us" / "service_nap_us"): 100 us with a core per caller, 5 us and naps of 10 us with more
+ * callers than cores.
+ * KVZ_HIP_SERVICE_DEBUG in the environment: a few lines of the workers' own timing on stderr when a service is destroyed. */
 KVZ_HIP_API int kvz_hip_set_tuning(const char *key, int value);
 
 /* Thin device-memory helpers so a C host needs no HIP headers. */

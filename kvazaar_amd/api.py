@@ -8,6 +8,7 @@ Two levels:
     therefore always go through the C ABI and the GPU.
 Names follow the reference's strategy types (strategies-picture.h:174-199,
 strategies-dct.h:55-69, strategies-quant.h:58-62, strategies-ipol.h:65-74)."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -16,6 +17,25 @@ from . import _lib
 from ._lib import BlockPair, IpolBlock, QuantParams, KvzHipError, check
 
 KINDS = {"dct": 0, "idct": 1, "dst": 2, "idst": 3, "trskip": 4, "itrskip": 5}
+
+
+@contextlib.contextmanager
+def tuned(**knobs):
+    """with tuned(key=value, ...) as more: the tuning knobs (kvz_hip_set_tuning) set for the length of the block; more(key=value, ...)
+    sets further ones inside it.  Every knob touched is back at its default (-1) afterwards, also when the block raises."""
+    L = _lib.load()
+    touched = set()
+
+    def more(**kv):
+        for k, v in kv.items():
+            touched.add(k)
+            check(L.kvz_hip_set_tuning(k.encode(), int(v)), "set_tuning %s" % k)
+    try:
+        more(**knobs)
+        yield more
+    finally:
+        for k in touched:
+            L.kvz_hip_set_tuning(k.encode(), -1)
 
 
 class DeviceBuffer:

@@ -13,7 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <string>
 #include <mutex>
 
 namespace kvzhip {
@@ -32,21 +31,6 @@ static dev_ctx g_ctx[KVZ_MAX_DEVICES];
 static std::atomic<int> g_default_dev{-1};    // first device initialised: the current device of threads that never chose one
 static thread_local int t_dev = -1;           // the calling thread's current device (kvz_hip_init / kvz_hip_set_device)
 static thread_local char g_err[512] = "";     // last error of the calling thread
-
-struct tune_entry { const char *key; std::atomic<int> value; };
-static tune_entry g_tune[] = { { "sad_wgs_per_cu", {-1} }, { "satd8_wgs_per_cu", {-1} }, { "dct32_wgs_per_cu", {-1} },
-                               { "idct32_wgs_per_cu", {-1} }, { "dct_wgs_per_cu", {-1} }, { "qr32_wgs_per_cu", {-1} },
-                               { "qr_wgs_per_cu", {-1} }, { "dct16_wgs_per_cu", {-1} }, { "idct16_wgs_per_cu", {-1} },
-                               { "qr16_wgs_per_cu", {-1} }, { "qr4_lane_kernel", {-1} },
-                               { "sao_edge_fast", {-1} }, 
-                               { "intra_rough_waves", {-1} }, { "pair_wave_kernel", {-1} }, { "qr4_wgs_per_cu", {-1} }, { "quant_wgs_per_cu", {-1} },
-                               { "qr8_reg_kernel", {-1} }, { "qr8_wgs_per_cu", {-1} }, { "qr_tile_kernel", {-1} }, { "dct4_tile", {-1} }, { "dct4_wgs_per_cu", {-1} }, { "idct4_wgs_per_cu", {-1} },
-                               { "wg_chunk_min_wgs", {-1} }, { "pair_satd_threads", {-1} }, { "qr8_tile_kernel", {-1} }, { "qr_tile_pipe", {-1} }, { "pipe", {-1} }, { "dct_pipe", {-1} }, { "sample8_wave", {-1} }, { "full_qsad", {-1} }, { "service_streams", {-1} }, { "service_inflight", {-1} }, { "service_workers", {-1} }, { "service_linger_us", {-1} }, { "service_life_ms", {-1} }, { "service_spin_us", {-1} }, { "service_ticket_base_k", {-1} }, { "service_push", {-1} }, { "service_nap_us", {-1} }, { "service_spin_crowded_us", {-1} }, { "event_fence", {-1} }, { "event_alias", {-1} }, { "cost_store_nt", {-1} } };
-int tuning(const char *key, int dflt)
-{
-  for (auto &e : g_tune) if (!std::strcmp(e.key, key)) { const int v = e.value.load(std::memory_order_relaxed); return v >= 0 ? v : dflt; }
-  return dflt;
-}
 
 int ctx_device() { return t_dev >= 0 ? t_dev : g_default_dev.load(std::memory_order_acquire); }
 bool ctx_ready()
@@ -108,14 +92,14 @@ hipStream_t ctx_stream(kvz_hip_stream s)
 // the carrier pool of the calling thread's device under the current event_fence
 static int event_pool()
 {
-  int fence = tuning("event_fence", 0);
+  int fence = tuning<tune::event_fence>();
   if (fence < 0 || fence > 2) fence = 2;
   return ctx_device() * 3 + fence;
 }
 
 hipEvent_t launch_carrier(hipStream_t st)
 {
-  if (!tuning("event_alias", 1)) return nullptr;
+  if (!tuning<tune::event_alias>()) return nullptr;
   alias_table &t = aliases();
   if (!t.armed(st)) return nullptr;
   // inside a capture the record / wait pairs are the graph's fork and join edges: they stay real records
@@ -195,9 +179,10 @@ extern "C" {
 
 int kvz_hip_set_tuning(const char *key, int value)
 {
-  if (!key) return kvzhip::invalid_arg(__func__);
-  for (auto &e : g_tune) if (!std::strcmp(e.key, key)) { e.value.store(value, std::memory_order_relaxed); return KVZ_HIP_OK; }
-  return kvzhip::invalid_arg(__func__);
+  const int i = tune_find(key);
+  if (i < 0) return kvzhip::invalid_arg(__func__);      // NULL or no key of tuning.h
+  tune_value[i].store(value, std::memory_order_relaxed);
+  return KVZ_HIP_OK;
 }
 
 int kvz_hip_device_count(void)
@@ -233,21 +218,7 @@ int kvz_hip_init(int device)
   if (rc != KVZ_HIP_OK) return rc;
   if (first) {
     // A/B runs of unmodified hosts: KVZ_HIP_TUNE="key=value,key=value" presets kvz_hip_set_tuning knobs
-    if (const char *env = std::getenv("KVZ_HIP_TUNE")) {
-      std::string all(env);
-      size_t pos = 0;
-      while (pos < all.size()) {
-        size_t end = all.find(',', pos);
-        if (end == std::string::npos) end = all.size();
-        const std::string kv = all.substr(pos, end - pos);
-        const size_t eq = kv.find('=');
-        if (eq != std::string::npos) {
-          const std::string key = kv.substr(0, eq);
-          for (auto &t : g_tune) if (key == t.key) t.value.store(std::atoi(kv.c_str() + eq + 1), std::memory_order_relaxed);
-        }
-        pos = end + 1;
-      }
-    }
+    if (const char *env = std::getenv("KVZ_HIP_TUNE")) tune_apply_env(env, tune_value);
     g_default_dev.store(device, std::memory_order_release);
   }
   t_dev = device;             // like hipSetDevice: the initialising thread now works on this device
@@ -503,12 +474,12 @@ void *kvz_hip_event_create(void)
   // back and invalidates the L2 of every XCD, and the next kernel waits for that and starts on cold caches -- 1.2 us of the
   // 6 us a record costs between the launches bench.py brackets.  Tuning key event_fence, read here:
   // 0 = no system fence (default), 1 = release to the device, 2 = HIP's default event.  Timing stays enabled in all three.
-  const int fence = tuning("event_fence", 0);
+  const int fence = tuning<tune::event_fence>();
   abi_event *a = new abi_event();
   hipError_t e = hipEventCreateWithFlags(&a->own, event_flags(fence));
   if (e != hipSuccess) { set_error("hipEventCreateWithFlags", e); delete a; return nullptr; }
   // the carrier this event may come to alias is made here, not inside the launch that the event times
-  if (tuning("event_alias", 1)) aliases().provision_event(a->alias, event_pool());
+  if (tuning<tune::event_alias>()) aliases().provision_event(a->alias, event_pool());
   return (void *)a;
 }
 void kvz_hip_event_destroy(void *ev)

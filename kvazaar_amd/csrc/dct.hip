@@ -90,7 +90,7 @@ static int launch_transform(const i16 *in, i16 *out, size_t count, hipStream_t s
   constexpr int TPB = 256 / N;
   // workgroups per CU of the grid-stride launch, measured per size (0.5 GiB arrays): 4x4 is best at <= 48 (5.8 TB/s, 5.2 at 96),
   // 8x8 keeps gaining up to ~192 (6.5 TB/s against 5.8 at 16), the 16x16 inverse peaks around 48
-  const unsigned grid = stream_grid(count, TPB, (unsigned)tuning("dct_wgs_per_cu", N == 8 ? 160 : N == 16 ? 48 : 16));
+  const unsigned grid = stream_grid(count, TPB, (unsigned)tuning_or<tune::dct_wgs_per_cu>(N == 8 ? 160 : N == 16 ? 48 : 16));
   launch_carried(transform_kernel<N, KIND>, dim3(grid), dim3(256), 0, st, in, out, count);
   KVZ_CHECK_LAUNCH("transform_kernel");
   return KVZ_HIP_OK;
@@ -105,7 +105,7 @@ extern "C" int kvz_hip_transform_batch(int kind, int n, const int16_t *in, int16
   switch (kind) {
     case KVZ_HIP_DCT:
       switch (n) {
-        case 4: return tuning("dct4_tile", 1) ? launch_dct4_tile(false, false, in, out, count, st) : launch_transform<4, 0>(in, out, count, st);
+        case 4: return tuning<tune::dct4_tile>() ? launch_dct4_tile(false, false, in, out, count, st) : launch_transform<4, 0>(in, out, count, st);
         case 8: return launch_transform<8, 0>(in, out, count, st);
         case 16: return dct32_use_valu() ? launch_transform<16, 0>(in, out, count, st) : launch_dct16_tile(false, in, out, count, st);
         case 32: return dct32_use_valu() ? launch_transform<32, 0>(in, out, count, st) : launch_dct32_mfma(false, in, out, count, st);
@@ -113,7 +113,7 @@ extern "C" int kvz_hip_transform_batch(int kind, int n, const int16_t *in, int16
       break;
     case KVZ_HIP_IDCT:
       switch (n) {
-        case 4: return tuning("dct4_tile", 1) ? launch_dct4_tile(true, false, in, out, count, st) : launch_transform<4, 1>(in, out, count, st);
+        case 4: return tuning<tune::dct4_tile>() ? launch_dct4_tile(true, false, in, out, count, st) : launch_transform<4, 1>(in, out, count, st);
         case 8: return launch_transform<8, 1>(in, out, count, st);
         // four blocks per MFMA tile: 6.1-6.2 TB/s against 5.2 for the butterflies and less for the earlier two-blocks-per-tile MFMA kernel
         case 16: return dct32_use_valu() ? launch_transform<16, 1>(in, out, count, st) : launch_dct16_tile(true, in, out, count, st);
@@ -121,10 +121,10 @@ extern "C" int kvz_hip_transform_batch(int kind, int n, const int16_t *in, int16
       }
       break;
     case KVZ_HIP_DST:
-      if (n == 4) return tuning("dct4_tile", 1) ? launch_dct4_tile(false, true, in, out, count, st) : launch_transform<4, 2>(in, out, count, st);
+      if (n == 4) return tuning<tune::dct4_tile>() ? launch_dct4_tile(false, true, in, out, count, st) : launch_transform<4, 2>(in, out, count, st);
       break;
     case KVZ_HIP_IDST:
-      if (n == 4) return tuning("dct4_tile", 1) ? launch_dct4_tile(true, true, in, out, count, st) : launch_transform<4, 3>(in, out, count, st);
+      if (n == 4) return tuning<tune::dct4_tile>() ? launch_dct4_tile(true, true, in, out, count, st) : launch_transform<4, 3>(in, out, count, st);
       break;
     case KVZ_HIP_TRSKIP:
     case KVZ_HIP_ITRSKIP:

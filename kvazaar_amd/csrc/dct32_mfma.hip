@@ -154,9 +154,9 @@ int launch_dct32_mfma(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   // 164.1 against 164.9 us with a run-to-run spread of 3 %; two adjacent tiles per wave with both loads issued first (66 VGPRs):
   // 6.48 TB/s, 163.8 us; three: 6.30 TB/s (profiles/headline_kernels_ab.txt).  At 6.2 - 6.5 TB/s with as many bytes written as
   // read the kernel runs at the rate of a plain copy on this device; more waves in flight do not raise it.
-  const size_t cap = wg_cap(inverse ? tuning("idct32_wgs_per_cu", 96) : tuning("dct32_wgs_per_cu", 4096));
+  const size_t cap = wg_cap(inverse ? tuning<tune::idct32_wgs_per_cu>() : tuning<tune::dct32_wgs_per_cu>());
   if (wgs > cap) wgs = cap;
-  if (tuning("dct_pipe", 0)) {
+  if (tuning<tune::dct_pipe>()) {
     if (inverse) launch_carried(dct32_mfma_kernel<32, true, false, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
     else launch_carried(dct32_mfma_kernel<32, false, false, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
   } else if (inverse) launch_carried(dct32_mfma_kernel<32, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
@@ -171,7 +171,7 @@ int launch_dct4_tile(bool inverse, bool dst, const i16 *in, i16 *out, size_t cou
   size_t wgs = (ntiles + 3) / 4;
   // workgroups per CU (0.5 GiB arrays): forward 64: 6.20, 128: 6.37, 192: 6.42, 256: 6.29 TB/s; inverse 32: 5.89, 64: 6.18, 96: 6.05, 128: 5.80
   // (the LDS butterfly kernel these replace: 5.4 / 5.55)
-  const size_t cap = wg_cap(inverse ? tuning("idct4_wgs_per_cu", 64) : tuning("dct4_wgs_per_cu", 192));
+  const size_t cap = wg_cap(inverse ? tuning<tune::idct4_wgs_per_cu>() : tuning<tune::dct4_wgs_per_cu>());
   if (wgs > cap) wgs = cap;
   const dim3 g((unsigned)wgs), b(256);
   if (dst) {
@@ -190,7 +190,7 @@ int launch_dct16_tile(bool inverse, const i16 *in, i16 *out, size_t count, hipSt
   const size_t ntiles = (count + 3) / 4;
   size_t wgs = (ntiles + 3) / 4;
   // workgroups per CU (0.5 GiB arrays): forward 64: 6.43, 96: 6.50, 128: 6.52, 192: 6.42, 256: 6.34 TB/s; inverse 32: 6.16, 64: 6.17, 96: 5.98, 128: 5.81
-  const size_t cap = wg_cap(inverse ? tuning("idct16_wgs_per_cu", 64) : tuning("dct16_wgs_per_cu", 128));
+  const size_t cap = wg_cap(inverse ? tuning<tune::idct16_wgs_per_cu>() : tuning<tune::dct16_wgs_per_cu>());
   if (wgs > cap) wgs = cap;
   if (inverse) launch_carried(dct32_mfma_kernel<16, true>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);
   else launch_carried(dct32_mfma_kernel<16, false>, dim3((unsigned)wgs), dim3(256), 0, st, in, out, count);

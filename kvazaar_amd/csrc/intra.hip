@@ -314,7 +314,7 @@ int launch_rough(const kvz_hip_intra_ref *refs, const u8 *orig, size_t count, in
   if (wgs > 0x7fffffffu) return kvzhip::invalid_arg("kvz_hip_intra_rough_batch");
   // 4x4 PUs: 64 PUs per workgroup make it LDS-limited (31 KB), eight waves per workgroup fill the CU's wave slots
   // (3.4 against 2.7 G PUs/s); the larger sizes are register-limited and lose a third with eight (measured)
-  const int nw = tuning("intra_rough_waves", LOG2 == 2 ? 8 : 4);
+  const int nw = tuning_or<tune::intra_rough_waves>(LOG2 == 2 ? 8 : 4);
   if (nw == 8) {
     if (sad) hipLaunchKernelGGL((intra_rough_kernel<LOG2, true, 8>), dim3((unsigned)wgs), dim3(512), 0, st, refs, orig, count, flags, satd, sad);
     else hipLaunchKernelGGL((intra_rough_kernel<LOG2, false, 8>), dim3((unsigned)wgs), dim3(512), 0, st, refs, orig, count, flags, satd, sad);

@@ -265,7 +265,7 @@ __device__ __forceinline__ void sample8x8_luma_wave(int lane, u8 *s_win, u32 *s_
 // first descriptor is worked on: 1 us on a 5 us workgroup).
 static inline unsigned wg_chunk(size_t count)
 {
-  const int min_wgs = kvzhip::tuning("wg_chunk_min_wgs", 4096);      // measured: 0: 1.37 G 8x8 samples/s, 2048: 2.30, 4096: 2.27, 16384: 2.10
+  const int min_wgs = kvzhip::tuning<tune::wg_chunk_min_wgs>();      // measured: 0: 1.37 G 8x8 samples/s, 2048: 2.30, 4096: 2.27, 16384: 2.10
   if (min_wgs <= 0) return 1;
   const size_t c = count / (size_t)min_wgs;
   return (unsigned)(c < 1 ? 1 : (c > 64 ? 64 : c));
@@ -623,7 +623,7 @@ static int sample_launch(bool luma, const kvz_hip_pixel *ref, uint32_t ref_strid
   hipStream_t st = ctx_stream(s);
   const unsigned long long *oo = (const unsigned long long *)out_offsets;
   const unsigned chunk = wg_chunk(count);
-  const int s8w = kvzhip::tuning("sample8_wave", 1);          // 0: 8x8 luma blocks on the general 2 x 4-sample path (A/B)
+  const int s8w = kvzhip::tuning<tune::sample8_wave>();          // 0: 8x8 luma blocks on the general 2 x 4-sample path (A/B)
   const unsigned gs = (unsigned)((count + 3) / 4), gb = (unsigned)((count + chunk - 1) / chunk);
 #define KVZ_SAMPLE(TAPS, O14)                                                                                        \
   do {                                                                                                               \

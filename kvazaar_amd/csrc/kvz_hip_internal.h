@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "../../include/kvz_hip.h"
+#include "tuning.h"                             // the kvz_hip_set_tuning knobs: tuning<tune::key>(), tuning_or<tune::key>(dflt)
 
 typedef uint8_t u8;
 typedef uint32_t u32;
@@ -27,7 +28,6 @@ void set_error(const char *what, hipError_t e);
 void set_error_msg(const char *what);
 int invalid_arg(const char *entry);             // records "<entry>: invalid argument" and returns KVZ_HIP_ERR_INVALID
 int num_cus();
-int tuning(const char *key, int dflt);     // kvz_hip_set_tuning override or dflt
 int stream_on_current_device(kvz_hip_stream s, const char *entry);   // KVZ_HIP_ERR_INVALID for a stream of another device
 
 // ---- rectangle copies (halo.hip) ----

@@ -730,11 +730,11 @@ static int launch_sad(int n, const u8 *a, const u8 *b, size_t count, u32 *costs,
 {
   // count here = number of block pairs (2 * items for DUAL)
   const unsigned threads = 256;
-  const bool nt = tuning("cost_store_nt", 1) != 0;      // store_cost: nontemporal result stores at 8x8; 0: the default policy
+  const bool nt = tuning<tune::cost_store_nt>() != 0;      // store_cost: nontemporal result stores at 8x8; 0: the default policy
 #define KVZ_SAD_CASE(N, U, NT)                                                                    \
   case N: {                                                                                       \
     size_t chunks = count * (N * N / 16);                                                         \
-    unsigned grid = stream_grid(chunks, (threads / 64) * 64 * U, (unsigned)tuning("sad_wgs_per_cu", 256)); \
+    unsigned grid = stream_grid(chunks, (threads / 64) * 64 * U, (unsigned)tuning<tune::sad_wgs_per_cu>()); \
     if (NT && nt) launch_carried(sad_nxn_kernel<N, U, DUAL, NT>, dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
     else launch_carried(sad_nxn_kernel<N, U, DUAL>, dim3(grid), dim3(threads), 0, st, a, b, costs, count, ps, is); \
   } break;
@@ -755,15 +755,15 @@ template <bool DUAL>
 static int launch_satd(int n, const u8 *a, const u8 *b, size_t count, u32 *costs, size_t ps, size_t is, hipStream_t st)
 {
   const unsigned threads = 256;
-  const bool nt = tuning("cost_store_nt", 1) != 0;      // as in launch_sad
+  const bool nt = tuning<tune::cost_store_nt>() != 0;      // as in launch_sad
   switch (n) {
     case 4:
       if (!DUAL) launch_carried(satd4_kernel<4>, dim3(stream_grid(count, threads * 4)), dim3(threads), 0, st, a, b, costs, count);
       else launch_carried(satd_4x4_kernel<DUAL>, dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
     case 8:
-      if (!DUAL && nt) launch_carried(satd8_kernel<4, true>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
-      else if (!DUAL) launch_carried(satd8_kernel<4>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning("satd8_wgs_per_cu", 256))), dim3(threads), 0, st, a, b, costs, count);
+      if (!DUAL && nt) launch_carried(satd8_kernel<4, true>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning<tune::satd8_wgs_per_cu>())), dim3(threads), 0, st, a, b, costs, count);
+      else if (!DUAL) launch_carried(satd8_kernel<4>, dim3(stream_grid(count * 4, threads * 4, (unsigned)tuning<tune::satd8_wgs_per_cu>())), dim3(threads), 0, st, a, b, costs, count);
       else launch_carried(satd_nxn_kernel<8, DUAL>, dim3(stream_grid(count, threads)), dim3(threads), 0, st, a, b, costs, count, ps, is);
       break;
     case 16:
@@ -783,7 +783,7 @@ constexpr size_t PAIR_WAVE_MAX = 4096;      // measured: at 32 400 16x16 pairs t
 template <bool SSD>
 static void launch_pair_sad(const plane_t &p1, const plane_t &p2, const kvz_hip_block_pair *pairs, size_t count, u32 *out, hipStream_t st)
 {
-  if (count <= PAIR_WAVE_MAX && tuning("pair_wave_kernel", 1))
+  if (count <= PAIR_WAVE_MAX && tuning<tune::pair_wave_kernel>())
     hipLaunchKernelGGL((pair_sad_wave_kernel<SSD>), dim3((unsigned)((count + 3) / 4)), dim3(256), 0, st, p1, p2, pairs, count, out);
   else
     hipLaunchKernelGGL((pair_sad_kernel<SSD>), dim3(stream_grid(count, 32)), dim3(256), 0, st, p1, p2, pairs, count, out);
@@ -856,11 +856,11 @@ int kvz_hip_image_calc_satd_batch(const kvz_hip_pixel *pic, uint32_t pic_stride,
   if (!pic || !ref || !pairs || !costs || ref_w <= 0 || ref_h <= 0) return kvzhip::invalid_arg(__func__);
   if (count == 0) return KVZ_HIP_OK;
   plane_t p1 = { pic, pic_stride, 0, 0 }, p2 = { ref, ref_stride, ref_w, ref_h };
-  if (count <= PAIR_WAVE_MAX && tuning("pair_wave_kernel", 1))
+  if (count <= PAIR_WAVE_MAX && tuning<tune::pair_wave_kernel>())
     hipLaunchKernelGGL(pair_satd_wave_kernel, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, ctx_stream(s), p1, p2, pairs, count, costs);
   else
   {
-    int threads = tuning("pair_satd_threads", 256) & ~63;
+    int threads = tuning<tune::pair_satd_threads>() & ~63;
     threads = threads < 64 ? 64 : (threads > 512 ? 512 : threads);
     hipLaunchKernelGGL(pair_satd_kernel, dim3(stream_grid(count, 64)), dim3((unsigned)threads), 0, ctx_stream(s), p1, p2, pairs, count, costs);
   }

@@ -417,7 +417,7 @@ int kvz_hip_quant_batch(const kvz_hip_quant_params *p, const kvz_hip_coeff *coef
   if (count == 0) return KVZ_HIP_OK;
   hipStream_t st = ctx_stream(s);
   const size_t total = count * (size_t)(width * width);
-  hipLaunchKernelGGL(quant_kernel, dim3(stream_grid(total, 2048, (unsigned)tuning("quant_wgs_per_cu", 256))), dim3(256), 0, st, coef, q_coef, total, width * width, k);
+  hipLaunchKernelGGL(quant_kernel, dim3(stream_grid(total, 2048, (unsigned)tuning<tune::quant_wgs_per_cu>())), dim3(256), 0, st, coef, q_coef, total, width * width, k);
   KVZ_CHECK_LAUNCH("quant_kernel");
   if (k.signhide) {
     const size_t ncg = (size_t)(width / 4) * (width / 4), items = count * ncg;
@@ -443,7 +443,7 @@ int kvz_hip_dequant_batch(const kvz_hip_quant_params *p, const kvz_hip_coeff *q_
   if ((((uintptr_t)coef | (uintptr_t)q_coef) & 15) != 0) return kvzhip::invalid_arg(__func__);
   if (count == 0) return KVZ_HIP_OK;
   const size_t total = count * (size_t)(width * width);
-  hipLaunchKernelGGL(dequant_kernel, dim3(stream_grid(total, 2048, (unsigned)tuning("quant_wgs_per_cu", 256))), dim3(256), 0, ctx_stream(s), q_coef, coef, total, width * width, k);
+  hipLaunchKernelGGL(dequant_kernel, dim3(stream_grid(total, 2048, (unsigned)tuning<tune::quant_wgs_per_cu>())), dim3(256), 0, ctx_stream(s), q_coef, coef, total, width * width, k);
   KVZ_CHECK_LAUNCH("dequant_kernel");
   return KVZ_HIP_OK;
 }
@@ -473,22 +473,22 @@ static int quantize_residual_impl(const kvz_hip_quant_params *p, int cu_is_intra
   if (count == 0) return KVZ_HIP_OK;
   hipStream_t st = ctx_stream(s);
   const bool dst = (width == 4 && color == 0 && cu_is_intra);     // strategies-dct.c:66-85
-  if ((width == 32 || width == 16) && !use_trskip && !k.signhide && tuning("qr_tile_kernel", 1))
+  if ((width == 32 || width == 16) && !use_trskip && !k.signhide && tuning<tune::qr_tile_kernel>())
     return launch_quantize_residual_tile(width, ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, k.q_bits, k.add, k.flat_qc, k.qtable,
                                          k.dq_mode, k.dq_shift, k.dq_add, k.dq_scale, k.dqtable, ssd_out, abs_sum_out, st);
   // 8x8: sixteen TUs per matrix-core tile (quant_tile_mfma.hip); the cost variant and "qr8_tile_kernel" = 0 use the register kernel
-  if (width == 8 && !use_trskip && !k.signhide && !ssd_out && tuning("qr_tile_kernel", 1) && tuning("qr8_tile_kernel", 1))
+  if (width == 8 && !use_trskip && !k.signhide && !ssd_out && tuning<tune::qr_tile_kernel>() && tuning<tune::qr8_tile_kernel>())
     return launch_quantize_residual_tile(8, ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, k.q_bits, k.add, k.flat_qc, k.qtable,
                                          k.dq_mode, k.dq_shift, k.dq_add, k.dq_scale, k.dqtable, nullptr, nullptr, st);
-  if (width == 8 && !use_trskip && !k.signhide && !k.qtable && k.dq_mode == 0 && tuning("qr8_reg_kernel", 1))
+  if (width == 8 && !use_trskip && !k.signhide && !k.qtable && k.dq_mode == 0 && tuning<tune::qr8_reg_kernel>())
     return launch_quantize_residual8_reg(ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, k.q_bits, k.add, k.flat_qc,
                                          k.dq_shift, k.dq_add, k.dq_scale, ssd_out, abs_sum_out, st);
-  if (width == 4 && !k.signhide && tuning("qr4_lane_kernel", 1)) {
-    const unsigned grid = stream_grid(count, 256, (unsigned)tuning("qr4_wgs_per_cu", 96)       /* measured: 16: 4.8 TB/s, 64: 5.4, 128: 5.4 */);
+  if (width == 4 && !k.signhide && tuning<tune::qr4_lane_kernel>()) {
+    const unsigned grid = stream_grid(count, 256, (unsigned)tuning<tune::qr4_wgs_per_cu>()       /* measured: 16: 4.8 TB/s, 64: 5.4, 128: 5.4 */);
     const bool flat = !k.qtable && k.dq_mode == 0;
     // measured A/B on one box (0.5 GiB operands): with the in-wave prefetch 5.00-5.05 TB/s, without 5.15-5.21: at 8 waves per SIMD the
     // hardware's wave interleaving already hides the latency and the prefetch costs a wave of occupancy (72 against 60 VGPRs)
-    const bool pipe = tuning("pipe", 0) != 0;
+    const bool pipe = tuning<tune::pipe>() != 0;
 #define KVZ_QR4(T) do { if (flat && pipe) hipLaunchKernelGGL((quantize_residual4_lane_kernel<T, true, true>), dim3(grid), dim3(256), 0, st, ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, k, ssd_out, abs_sum_out); \
                         else if (flat) hipLaunchKernelGGL((quantize_residual4_lane_kernel<T, false, true>), dim3(grid), dim3(256), 0, st, ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, k, ssd_out, abs_sum_out); \
                         else hipLaunchKernelGGL((quantize_residual4_lane_kernel<T, false, false>), dim3(grid), dim3(256), 0, st, ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, k, ssd_out, abs_sum_out); } while (0)
@@ -497,7 +497,7 @@ static int quantize_residual_impl(const kvz_hip_quant_params *p, int cu_is_intra
     KVZ_CHECK_LAUNCH("quantize_residual4_lane_kernel");
     return KVZ_HIP_OK;
   }
-#define KVZ_QR(N, TRK) hipLaunchKernelGGL((quantize_residual_kernel<N, TRK>), dim3(stream_grid(count, 256 / N, (unsigned)tuning("qr_wgs_per_cu", N == 8 ? 64 : 16))), dim3(256), 0, st, \
+#define KVZ_QR(N, TRK) hipLaunchKernelGGL((quantize_residual_kernel<N, TRK>), dim3(stream_grid(count, 256 / N, (unsigned)tuning_or<tune::qr_wgs_per_cu>(N == 8 ? 64 : 16))), dim3(256), 0, st, \
                                           ref_in, pred_in, rec_out, coeff_out, has_coeffs, count, scan_order, k, ssd_out, abs_sum_out)
   switch (width) {
     case 4: if (use_trskip) KVZ_QR(4, 4); else if (dst) KVZ_QR(4, 2); else KVZ_QR(4, 0); break;

@@ -269,12 +269,12 @@ int launch_quantize_residual8_reg(const u8 *ref_in, const u8 *pred_in, u8 *rec_o
   const q8_consts k = { q_bits, add, flat_qc, dq_shift, dq_add, dq_scale };
   const size_t ngroups = (count + 7) / 8;
   size_t wgs = (ngroups + 3) / 4;                       // 4 waves per workgroup, one group of 8 TUs per wave step
-  const size_t cap = wg_cap(tuning("qr8_wgs_per_cu", 32));   // measured (0.5 GiB operands): 32: 4.95, 64: 4.84, 128: 4.79, 192: 4.67 TB/s
+  const size_t cap = wg_cap(tuning_or<tune::qr8_wgs_per_cu>(32));   // measured (0.5 GiB operands): 32: 4.95, 64: 4.84, 128: 4.79, 192: 4.67 TB/s
   if (wgs > cap) wgs = cap;
   // "pipe" 1: the iteration's wait on vector memory placed by hand before its first store (wait_vmem_all).  Measured A/B on one
   // box: 4.59 TB/s with it, 4.73 without -- at this kernel's 8 waves per SIMD the wave interleaving hides the latency by itself;
   // the matrix-core tile kernels (4 waves per SIMD) gain 10-15 % from the same placement.
-  if (!ssd_out && tuning("pipe", 0))
+  if (!ssd_out && tuning<tune::pipe>())
     hipLaunchKernelGGL((quantize_residual8_reg_kernel<false, true>), dim3((unsigned)wgs), dim3(256), 0, st, ref_in, pred_in, rec_out, coeff_out,
                        has_coeffs, count, k, ssd_out, abs_sum_out);
   else if (ssd_out)

@@ -429,12 +429,12 @@ int launch_tile(const u8 *ref_in, const u8 *pred_in, u8 *rec_out, i16 *coeff_out
   const size_t ntiles = (count + TUS - 1) / TUS;
   size_t wgs = (ntiles + 3) / 4;
   // workgroups per CU, measured at 0.5 GiB operands: 32x32 -- 8: 5.47, 16: 5.12, 32: 4.88, 64: 4.49 TB/s; 16x16 -- 8: 5.32, 16: 5.13, 32: 4.90, 64: 4.47
-  const size_t cap = wg_cap(tuning(N == 32 ? "qr32_wgs_per_cu" : (N == 16 ? "qr16_wgs_per_cu" : "qr8_wgs_per_cu"), 8));
+  const size_t cap = wg_cap(N == 32 ? tuning<tune::qr32_wgs_per_cu>() : N == 16 ? tuning<tune::qr16_wgs_per_cu>() : tuning_or<tune::qr8_wgs_per_cu>(8));
   if (wgs > cap) wgs = cap;
   if constexpr (N == 8) {
     hipLaunchKernelGGL((quantize_residual_tile_kernel<8, false>), dim3((unsigned)wgs), dim3(256), 0, st, ref_in, pred_in, rec_out, coeff_out,
                        has_coeffs, count, k, ssd_out, abs_sum_out);
-  } else if (!ssd_out && !tuning("qr_tile_pipe", 1)) {
+  } else if (!ssd_out && !tuning<tune::qr_tile_pipe>()) {
     hipLaunchKernelGGL((quantize_residual_tile_kernel<N, false, false>), dim3((unsigned)wgs), dim3(256), 0, st, ref_in, pred_in, rec_out, coeff_out,
                        has_coeffs, count, k, ssd_out, abs_sum_out);
   } else if (ssd_out)

@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void sao_reconstruct_kernel(const u8 *__restri
 // the packed-accumulator kernel: whole dwords per row, dword-aligned arrays, an interior to work on
 bool edge_fast_ok(const void *orig, const void *rec, int bw, int bh)
 {
-  return tuning("sao_edge_fast", 1) && (bw & 3) == 0 && bh >= 3 && (((uintptr_t)orig | (uintptr_t)rec) & 3) == 0;
+  return tuning<tune::sao_edge_fast>() && (bw & 3) == 0 && bh >= 3 && (((uintptr_t)orig | (uintptr_t)rec) & 3) == 0;
 }
 
 bool block_dims_ok(int bw, int bh)

@@ -60,6 +60,8 @@ constexpr int BATCH_CAP = 256;        // units per batch buffer (a larger batch 
 // 16 cores: 8.3 frames/s polling for 40 us, 9.7 for 10 us, 11.6-13.1 for 0-5 us with naps of 5-10 us; 48 threads: 8.6 -> 10.6-11.2.
 constexpr uint64_t SPIN_NS = 100 * 1000, SPIN_CROWDED_NS = 5 * 1000;
 constexpr long NAP_NS = 10 * 1000;
+static_assert(SPIN_CROWDED_NS == 1000ull * tune_default[(int)tune::service_spin_crowded_us] && NAP_NS == 1000L * tune_default[(int)tune::service_nap_us],
+              "the waits a service starts with are the knobs' defaults (tuning.h)");
 constexpr uint64_t WAIT_LIMIT_NS = 20ull * 1000 * 1000 * 1000;    // a request that is not answered in 20 s is a failure
 
 inline uint64_t now_ns()
@@ -348,8 +350,8 @@ kvz_hip_me_service *kvz_hip_me_service_create(const kvz_hip_me_service_config *c
   ok = ok && hipHostMalloc((void **)&svc->areas, sizeof(thread_area) * svc->max_threads, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess;
   ok = ok && hipHostMalloc((void **)&svc->ring, sizeof(serve_unit) * (size_t)svc->n_batch * BATCH_CAP, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess;
   if (ok) std::memset(svc->areas, 0, sizeof(thread_area) * svc->max_threads);
-  svc->n_streams = kvzhip::tuning("service_streams", 8);
-  svc->inflight_cap = kvzhip::tuning("service_inflight", 4);       // measured: 1080p full16 all served 2.41 -> 3.76 frames/s, medium 3.74 -> 4.31 (same box)
+  svc->n_streams = kvzhip::tuning<tune::service_streams>();
+  svc->inflight_cap = kvzhip::tuning<tune::service_inflight>();       // measured: 1080p full16 all served 2.41 -> 3.76 frames/s, medium 3.74 -> 4.31 (same box)
   if (svc->n_streams < 1) svc->n_streams = 1;
   if (svc->n_streams > N_STREAMS) svc->n_streams = N_STREAMS;
   for (int i = 0; i < svc->n_streams && ok; ++i) ok = hipStreamCreateWithFlags(&svc->streams[i], hipStreamNonBlocking) == hipSuccess;
@@ -357,13 +359,13 @@ kvz_hip_me_service *kvz_hip_me_service_create(const kvz_hip_me_service_config *c
   // Resident workers are the default way to the device (measured against a launch per batch on the same box, 1080p, 16 encoder
   // threads: exhaustive +-16 search 4.3 -> 6.8 frames/s, preset medium 5.8 -> 6.3, 16 closed-loop C threads 211k -> 317k requests/s);
   // "service_workers" 0 selects the launches, and so does a service with more calling threads than the ring is sized for.
-  svc->n_workers = kvzhip::tuning("service_workers", 64);
+  svc->n_workers = kvzhip::tuning<tune::service_workers>();
   svc->debug = getenv("KVZ_HIP_SERVICE_DEBUG") != nullptr;
-  svc->spin_crowded_ns = 1000ull * (uint64_t)kvzhip::tuning("service_spin_crowded_us", (int)(SPIN_CROWDED_NS / 1000));
-  svc->nap_ns = 1000L * kvzhip::tuning("service_nap_us", (int)(NAP_NS / 1000));
+  svc->spin_crowded_ns = 1000ull * (uint64_t)kvzhip::tuning<tune::service_spin_crowded_us>();
+  svc->nap_ns = 1000L * kvzhip::tuning<tune::service_nap_us>();
   if (svc->nap_ns < 1000) svc->nap_ns = 1000;
-  svc->spin_tuned = kvzhip::tuning("service_spin_us", -1) >= 0;
-  svc->spin_ns = 1000ull * (uint64_t)kvzhip::tuning("service_spin_us", (int)(SPIN_NS / 1000));
+  svc->spin_tuned = kvzhip::tuning_is_set(tune::service_spin_us);
+  svc->spin_ns = 1000ull * (uint64_t)kvzhip::tuning_or<tune::service_spin_us>((int)(SPIN_NS / 1000));
   {
     cpu_set_t set;
     CPU_ZERO(&set);
@@ -386,8 +388,8 @@ kvz_hip_me_service *kvz_hip_me_service_create(const kvz_hip_me_service_config *c
   if (svc->n_workers > 0 && ok) {
     // the wall clock counts 10 ns.  Idle workers cost a few atomics per microsecond; a relaunch costs the first request after a
     // pause ~15 us, so they stay through pauses of a couple of milliseconds (an encoder that serves only its largest PUs posts that rarely)
-    svc->linger_ticks = 100ull * (unsigned long long)kvzhip::tuning("service_linger_us", 2000);
-    svc->life_ticks = 100000ull * (unsigned long long)kvzhip::tuning("service_life_ms", 20);
+    svc->linger_ticks = 100ull * (unsigned long long)kvzhip::tuning<tune::service_linger_us>();
+    svc->life_ticks = 100000ull * (unsigned long long)kvzhip::tuning<tune::service_life_ms>();
     ok = ok && hipHostMalloc((void **)&svc->wring, sizeof(serve_slot) * WRING_SLOTS, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) == hipSuccess;
     ok = ok && hipHostMalloc((void **)&svc->ctl, sizeof(serve_ring_ctl), hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent) == hipSuccess;
     ok = ok && hipMalloc((void **)&svc->wdev, sizeof(serve_ring_dev)) == hipSuccess;
@@ -395,7 +397,7 @@ kvz_hip_me_service *kvz_hip_me_service_create(const kvz_hip_me_service_config *c
     if (ok) { std::memset(svc->wring, 0, sizeof(serve_slot) * WRING_SLOTS); std::memset(svc->ctl, 0, sizeof(serve_ring_ctl)); }
     // tickets normally start at 0; "service_ticket_base_k" (x 1024) starts them elsewhere, so that a test can walk the counters across
     // 2^32 in seconds instead of an hour of full load
-    const unsigned long long base = 1024ull * (unsigned long long)kvzhip::tuning("service_ticket_base_k", 0);
+    const unsigned long long base = 1024ull * (unsigned long long)kvzhip::tuning<tune::service_ticket_base_k>();
     if (ok && base) {
       serve_ring_dev d0;
       std::memset(&d0, 0, sizeof(d0));
@@ -406,7 +408,7 @@ kvz_hip_me_service *kvz_hip_me_service_create(const kvz_hip_me_service_config *c
     }
     // push mode when the host can write device memory (large BAR); tuning "service_push" 0 keeps the workers reading host memory
     int large_bar = 0;
-    if (ok && kvzhip::tuning("service_push", 1) != 0 && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, svc->device) == hipSuccess && large_bar) {
+    if (ok && kvzhip::tuning<tune::service_push>() != 0 && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, svc->device) == hipSuccess && large_bar) {
       bool got = hipExtMallocWithFlags((void **)&svc->dring, sizeof(serve_slot) * WRING_SLOTS, hipDeviceMallocFinegrained) == hipSuccess &&
                  hipExtMallocWithFlags((void **)&svc->dpush, sizeof(serve_push), hipDeviceMallocFinegrained) == hipSuccess &&
                  hipMemset(svc->dring, 0, sizeof(serve_slot) * WRING_SLOTS) == hipSuccess && hipMemset(svc->dpush, 0, sizeof(serve_push)) == hipSuccess &&

@@ -247,7 +247,7 @@ int kvzhip::serve_workers_launch(const u8 *planes, size_t plane_bytes, int n_slo
                                  unsigned long long linger_ticks, unsigned long long life_ticks, unsigned long long poll_period, hipStream_t st)
 {
   if (count <= 0) return KVZ_HIP_OK;
-  if (kvzhip::tuning("full_qsad", 1))
+  if (kvzhip::tuning<tune::full_qsad>())
     hipLaunchKernelGGL((serve_worker_kernel<true>), dim3((unsigned)count), dim3(512), 0, st, planes, plane_bytes, n_slots, stride, w, h, ring, host_ring, push, ring_mask, ctl, dev, ids, linger_ticks, life_ticks, poll_period);
   else
     hipLaunchKernelGGL((serve_worker_kernel<false>), dim3((unsigned)count), dim3(512), 0, st, planes, plane_bytes, n_slots, stride, w, h, ring, host_ring, push, ring_mask, ctl, dev, ids, linger_ticks, life_ticks, poll_period);
@@ -260,7 +260,7 @@ int kvzhip::serve_launch(bool constrained, const u8 *planes, size_t plane_bytes,
                          const serve_unit *units, int count, hipStream_t st)
 {
   if (count <= 0) return KVZ_HIP_OK;
-  const bool qsad = kvzhip::tuning("full_qsad", 1) != 0;
+  const bool qsad = kvzhip::tuning<tune::full_qsad>() != 0;
   if (constrained && qsad) hipLaunchKernelGGL((serve_kernel<true, true>), dim3((unsigned)count), dim3(512), 0, st, planes, plane_bytes, n_slots, stride, w, h, units, count);
   else if (constrained) hipLaunchKernelGGL((serve_kernel<true, false>), dim3((unsigned)count), dim3(512), 0, st, planes, plane_bytes, n_slots, stride, w, h, units, count);
   else if (qsad) hipLaunchKernelGGL((serve_kernel<false, true>), dim3((unsigned)count), dim3(512), 0, st, planes, plane_bytes, n_slots, stride, w, h, units, count);

@@ -7,6 +7,16 @@ def rng(seed):
     return np.random.default_rng(seed)
 
 
+def tuning_table():
+    """[(key, default)] of the tuning knobs in table order, read from the rows of KVZ_TUNE_KEYS in kvazaar_amd/csrc/tuning.h;
+    default is None where the table says TUNE_PER_SITE"""
+    import os
+    import re
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "kvazaar_amd", "csrc", "tuning.h")
+    rows = re.findall(r'^\s*X\((\w+),\s*(\w+),\s*"', open(path).read(), re.M)
+    return [(key, None if dflt == "TUNE_PER_SITE" else int(dflt)) for key, dflt in rows]
+
+
 def lcg_bytes(n, seed=12345):
     """x = 1664525*x + 1013904223 (mod 2^32), byte = bits 8..15"""
     out = np.empty(n, dtype=np.uint8)

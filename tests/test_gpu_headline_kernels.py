@@ -31,18 +31,8 @@ def env():
 @pytest.fixture
 def knobs(env):
     """knobs(key=value, ...) sets tuning knobs; every knob set is back at its default after the test"""
-    _, _lib, L = env
-    touched = set()
-
-    def set_(**kv):
-        for k, v in kv.items():
-            touched.add(k)
-            _lib.check(L.kvz_hip_set_tuning(k.encode(), int(v)), "tuning %s" % k)
-    try:
+    with env[0].tuned() as set_:
         yield set_
-    finally:
-        for k in touched:
-            L.kvz_hip_set_tuning(k.encode(), -1)
 
 
 def block_pairs(n, count, seed):

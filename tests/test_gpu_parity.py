@@ -494,6 +494,21 @@ def test_transform_16x16_tile_tails(api):
     assert L.kvz_hip_set_tuning(b"no_such_key", 1) != 0
 
 
+def test_set_tuning_takes_every_key_of_the_table():
+    """every row of kvazaar_amd/csrc/tuning.h is a key that can be set (here to -1, the default); a string that is no key and NULL
+    are refused"""
+    from kvazaar_amd import _lib
+    from patterns import tuning_table
+    L = _lib.load()
+    table = tuning_table()
+    assert len(table) == 43
+    for key, _ in table:
+        assert L.kvz_hip_set_tuning(key.encode(), -1) == _lib.OK, key
+    assert L.kvz_hip_set_tuning(b"no_such_key", -1) != 0
+    assert L.kvz_hip_set_tuning(None, -1) != 0
+    assert b"kvz_hip_set_tuning: invalid argument" in L.kvz_hip_last_error()
+
+
 # ---- intra group (SURVEY 8(f) row 2) ----
 from patterns import intra_ref_cases  # noqa: E402
 

@@ -39,19 +39,6 @@ def _lib0():
     return _lib.init(0)
 
 
-class tuned:
-    """a tuning knob for the length of a with-block"""
-
-    def __init__(self, name, value):
-        self.name, self.value = name, value
-
-    def __enter__(self):
-        assert _lib0().kvz_hip_set_tuning(self.name, self.value) == 0
-
-    def __exit__(self, *exc):
-        _lib0().kvz_hip_set_tuning(self.name, -1)
-
-
 def embed_call(layout, planes, seed, offsets=None):
     """The compact `planes` of ONE call on `layout`: plane k gets the k-th stride of the layout (so they all differ and grow with
     k) and a buffer long enough for the largest of them.  offsets: per plane, rows added to the layout's `top`.
@@ -125,7 +112,7 @@ def test_pair_entry(api, entry, layout):
     p, r = (view(api, e) for e in embed_call(layout, [pic, ref], 10))
     f = getattr(api, entry + "_batch")
     for knob in (1, 0):
-        with tuned(b"pair_wave_kernel", knob):
+        with api.tuned(pair_wave_kernel=knob):
             np.testing.assert_array_equal(f(p, r, pairs), want, err_msg="%s layout %s pair_wave_kernel %d" % (entry, layout, knob))
     np.testing.assert_array_equal(f(p, r, small), want_small, err_msg="%s layout %s, 4097 8x8 pairs" % (entry, layout))
 
@@ -189,10 +176,10 @@ def test_ctu_sad_grid(api, layout):
 # ------------------------------------------------------------------ search_pu
 ME_SIZES = ((8, 8), (16, 16), (32, 32), (64, 64), (16, 8), (8, 16), (32, 16), (64, 32), (24, 32), (32, 8),     # 2Nx2N, SMP
             (8, 4), (4, 8), (16, 4), (4, 16), (16, 12), (12, 16), (32, 24), (64, 16))                           # AMP
-# one run per kernel family: (name, me_params arguments, tuning knob or None)
+# one run per kernel family: (name, me_params arguments, tuning knobs or None)
 ME_RUNS = (("hexbs", dict(fme_level=4), None), ("dia", dict(algorithm=1), None), ("tz", dict(algorithm=2), None),
-           ("full, full_qsad 0", dict(algorithm=3, search_range=8), (b"full_qsad", 0)),
-           ("full, full_qsad 1", dict(algorithm=3, search_range=8), (b"full_qsad", 1)),
+           ("full, full_qsad 0", dict(algorithm=3, search_range=8), dict(full_qsad=0)),
+           ("full, full_qsad 1", dict(algorithm=3, search_range=8), dict(full_qsad=1)),
            ("mv_rdo", dict(mv_rdo=1, refs_before=3, ref_idx=2, lambda_cost=11), None),
            ("tile", dict(mv_constraint=4, tile=(0, 64, 192, 64), lambda_cost=11), None))
 
@@ -234,10 +221,7 @@ def test_search_pu(api, layout):
     pic, ref, runs = me_case()
     p, r = (view(api, e) for e in embed_call(layout, [pic, ref], 40))
     for name, prm, knob, pus, cabac, want in runs:
-        if knob:
-            with tuned(*knob):
-                got = api.search_pu_batch(p, r, pus, prm, cabac=cabac)
-        else:
+        with api.tuned(**(knob or {})):
             got = api.search_pu_batch(p, r, pus, prm, cabac=cabac)
         assert_me_equal(got, want, "layout %s, %s" % (layout, name))
 

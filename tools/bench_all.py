@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
-from kvazaar_amd import _lib  # noqa: E402
+from kvazaar_amd import _lib, api  # noqa: E402
 from kvazaar_amd._lib import QuantParams  # noqa: E402
 
 
@@ -214,7 +214,7 @@ def main():
     cases.append(("intra_build_reference_8x8(PUs)", 32400, 130 + 33,
                   lambda: L.kvz_hip_intra_build_reference_batch(3, 0, rec_d.data_ptr(), 1920, 1920, 1080, pos_d.data_ptr(), 32400, refs8_d.data_ptr(), st)))
 
-    tune_key, tune_vals = None, [None]
+    tune_key, tune_vals = "", [None]
     if args.tune:
         tune_key, vals = args.tune.split("=")
         tune_vals = [int(v) for v in vals.split(",")]
@@ -226,15 +226,12 @@ def main():
         best = {}
         for _ in range(args.rounds):
             for v in tune_vals:
-                if tune_key:
-                    _lib.check(L.kvz_hip_set_tuning(tune_key.encode(), v), "set_tuning")
-                ms = timed(L, st, lambda: _lib.check(fn(), name))
+                with api.tuned(**({tune_key: v} if tune_key else {})):
+                    ms = timed(L, st, lambda: _lib.check(fn(), name))
                 best[v] = min(best.get(v, 1e9), ms)
         for v in tune_vals:
             ms = best[v]
             print("%-26s %10s %12.1f %10.1f %8.4f" % (name, "-" if v is None else v, blocks / ms / 1e3, blocks * bpb / ms / 1e6, ms))
-    if tune_key:
-        L.kvz_hip_set_tuning(tune_key.encode(), -1)
     if not args.only or any(o in "inter_recon_frame_p inter_recon_frame_b" for o in args.only.split(",")):
         inter_recon_rows(L, st, dev, max(args.rounds, 5))
     if not args.only or any(o in "inter_residual_frame_1080p inter_residual_frame_4k inter_residual_frame_1080p_lcu_qp inter_residual_frame_1080p_ts inter_residual_frame_1080p_lossless" for o in args.only.split(",")):

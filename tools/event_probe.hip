@@ -22,7 +22,6 @@ void set_error(const char *, hipError_t) {}
 void set_error_msg(const char *) {}
 int invalid_arg(const char *) { return -1; }
 int num_cus() { return 256; }
-int tuning(const char *, int d) { return d; }
 int stream_on_current_device(kvz_hip_stream, const char *) { return 0; }
 hipEvent_t launch_carrier(hipStream_t) { return nullptr; }      // picture.hip's own entries launch plainly here; the probe binds its events itself
 void launch_uncarry(hipStream_t) {}
