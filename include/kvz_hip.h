@@ -1007,7 +1007,8 @@ typedef struct {
  *   transform skip, RDOQ, scaling lists (params->scaling_list != 0 returns KVZ_HIP_ERR_INVALID; kvz_hip_inter_residual_frame_sl
  *   below takes them) and per-CU QP (the qp field of the records is not read; a QP per LCU: kvz_hip_inter_residual_frame_qp below).  Intra CUs need their neighbours' reconstruction and are not handled, as in
  *   kvz_hip_inter_recon_frame: kvz_hip_intra_recon_frame (below) does them next.  RDOQ is built since as a batch entry of its own,
- *   kvz_hip_rdoq_batch (further below); this stage does not call it.
+ *   kvz_hip_rdoq_batch (further below); this stage does not call it.  Since then kvz_hip_inter_residual_frame_rdoq
+ *   (further below) is this stage with kvz_rdoq as its quantiser.
  * Outputs:
  *   rec planes: the reconstruction inside the inter CUs (a TU without coefficients keeps its prediction).
  *   coeff_y / coeff_u / coeff_v: DEVICE, 16-byte aligned, the layout of lcu->coeff: per LCU, in raster order of the
@@ -1347,7 +1348,8 @@ KVZ_HIP_API int kvz_hip_scaling_tables_pack(const int32_t *const quant_coeff[4][
  * OUT OF SCOPE: RDOQ and its error_scale, transform skip, parsing --cqmfile, signalling the lists.  Lossless coding has entries of
  * its own, kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below): nothing is quantised there.
  * RDOQ with its error_scale is built since as a batch entry of its own, kvz_hip_rdoq_batch with kvz_hip_rdoq_tables_pack (further
- * below); these two stages still quantise with the rdoq-off path. */
+ * below); these two stages still quantise with the rdoq-off path.  Since then kvz_hip_inter_residual_frame_rdoq and
+ * kvz_hip_intra_recon_frame_rdoq (further below) are the two _sl entries with kvz_rdoq as their quantiser. */
 KVZ_HIP_API int kvz_hip_inter_residual_frame_sl(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
                                                 kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus,
                                                 kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v,
@@ -1407,7 +1409,7 @@ typedef struct {
  *   with that rule, and kvz_hip_coeff_cost_batch is the count for any TU of the coefficient arrays they write.  OUT OF SCOPE: RDOQ
  *   and the transform-skip term of the intra rough search (search_intra.c:105-167).  Lossless coding switches transform skip off (encoder.c:623-628) and has entries of its own:
  *   kvz_hip_inter_residual_frame_lossless and kvz_hip_intra_recon_frame_lossless (below).  RDOQ is built since as a batch entry of its
- *   own, kvz_hip_rdoq_batch (further below); these stages do not call it.
+ *   own, kvz_hip_rdoq_batch (further below); these stages do not call it.  The _rdoq entries further below do, without transform skip.
  * Errors: ts != NULL with tr_skip_out == NULL, with bit_cost < 0 while lcu_bit_cost == NULL, or with lcu_bit_cost not 4-byte
  *   aligned returns KVZ_HIP_ERR_INVALID and nothing is written; so does every error of the _sl entry.
  * Launches and capture: asynchronous, no allocation, no synchronisation with the host, usable between kvz_hip_graph_begin / _end.
@@ -1526,7 +1528,8 @@ typedef struct {
  *   not 2-byte aligned, with n_sets == 0, or with a misaligned lcu_ctx.
  * The multi-picture _frames_ts entries take no pricing yet.  OUT OF SCOPE: RDOQ, the transform-tree flag bits of the rd cost and
  *   the transform-skip term of the intra rough search.  The ABI version stays 4.  RDOQ is built since as a batch entry of its own,
- *   kvz_hip_rdoq_batch (further below); these stages do not call it. */
+ *   kvz_hip_rdoq_batch (further below); these stages do not call it.  The _rdoq entries further below do, without
+ *   transform skip. */
 KVZ_HIP_API int kvz_hip_inter_residual_frame_ts_cabac(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y,
                                                       kvz_hip_pixel *rec_u, kvz_hip_pixel *rec_v, uint32_t stride_c,
                                                       kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u,
@@ -1700,6 +1703,65 @@ typedef struct {
 KVZ_HIP_API int kvz_hip_rdoq_batch(const kvz_hip_coeff *coef, kvz_hip_coeff *dest, const kvz_hip_rdoq_desc *descs, size_t n,
                                    const kvz_hip_coeff_ctx *ctx_sets, const kvz_hip_rdoq_state *states, uint32_t n_sets,
                                    const kvz_hip_rdoq_tables *tables, const kvz_hip_rdoq_params *params, kvz_hip_stream s);
+
+/* ---- RDOQ inside the two single-picture residual stages of the picture chain ----
+ * kvz_quantize_residual calls kvz_rdoq instead of kvz_quant where cfg.rdoq_enable && (width > 4 || !cfg.rdoq_skip)
+ * (quant-generic.c:214-221): every TU at preset medium and slower.  What the two entries below read for that, beside the arguments of
+ * the _sl entries.  Offsets in front of the fields.
+ * ctx_sets / states: the context sets and, index-parallel to them, the states (lambda and the nine cbf context bytes).  states[].qp is
+ *   NOT read by these entries: a TU is handed the QP of its LCU, exactly the value the _sl entry quantises that TU with.
+ * lcu_ctx: one set index per LCU in raster order, or NULL: set 0 everywhere.  An index >= n_sets is used as n_sets - 1, the rule of
+ *   kvz_hip_coeff_pricing.
+ * tables: quant and err_scale as kvz_hip_rdoq_tables_pack lays them out; RDOQ reads both for flat lists too, so they are always
+ *   required.  rdoq_skip: cfg.rdoq_skip -- the 4x4 TUs keep the plain quantiser. */
+typedef struct {
+  const kvz_hip_coeff_ctx  *ctx_sets;   /*  0: DEVICE, n_sets records, 2-byte aligned */
+  const kvz_hip_rdoq_state *states;     /*  8: DEVICE, n_sets records, 8-byte aligned, index-parallel to ctx_sets */
+  const uint16_t           *lcu_ctx;    /* 16: DEVICE, optional: one set index per LCU, raster order; NULL = set 0 */
+  kvz_hip_rdoq_tables       tables;     /* 24: quant + err_scale, DEVICE, as kvz_hip_rdoq_tables_pack lays them out; always required */
+  uint32_t                  n_sets;     /* 40: the records in ctx_sets and in states */
+  int32_t                   rdoq_skip;  /* 44: cfg.rdoq_skip: 4x4 TUs keep the plain quantiser */
+} kvz_hip_rdoq_source;          /* 48 bytes; HOST struct, copied at the call */
+
+/* kvz_hip_inter_residual_frame_sl and kvz_hip_intra_recon_frame_sl with `rdoq` placed before params.
+ * rdoq == NULL: the call is the _sl entry, byte for byte; it calls that entry, which then names itself in kvz_hip_last_error.
+ * Otherwise everything of the _sl contract holds -- lcu_qp, the optional tables, tiles in the intra entry, which CUs are owned, the
+ *   transform tree, the LCU coefficient layout, cbf_y, cbf_out, costs, and nothing outside the owned records is touched -- and only the
+ *   quantiser of a TU changes: where width > 4 || !rdoq_skip its levels are what kvz_rdoq leaves, as kvz_hip_rdoq_batch defines them;
+ *   every other TU takes the _sl quantiser with its own sign hiding.
+ * What kvz_rdoq is handed: type 0 for Y and 2 for U and V; scan_mode the TU's scan order (diagonal in the inter entry,
+ *   kvz_get_scan_order of the intra mode in the intra entry); block_type from the CU (CU_INTER / CU_INTRA); qp the QP of the TU's LCU;
+ *   lambda, the nine cbf context bytes and the contexts from states[set] and ctx_sets[set] with set = lcu_ctx[lcu]; signhide from
+ *   params; the quant and error-scale tables from rdoq->tables.  The optional `tables` argument keeps its _sl meaning: it serves
+ *   dequantisation and the plain quantiser of the skipped 4x4 TUs.
+ * tr_depth: tr_depth - depth + (part_size == SIZE_NxN ? 1 : 0) of the record at the TU's own top-left SCU (the cur_pu of
+ *   transform.c:437; quant-generic.c:218-219), clamped into 0..3 so that no map can index outside qt_cbf_model_chroma[4]; a reference
+ *   encode never leaves that range.
+ * After the levels, as quant-generic.c:227-270: has_coeffs is set when any level is non-zero; dequantisation, inverse transform,
+ *   reconstruction and clipping run only then, otherwise the prediction stands; ssd_*, zero_ssd_* and coeff_abs_* keep their
+ *   definitions, taken over the RDOQ levels.
+ * Errors beyond the _sl entry's (KVZ_HIP_ERR_INVALID, nothing written): ctx_sets, states, tables.quant or tables.err_scale NULL;
+ *   n_sets == 0; ctx_sets or lcu_ctx not 2-byte aligned; states or err_scale not 8-byte aligned; quant not 16-byte aligned.
+ * Any lambda, context byte or table value is memory-safe, as in the batch entry; the result is specified for finite lambda > 0 only.
+ * Launches: asynchronous on s, no allocation, no workspace, no host synchronisation.  The inter entry: the init launch of the _sl
+ *   entry (with cbf_out or costs) and four launches, one per TU width, a wave per TU (with rdoq_skip the 4x4 launch is the _sl
+ *   entry's).  The intra entry: the launches of the _sl entry, one per step of the wavefront, a wave per LCU and plane; the serial
+ *   recursion of kvz_rdoq runs on one lane inside every step.  Launch shapes depend on the sizes only, and in the intra entry on the
+ *   grid.  Usable between kvz_hip_graph_begin / _end; a captured call may be replayed after the CONTENTS of every array changed.
+ *   The ABI version stays 4.
+ * OUT OF SCOPE: transform skip together with RDOQ (these entries take no kvz_hip_trskip), the multi-picture _frames / _frames_ts
+ *   entries, the drop-in's quantize_residual, lossless, bit depths above 8, a recursion on more than one lane. */
+KVZ_HIP_API int kvz_hip_inter_residual_frame_rdoq(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                                                  kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y,
+                                                  kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out,
+                                                  kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp, const kvz_hip_scaling_tables *tables,
+                                                  const kvz_hip_rdoq_source *rdoq, const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frame_rdoq(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
+                                               kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, const uint8_t *intra_modes,
+                                               kvz_hip_coeff *coeff_y, kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out,
+                                               kvz_hip_inter_residual_cost *costs, const int8_t *lcu_qp, const kvz_hip_tile_grid *grid,
+                                               const kvz_hip_scaling_tables *tables, const kvz_hip_rdoq_source *rdoq,
+                                               const kvz_hip_inter_residual_params *params, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* Several independent pictures through the residual stages at once    */

@@ -178,6 +178,12 @@ class RdoqTables(C.Structure):
     _fields_ = [("quant", C.c_void_p), ("err_scale", C.c_void_p)]
 
 
+class RdoqSource(C.Structure):
+    """kvz_hip_rdoq_source"""
+    _fields_ = [("ctx_sets", C.c_void_p), ("states", C.c_void_p), ("lcu_ctx", C.c_void_p), ("tables", RdoqTables), ("n_sets", C.c_uint32),
+                ("rdoq_skip", C.c_int32)]
+
+
 class RdoqParams(C.Structure):
     """kvz_hip_rdoq_params"""
     _fields_ = [("signhide", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -293,6 +299,9 @@ SIGNATURES = {
                                                    C.POINTER(CoeffPricing), _P, _P]),
     "kvz_hip_intra_recon_frame_ts_cabac": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(TrSkip),
                                                 _P, C.POINTER(CoeffPricing), _P, _P]),
+    "kvz_hip_inter_residual_frame_rdoq": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(RdoqSource), _P, _P]),
+    "kvz_hip_intra_recon_frame_rdoq": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(ScalingTables), C.POINTER(RdoqSource),
+                                            _P, _P]),
     "kvz_hip_inter_residual_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_intra_recon_frame_lossless": (_I, [_P, _P, _U, _P, _P, _U, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(Lossless), _P]),
     "kvz_hip_inter_residual_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),

@@ -810,7 +810,7 @@ TRSKIP = np.dtype([("bit_cost", "<i4"), ("reserved", "<i4"), ("lcu_bit_cost", "<
 
 
 def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhide=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                         trskip=None, tr_skip=None, pricing=None, scaling=None):
+                         trskip=None, tr_skip=None, pricing=None, rdoq=None, scaling=None):
     """kvz_hip_inter_residual_frame.  src: (y, u, v) uint8 planes of the source picture (its luma shape is the picture size;
     u, v None for 4:0:0); pred: (y, u, v) planes holding the prediction, at least as large (a wider array gives a stride);
     cus: kvz_hip_cu_info records [height / 4, width / 4]; coeff / cbf_out / costs: optional initial contents of the outputs
@@ -823,25 +823,30 @@ def inter_residual_frame(src, pred, cus, qp, chroma=1, slice_is_intra=0, signhid
     tr_skip: optional initial contents of that array (default zeros).
     pricing (with trskip): dict(sets=COEFF_CTX [m], fast_limit=int, lcu_ctx=uint16 [LCUs] or None) -> kvz_hip_inter_residual_frame_ts_cabac:
     a trial is priced with CABAC on its LCU's set where the LCU's QP is at or above fast_limit.  An empty dict: that entry with
-    pricing == NULL."""
+    pricing == NULL.
+    rdoq (without trskip): dict(sets=COEFF_CTX [m], states=RDOQ_STATE [m], tables=(quant int32, err_scale float64) as pack_rdoq_tables
+    makes them, lcu_ctx=uint16 [LCUs] or None, skip=0 | 1) -> kvz_hip_inter_residual_frame_rdoq (with or without lcu_qp and scaling):
+    the TUs wider than 4, and the 4x4 TUs unless skip, take their levels from kvz_rdoq on the set of their LCU.  An empty dict: that
+    entry with rdoq == NULL.  Together with trskip: ValueError."""
     return _residual_frame(None, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, scaling=scaling,
-                           trskip=trskip, tr_skip=tr_skip, pricing=pricing)
+                           trskip=trskip, tr_skip=tr_skip, pricing=pricing, rdoq=rdoq)
 
 
 def intra_recon_frame(src, rec, cus, modes, qp, chroma=1, signhide=0, slice_is_intra=0, coeff=None, cbf_out=None, costs=None, lcu_qp=None,
-                      tiles=None, trskip=None, tr_skip=None, pricing=None, scaling=None):
+                      tiles=None, trskip=None, tr_skip=None, pricing=None, rdoq=None, scaling=None):
     """kvz_hip_intra_recon_frame.  As inter_residual_frame; rec: (y, u, v) planes as the inter stages left them (the pixels of the
     intra CUs are not read); modes: uint8 [height / 4, width / 4, 2] = intra.mode, intra.mode_chroma per SCU.  Returns the same
     dict.  lcu_qp: int8 [LCUs] in raster order -> kvz_hip_intra_recon_frame_qp.  tiles: a TILE_GRID record ->
     kvz_hip_intra_recon_frame_tiles (with or without lcu_qp).  scaling: the pair of packed arrays of pack_scaling_tables ->
     kvz_hip_intra_recon_frame_sl (with or without lcu_qp and tiles).  trskip, tr_skip: as in inter_residual_frame ->
     kvz_hip_intra_recon_frame_ts (with or without lcu_qp, tiles and scaling).  pricing: as in inter_residual_frame ->
-    kvz_hip_intra_recon_frame_ts_cabac."""
+    kvz_hip_intra_recon_frame_ts_cabac.  rdoq: as in inter_residual_frame -> kvz_hip_intra_recon_frame_rdoq (with or without lcu_qp,
+    tiles and scaling)."""
     cus = np.ascontiguousarray(cus)
     modes = np.ascontiguousarray(modes, dtype=np.uint8)
     assert modes.shape == cus.shape + (2,)
     return _residual_frame(modes, src, rec, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp, tiles, scaling, trskip, tr_skip,
-                           pricing)
+                           pricing, rdoq)
 
 
 class _StagedPicture:
@@ -892,9 +897,11 @@ class _StagedPicture:
 
 
 def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide, coeff, cbf_out, costs, lcu_qp=None, tiles=None, scaling=None,
-                    trskip=None, tr_skip=None, pricing=None):
+                    trskip=None, tr_skip=None, pricing=None, rdoq=None):
     """the staging both residual stages share; modes None: the inter stage; lcu_qp given: the _qp entries; tiles given (intra only): the
     _tiles entry; scaling given: the _sl entries, the packed arrays uploaded for the call; trskip given: the _ts entries"""
+    if rdoq is not None and trskip is not None:
+        raise ValueError("rdoq together with trskip: the _rdoq entries take no kvz_hip_trskip")
     L = _lib.init()
     st = _StagedPicture(modes, src, pred, cus, chroma, coeff, cbf_out, costs)
     width, height, cus = st.width, st.height, st.cus
@@ -951,6 +958,30 @@ def _residual_frame(modes, src, pred, cus, qp, chroma, slice_is_intra, signhide,
             check(L.kvz_hip_intra_recon_frame_ts(*planes, dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None,
                                                  C.byref(sl) if sl is not None else None, C.byref(ts), dts.ptr, prm.ctypes.data, None),
                   "intra_recon frame_ts")
+    elif rdoq is not None:
+        # the _rdoq entries: the sets, the states, the two tables and the optional index per LCU uploaded for the call
+        rq_ref = None                                            # an empty dict: the entries with rdoq == NULL
+        if rdoq:
+            sets = np.ascontiguousarray(rdoq["sets"], dtype=COEFF_CTX).ravel()
+            states = np.ascontiguousarray(rdoq["states"], dtype=RDOQ_STATE).ravel()
+            assert len(sets) == len(states)
+            rq_q = np.ascontiguousarray(rdoq["tables"][0], dtype=np.int32).reshape(SL_TABLE_LEN)
+            rq_e = np.ascontiguousarray(rdoq["tables"][1], dtype=np.float64).reshape(SL_TABLE_LEN)
+            d_sets, d_states, d_rq, d_re = (DeviceBuffer.from_numpy(a) for a in (sets, states, rq_q, rq_e))
+            d_lc = None
+            if rdoq.get("lcu_ctx") is not None:
+                d_lc = DeviceBuffer.from_numpy(np.ascontiguousarray(rdoq["lcu_ctx"], dtype=np.uint16).reshape(lcu_count(width, height)))
+            rq = _lib.RdoqSource(d_sets.ptr, d_states.ptr, d_lc.ptr if d_lc is not None else None, _lib.RdoqTables(d_rq.ptr, d_re.ptr), len(sets),
+                                 int(rdoq.get("skip", 0)))
+            rq_ref = C.byref(rq)
+        if modes is None:
+            assert tiles is None
+            check(L.kvz_hip_inter_residual_frame_rdoq(*planes, *outs, dqp, C.byref(sl) if sl is not None else None, rq_ref, prm.ctypes.data, None),
+                  "inter_residual frame_rdoq")
+        else:
+            g = _grid(tiles) if tiles is not None else None
+            check(L.kvz_hip_intra_recon_frame_rdoq(*planes, st.dm.ptr, *outs, dqp, g.ctypes.data if g is not None else None,
+                                                   C.byref(sl) if sl is not None else None, rq_ref, prm.ctypes.data, None), "intra_recon frame_rdoq")
     elif modes is None:
         assert tiles is None
         if sl is not None:

@@ -162,6 +162,18 @@ inline bool chain_trskip_ok(const kvz_hip_trskip *ts, const uint8_t *tr_skip_out
 {
   return tr_skip_out && (ts->lcu_bit_cost || ts->bit_cost >= 0) && !((uintptr_t)ts->lcu_bit_cost & 3);
 }
+// RDOQ, rdoq != NULL (kvz_hip_inter_residual_frame_rdoq, kvz_hip_intra_recon_frame_rdoq): why the record is refused, or nullptr.  The
+// order of the checks is part of the interface (tests/test_rdoq_chain_host_checks.py pins it)
+inline const char *chain_rdoq_why(const kvz_hip_rdoq_source *r)
+{
+  if (!r->ctx_sets || !r->states) return "ctx_sets or states is null";
+  if (!r->tables.quant || !r->tables.err_scale) return "a table is null";
+  if (r->n_sets == 0) return "n_sets is 0";
+  if (((uintptr_t)r->ctx_sets & 1) || ((uintptr_t)r->lcu_ctx & 1)) return "ctx_sets or lcu_ctx not 2-byte aligned";
+  if (((uintptr_t)r->states & 7) || ((uintptr_t)r->tables.err_scale & 7)) return "states or err_scale not 8-byte aligned";
+  if ((uintptr_t)r->tables.quant & 15) return "quant not 16-byte aligned";
+  return nullptr;
+}
 // one QP for the picture (no lcu_qp): what the one-QP entry refuses.  That entry asks make_consts (quant_core.h) for the constants of
 // the 4x4 luma and chroma TUs, which fails where scaled_qp is negative: for luma that is the QP itself, for chroma it is clamped into
 // 0..57 (tests/test_chain_host_checks.py holds this rule against what make_consts decided for every QP)

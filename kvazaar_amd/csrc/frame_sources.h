@@ -1,6 +1,7 @@
 // frame_sources.h -- what the two residual stages of the picture chain (intra_recon_core.h, inter_residual_core.h) share about
 // their options.  A kernel of either stage takes its optional sources as a trailing pack in a fixed order: lcu_qp_source, then the
-// stage's own tile_source / sl_source / ts_source (they differ between the stages and live in the cores), then cabac_source.  The
+// stage's own tile_source / sl_source / ts_source (they differ between the stages and live in the cores), then cabac_source; or,
+// behind sl_source and without transform skip, rdoq_source.  The
 // pack's type selects the instantiation; inside the kernel a source is found by its type (source_of), whatever else the pack holds.
 // Also here: the body of the stages' init kernels.  Everything has internal linkage, as in the cores.
 #pragma once
@@ -36,6 +37,22 @@ inline lcu_qp_source qp_source_of(const kvz_hip_chain_picture &p) { return { p.l
 struct cabac_source { const kvz_hip_coeff_ctx *sets; const uint16_t *lcu_ctx; u32 n_sets; int fast_limit; };
 // a trial's levels in LDS rows of ld, as coeff_cabac_count reads them
 struct cabac_lds_coeffs { const i16 *p; int ld; __device__ __forceinline__ int at(int x, int y) const { return p[y * ld + x]; } };
+
+// RDOQ (kvz_hip_inter_residual_frame_rdoq, kvz_hip_intra_recon_frame_rdoq) is rdoq_source, the last trailing argument, behind the lists
+// where there are lists: kvz_hip_rdoq_source as the kernel reads it.  A TU wider than 4, and a 4x4 TU unless skip is set, takes its
+// levels from kvz_rdoq (rdoq_core.h through rdoq_stage.h) on the context set and the state of its LCU, an index beyond the table being
+// the last set; every other TU keeps the plain quantiser.  What a wave holds about its LCU for that is rdoq_lcu<true>, which
+// rdoq_stage.h defines: the translation units without RDOQ never see the cost arithmetic or its floating-point pragma.
+struct rdoq_source {
+  const kvz_hip_coeff_ctx *sets;
+  const kvz_hip_rdoq_state *states;
+  const uint16_t *lcu_ctx;
+  const int32_t *quant;
+  const double *err_scale;
+  u32 n_sets;
+  int skip;
+};
+template <bool ON> struct rdoq_lcu { static constexpr bool on = false; };
 
 // The body of the init kernels: outputs that the TUs of several planes accumulate into start from zero inside the stage's CUs, and
 // keep their contents elsewhere.  a: the picture's record (cus, cus_stride, cbf_out, cost), i: an SCU of it in raster order, cu_at:

@@ -168,10 +168,14 @@ struct cabac_lds_ctx {
 // The lanes beyond 8 repeat lane % 8.  A chroma TU of the same kernel is coded as without TS.
 // CABAC (with TS): where the LCU's QP is at or above the limit, a trial's price is get_coeff_cabac_cost of its 16 levels
 // (coeff_cabac_core.h) instead of the estimate: the first lane of each trial's quad counts on a copy of the LCU's set of its own.
-template <int N, bool TILES, bool SL = false, bool TS = false, bool CABAC = false, typename ARGS>
+// RQ (rdoq_lcu<true>, rdoq_stage.h; without TS): a TU that takes RDOQ gets its levels from kvz_rdoq on the coefficient rows instead of
+// the quantiser and its sign hiding; tr_depth is what kvz_quantize_residual hands over for the TU.  Everything after the levels is shared.
+template <int N, bool TILES, bool SL = false, bool TS = false, bool CABAC = false, typename ARGS, typename RQ = rdoq_lcu<false>>
 __device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const tile_rect &tr, const quant_consts &k, u8 *tile, u8 (*s_ref)[RS],
-                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq, const ts_lcu ts = {}, const cabac_lcu cb = {})
+                                        u8 *s_ext, u8 *s_pred, i16 *ta, i16 *tb, i16 *tq, const ts_lcu ts = {}, const cabac_lcu cb = {},
+                                        const RQ rq = {}, int tr_depth = 0)
 {
+  static_assert(!RQ::on || !TS, "RDOQ: not together with transform skip");
   static_assert(!TS || N == 4, "transform skip: 4x4 TUs only");
   static_assert(!CABAC || TS, "CABAC pricing belongs to the transform-skip decision");
   constexpr int LOG2 = N == 4 ? 2 : N == 8 ? 3 : N == 16 ? 4 : 5, LD = lds_tile_ld(N), W4 = N / 4;
@@ -286,7 +290,18 @@ __device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const t
     }
   }
   int any = 0;
-  if constexpr (SL) {
+  [[maybe_unused]] bool rdoq = false;                                           // RQ: kvz_rdoq instead of kvz_quant (wave-uniform)
+  if constexpr (RQ::on) {
+    rdoq = rq.takes(N);
+    if (rdoq) {
+      rq.template tu<N, LD>(ta, tq, lane, t.plane ? 2 : 0, t.scan, 1, tr_depth);
+#pragma unroll
+      for (int x = 0; x < N; ++x) any |= tq[row * LD + x];
+    }
+  }
+  if (rdoq) {
+    // the levels are kvz_rdoq's, its own sign hiding included
+  } else if constexpr (SL) {
 #pragma unroll
     for (int j = 0; j < W4; ++j) {
       const int4 f4 = *(const int4 *)(k.qtable + row * N + 4 * j);
@@ -306,7 +321,7 @@ __device__ __forceinline__ void intra_tu(const ARGS &a, const tu_pos &t, const t
       any |= v;
     }
   }
-  if (k.signhide) {
+  if (k.signhide && !rdoq) {
     // a lane per coefficient group, as sign_hide_kernel (quant.hip): the block's ac_sum is a sum over the lanes, the "last"
     // group a ballot of the lanes that hold a level
     __syncthreads();
@@ -525,7 +540,8 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
 {
   constexpr bool MULTI = batch_of<ARGS>::multi, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2 || batch_of<ARGS>::tiles,
                  SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl, TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts,
-                 CABAC = pack_has<cabac_source, PER_LCU...>;
+                 CABAC = pack_has<cabac_source, PER_LCU...>, RDOQ = pack_has<rdoq_source, PER_LCU...>;
+  static_assert(!RDOQ || (LCU_QP && !MULTI && !TS), "RDOQ: the single-picture entries without transform skip");
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -623,6 +639,7 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
   lcu_sets<LCU_QP> own;                                                      // the LCU's own sets, [log2 N - 2]
   [[maybe_unused]] ts_lcu skip = {};
   [[maybe_unused]] cabac_lcu price = {};
+  [[maybe_unused]] rdoq_lcu<RDOQ> rq = {};
   if constexpr (MULTI) {
     // the array's value clamped as in the per-LCU entry, or the picture's QP as it stands as in the one-QP entry
     const int qp = (int)__builtin_amdgcn_readfirstlane((u32)(a.lcu_qp ? clip_lcu_qp((int)a.lcu_qp[(size_t)lcu_y * a.lcus_x + lcu_x]) : a.qp));
@@ -660,6 +677,15 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
       const u32 want = __builtin_amdgcn_readfirstlane(cb.lcu_ctx ? (u32)cb.lcu_ctx[(size_t)lcu_y * a.lcus_x + lcu_x] : 0u);
       price = { cb.sets + min(want, cb.n_sets - 1u), qp >= cb.fast_limit };   // an index beyond the table is its last set
     }
+    if constexpr (RDOQ) {
+      // the LCU's context set, state bytes and lambda into LDS once, beside the arrays of the recursion
+      __shared__ typename rdoq_lcu<RDOQ>::lds s_rdoq;
+      rq.m = &s_rdoq;
+      rq.r = source_of<rdoq_source>(per_lcu...);
+      rq.qp = qp;
+      rq.signhide = q.signhide != 0;
+      rq.stage((size_t)lcu_y * a.lcus_x + lcu_x, lane);
+    }
   }
 
   // ---- the walk: 256 SCUs in z-order; a leaf TU is done at its top-left SCU ----
@@ -689,6 +715,15 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
     const quant_consts *kk;
     if constexpr (LCU_QP) kk = own.k;
     else kk = a.k[plane ? 1 : 0];
+    if constexpr (RDOQ) {
+      // head is the record at the TU's own top-left SCU: the cur_pu of transform.c:437
+      const int trd = rq.tr_depth_of(head);
+      if (n == 32) intra_tu<32, TILES, SL>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq, {}, {}, rq, trd);
+      else if (n == 16) intra_tu<16, TILES, SL>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq, {}, {}, rq, trd);
+      else if (n == 8) intra_tu<8, TILES, SL>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq, {}, {}, rq, trd);
+      else intra_tu<4, TILES, SL>(a, p, tr, kk[0], tile, s_ref, s_ext, s_pred, sa, sb, sq, {}, {}, rq, trd);
+      continue;
+    }
     if (n == 32) intra_tu<32, TILES, SL>(a, p, tr, kk[3], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 16) intra_tu<16, TILES, SL>(a, p, tr, kk[2], tile, s_ref, s_ext, s_pred, sa, sb, sq);
     else if (n == 8) intra_tu<8, TILES, SL>(a, p, tr, kk[1], tile, s_ref, s_ext, s_pred, sa, sb, sq);

@@ -10,6 +10,7 @@
 // large kernel to three waves per CU.
 #include "rdoq_core.h"
 #include "quant_core.h"
+#include "rdoq_stage.h"
 #include "rdoq_host.h"
 
 #include <stdio.h>
@@ -28,29 +29,6 @@ __device__ __forceinline__ bool rdoq_desc_ok(const kvz_hip_rdoq_desc &d, u32 n_s
          (d.block_type == 1 || d.block_type == 2) && d.tr_depth <= 3 && (d.src_offset & 3u) == 0 && (d.dst_offset & 3u) == 0 && d.ctx_index < n_sets;
 }
 __device__ __forceinline__ bool rdoq_qp_ok(int qp) { return qp >= 0 && qp <= 51; }
-
-// byte i of the nine context bytes rdoq_core.h reads of a state (RQ_ROOT_CBF, RQ_CBF_LUMA.., RQ_CBF_CHROMA..), field by field
-__device__ __forceinline__ u8 rdoq_state_byte(const kvz_hip_rdoq_state &st, int i)
-{
-  return i == RQ_ROOT_CBF ? st.root_cbf : i < RQ_CBF_CHROMA ? st.qt_cbf_luma[i - RQ_CBF_LUMA] : st.qt_cbf_chroma[i - RQ_CBF_CHROMA];
-}
-
-// the constants of one TU (rdo.c:553-564) and where its two tables begin
-__device__ __forceinline__ rdoq_tu rdoq_make_tu(const kvz_hip_rdoq_desc &d, int qp, double lambda, int signhide, int &table_at)
-{
-  rdoq_tu t;
-  t.log2w = d.width == 4 ? 2 : d.width == 8 ? 3 : d.width == 16 ? 4 : 5;
-  t.type = d.type;
-  t.scan_mode = d.scan_mode;
-  t.intra = d.block_type == 1;
-  t.tr_depth = d.tr_depth;
-  t.qp_scaled = scaled_qp(d.type, qp);
-  t.q_bits = 14 + t.qp_scaled / 6 + (15 - 8 - t.log2w);
-  t.signhide = signhide;
-  t.lambda = lambda;
-  table_at = sl_table_offset(t.log2w - 2, (t.intra ? 0 : 3) + (d.type ? 1 : 0), t.qp_scaled % 6);
-  return t;
-}
 
 __global__ void __launch_bounds__(64) rdoq_small_kernel(const kvz_hip_coeff *__restrict__ coef, kvz_hip_coeff *__restrict__ dest,
                                                         const kvz_hip_rdoq_desc *__restrict__ descs, u32 n, const kvz_hip_coeff_ctx *__restrict__ ctx_sets,

@@ -261,6 +261,8 @@ def main():
         coeff_cost_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
     if not args.only or any(o in "rdoq_batch_1080p_4x4 rdoq_batch_1080p_8x8 rdoq_batch_1080p_16x16 rdoq_batch_1080p_32x32" for o in args.only.split(",")):
         rdoq_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "inter_residual_rdoq_1080p intra_recon_rdoq_1080p_mixed intra_recon_rdoq_1080p_all" for o in args.only.split(",")):
+        rdoq_chain_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
 
 
 RDOQ_QP = 27
@@ -319,6 +321,80 @@ def rdoq_rows(L, st, dev, rounds, only, iters=5):
         ms = float(np.median(t))
         print("%-32s %9d %10.4f %18s %10d %12.3f %10.1f   %.2f levels / TU" % (name, 2, ms, "%.4f..%.4f" % (min(t), max(t)), count, count / ms / 1e3,
                                                                                 ms * 1e6 / count, float((dest != 0).float().sum()) / count))
+
+
+def rdoq_chain_rows(L, st, dev, rounds, only, iters=3):
+    """RDOQ inside the two residual stages: kvz_hip_inter_residual_frame_rdoq on the picture of the inter_residual_frame_1080p row and
+    kvz_hip_intra_recon_frame_rdoq on the two pictures of the intra_recon_frame_1080p_* rows, at QP 27 with flat lists, one context set per
+    LCU row (drawn from the fixture's sets, lambda of QP 27), sign hiding as in those rows.  Per picture, interleaved round by round in one
+    process: the entry with rdoq == NULL (the _sl entry on the same arguments: the stage without RDOQ), rdoq_skip 0 and rdoq_skip 1.  Device
+    time by events, ms per call: median and min..max over the rounds; TUs of the stage, and ns per TU for the inter stage."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inter_residual_cases as RC
+    import intra_recon_cases as XC
+    import rdoq_cases as K
+    W, H = 1920, 1080
+    lx, ly = (W + 63) // 64, (H + 63) // 64
+    z = np.load(os.path.join(ROOT, "tests", "golden", "rdoq.npz"))
+    dumps = z["dumps"][np.random.default_rng(61).integers(0, len(z["dumps"]), ly)]
+    sets = np.array([api.coeff_ctx_from_dump(d, 256) for d in dumps], dtype=api.COEFF_CTX)
+    states = np.array([api.rdoq_state_from_dump(d, K.lambda_of(RDOQ_QP), RDOQ_QP) for d in dumps], dtype=api.RDOQ_STATE)
+    lcu_ctx = np.repeat(np.arange(ly, dtype=np.uint16), lx)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    d_s, d_t, d_l, d_q, d_e = (up(a) for a in (sets, states, lcu_ctx, z["quant"][0], z["err_scale"][0]))
+    rq = [_lib.RdoqSource(d_s.data_ptr(), d_t.data_ptr(), d_l.data_ptr(), _lib.RdoqTables(d_q.data_ptr(), d_e.data_ptr()), len(sets), skip) for skip in (0, 1)]
+    print("%-34s %12s %9s %10s %18s %10s %10s" % ("kernel", "variant", "launches", "ms", "min..max ms", "TUs", "ns / TU"))
+    pictures = (("inter_residual_rdoq_1080p", None), ("intra_recon_rdoq_1080p_mixed", 0.1), ("intra_recon_rdoq_1080p_all", 1.0))
+    for name, share in pictures:
+        if not any(o in name for o in only):
+            continue
+        up2 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+        if share is None:
+            cus, _ = RC.make_map(W, H, 41, intra_share=0.0, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+            pred = RC.smooth_planes(W, H, 42)
+            src, modes, signhide = RC.make_source(pred, cus, 43), None, 0
+            n_tus, launches = len(RC.walk_tus(cus, W, H)), 5
+        else:
+            cus, _, modes = XC.make_map(W, H, 51, intra_share=share, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+            (src, pred), signhide = XC.make_planes(cus, 52), 1
+            n_tus, launches = len(XC.walk_tus(cus, modes, W, H)), 1 + lx + 2 * (ly - 1)
+        src_d, master, cus_d = [up2(p) for p in src], [up2(p) for p in pred], up2(cus)
+        modes_d = up2(modes) if modes is not None else None
+        recs = [[torch.empty_like(m) for m in master] for _ in range(iters + 1)]
+        shapes = api.coeff_shapes(W, H)
+        co_d = [torch.empty(shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)]
+        cbf_d = torch.empty(cus.shape, dtype=torch.uint8, device=dev)
+        cost_d = torch.empty(cus.shape + (6,), dtype=torch.int32, device=dev)
+        table = api.ref_picture_table([(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2)], W, H)
+        prm = api.inter_residual_params(RDOQ_QP, 0, signhide, 1)
+        turn = [0]
+
+        def call(source):
+            r = recs[turn[0] % len(recs)]                # the inter stage works in place: a fresh copy of the prediction per call
+            turn[0] += 1
+            head = (table.ctypes.data, r[0].data_ptr(), W, r[1].data_ptr(), r[2].data_ptr(), W // 2, cus_d.data_ptr())
+            outs = (co_d[0].data_ptr(), co_d[1].data_ptr(), co_d[2].data_ptr(), cbf_d.data_ptr(), cost_d.data_ptr())
+            ref = C.byref(source) if source is not None else None
+            if modes_d is None:
+                return L.kvz_hip_inter_residual_frame_rdoq(*head, *outs, None, None, ref, prm.ctypes.data, st)
+            return L.kvz_hip_intra_recon_frame_rdoq(*head, modes_d.data_ptr(), *outs, None, None, None, ref, prm.ctypes.data, st)
+
+        def refresh():
+            for r in recs:
+                for d, m in zip(r, master):
+                    d.copy_(m)
+            torch.cuda.synchronize()
+            turn[0] = 0
+        variants = (("rdoq == NULL", None), ("rdoq_skip 0", rq[0]), ("rdoq_skip 1", rq[1]))
+        t = {v[0]: [] for v in variants}
+        for _ in range(rounds):                          # interleaved round by round
+            for what, source in variants:
+                refresh()
+                t[what].append(timed(L, st, lambda: _lib.check(call(source), name), iters=iters - 1, warm=1))
+        for what, _ in variants:
+            ms = float(np.median(t[what]))
+            print("%-34s %12s %9d %10.4f %18s %10d %10.1f" % (name, what, launches, ms, "%.4f..%.4f" % (min(t[what]), max(t[what])), n_tus, ms * 1e6 / n_tus))
 
 
 def rdoq_cpu_rows(limit=4000):
