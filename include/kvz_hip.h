@@ -1750,7 +1750,8 @@ typedef struct {
  *   grid.  Usable between kvz_hip_graph_begin / _end; a captured call may be replayed after the CONTENTS of every array changed.
  *   The ABI version stays 4.
  * OUT OF SCOPE: transform skip together with RDOQ (these entries take no kvz_hip_trskip), the multi-picture _frames / _frames_ts
- *   entries, the drop-in's quantize_residual, lossless, bit depths above 8, a recursion on more than one lane. */
+ *   entries, the drop-in's quantize_residual, lossless, bit depths above 8, a recursion on more than one lane.  Since then the
+ *   multi-picture form exists as entries of its own: the _frames_rdoq entries further below. */
 KVZ_HIP_API int kvz_hip_inter_residual_frame_rdoq(const kvz_hip_ref_picture *src, kvz_hip_pixel *rec_y, uint32_t stride_y, kvz_hip_pixel *rec_u,
                                                   kvz_hip_pixel *rec_v, uint32_t stride_c, kvz_hip_cu_info *cus, kvz_hip_coeff *coeff_y,
                                                   kvz_hip_coeff *coeff_u, kvz_hip_coeff *coeff_v, uint8_t *cbf_out,
@@ -1875,9 +1876,65 @@ typedef struct {
  *   pictures (the QP map, deblocking and SAO of several pictures are kvz_hip_cu_qp_frames, kvz_hip_deblock_frames,
  *   kvz_hip_sao_stats_frames and kvz_hip_sao_frames below) in these entries -- it is an entry of its own,
  *   kvz_hip_inter_recon_frames further below; RDOQ.  The ABI version stays 4.  (RDOQ exists as the batch entry kvz_hip_rdoq_batch,
- *   above; inside these stages it is still to come.) */
+ *   above; inside these stages it is still to come.)  Since then it came, as entries of their own: the _frames_rdoq entries below. */
 KVZ_HIP_API int kvz_hip_inter_residual_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
 KVZ_HIP_API int kvz_hip_intra_recon_frames_ts(const kvz_hip_chain_picture_ts *pictures, int n_pictures, kvz_hip_stream s);
+
+/* ------------------------------------------------------------------ */
+/* Several independent pictures with RDOQ through the residual stages  */
+/*   reference: the pictures in flight (--owf) of an encode at preset  */
+/*   medium and slower, where cfg.rdoq_enable is set                   */
+/* ------------------------------------------------------------------ */
+/* One picture of kvz_hip_*_frames_rdoq: the arguments of kvz_hip_inter_residual_frame_rdoq / kvz_hip_intra_recon_frame_rdoq as a
+ * record.  The record is HOST memory, copied at the call, and so is what grid and rdoq point to.  Offsets in front of the fields. */
+typedef struct {
+  kvz_hip_chain_picture pic;          /*   0: as for kvz_hip_*_frames; pic.params.scaling_list != 0 exactly when tables are given */
+  const kvz_hip_tile_grid *grid;      /* 160: HOST, optional, copied at the call; NULL = one tile.  Read by the intra entry only */
+  kvz_hip_scaling_tables tables;      /* 168: both NULL = flat lists; else both DEVICE, non-NULL, 16-byte aligned */
+  const kvz_hip_rdoq_source *rdoq;    /* 184: HOST, copied at the call; what it points to is DEVICE memory */
+} kvz_hip_chain_picture_rdoq;         /* 192 bytes */
+/* kvz_hip_inter_residual_frame_rdoq and kvz_hip_intra_recon_frame_rdoq for n_pictures (0..KVZ_HIP_MAX_CHAIN_PICTURES) pictures that do
+ * not depend on each other, in one asynchronous call.  With RDOQ the serial recursion of kvz_rdoq runs on one lane inside every step
+ * of the intra wavefront, and a launch of one picture leaves the rest of the device idle for that time: pictures in flight fill it.
+ * THE RULE: for every picture i and every output array (the rec planes, the coefficients, cus[].cbf_y, cbf_out, costs), the result is
+ *   byte for byte what kvz_hip_inter_residual_frame_rdoq / kvz_hip_intra_recon_frame_rdoq leaves when called with the fields of
+ *   pictures[i].  Everything those entries define holds per picture: which TUs take kvz_rdoq and which keep the plain quantiser; the
+ *   context set of the TU's LCU, an index >= n_sets used as n_sets - 1; tr_depth from the record at the TU's own top-left SCU; the QP
+ *   of the LCU; sign hiding; the tile rule for an intra TU's neighbours; the tables a TU takes.  Pictures of one call may differ in
+ *   size, chroma format (4:0:0 beside 4:2:0), QP, signhide and slice_is_intra; in their tile grid, tiled pictures beside untiled ones
+ *   included; in whether they carry lcu_qp, cbf_out and costs; in which scaling tables they point to; and in their ctx_sets, states,
+ *   lcu_ctx and n_sets: every picture has its own CABAC contexts and lambdas.
+ * ONE RESTRICTION: a call is homogeneous, after the model of kvz_hip_*_frames_ts.  Either every record carries tables or none does;
+ *   either every record carries rdoq or none does; and every record's rdoq->rdoq_skip, rdoq->tables.quant and rdoq->tables.err_scale
+ *   equal those of record 0.  All of them are encoder-wide (--scaling-list, --rdoq, --rdoq-skip, the lists the tables were packed
+ *   from).  The options select the kernel instantiation -- rdoq_skip also which 4x4 kernel the inter entry launches -- and the RDOQ
+ *   tables travel once per call because a pair of pointers per record would pass the 4 KB that a kernel's arguments may take.  A
+ *   record that differs from record 0 is refused.
+ * No rdoq at all: when no record carries rdoq, the call IS kvz_hip_inter_residual_frames_ts / kvz_hip_intra_recon_frames_ts on the
+ *   same fields with ts == NULL, byte for byte (it calls it, and that entry names itself in kvz_hip_last_error).
+ * Independence is the caller's promise, as for kvz_hip_*_frames.  Records whose rec_y, cus or coeff_y base pointers coincide are
+ *   refused; the tables, lcu_qp and everything rdoq points to are inputs and may be shared.
+ * Errors: those of kvz_hip_*_frames_ts (n_pictures == 0 is a no-op), and per record what the _rdoq single entry refuses: ctx_sets,
+ *   states, tables.quant or tables.err_scale NULL; n_sets == 0; ctx_sets or lcu_ctx not 2-byte aligned; states or err_scale not 8-byte
+ *   aligned; quant not 16-byte aligned.  Also: the homogeneity rule; shared outputs; and (intra entry) a record whose grid no longer
+ *   fits the pool of KVZ_HIP_CHAIN_TILE_BOUNDS boundaries.  The order per record: homogeneity, the record's own checks, its grid and
+ *   the grid's place in the pool, the outputs of the earlier records.  Every record is checked before anything is launched: a
+ *   refusal returns KVZ_HIP_ERR_INVALID, writes nothing for any picture, and kvz_hip_last_error() names the record's index
+ *   ("picture 2") -- for the pool, the record at which it overflowed.
+ * Execution: asynchronous on s; no host synchronisation, no allocation, no workspace -- the call owns no device buffer.  The records
+ *   (208 / 184 bytes per picture), the pool and the shared RDOQ tables travel in the kernel arguments and are read with scalar
+ *   loads.  Usable between kvz_hip_graph_begin / _end.  The launch shapes depend only on the sizes, the chroma flags, the grids,
+ *   rdoq_skip and the presence of cbf_out / costs: a captured call may be replayed after the CONTENTS of every device array changed,
+ *   the context sets and states included.
+ * Launches: kvz_hip_intra_recon_frames_rdoq makes the wavefront launches of kvz_hip_intra_recon_frames_ts -- max over the pictures of
+ *   (max over the picture's tiles of w_t + 2 (h_t - 1)) -- plus one init launch if any picture has cbf_out or costs; a wave per LCU
+ *   and plane.  kvz_hip_inter_residual_frames_rdoq makes the init launch and one launch per TU width, each covering all pictures,
+ *   a wave per TU; with rdoq_skip the 4x4 launch is that of kvz_hip_inter_residual_frames_ts.
+ * OUT OF SCOPE: transform skip together with RDOQ (the record has no ts), a call that mixes pictures with and without rdoq or with
+ *   different RDOQ tables, the drop-in's quantize_residual, lossless, bit depths above 8, a recursion on more than one lane.  The
+ *   single-picture entries and every older kernel are unchanged.  The ABI version stays 4. */
+KVZ_HIP_API int kvz_hip_inter_residual_frames_rdoq(const kvz_hip_chain_picture_rdoq *pictures, int n_pictures, kvz_hip_stream s);
+KVZ_HIP_API int kvz_hip_intra_recon_frames_rdoq(const kvz_hip_chain_picture_rdoq *pictures, int n_pictures, kvz_hip_stream s);
 
 /* ------------------------------------------------------------------ */
 /* Several independent pictures through the QP map, deblocking and     */

@@ -184,6 +184,11 @@ class RdoqSource(C.Structure):
                 ("rdoq_skip", C.c_int32)]
 
 
+class ChainPictureRdoq(C.Structure):
+    """kvz_hip_chain_picture_rdoq"""
+    _fields_ = [("pic", ChainPicture), ("grid", C.POINTER(TileGrid)), ("tables", ScalingTables), ("rdoq", C.POINTER(RdoqSource))]
+
+
 class RdoqParams(C.Structure):
     """kvz_hip_rdoq_params"""
     _fields_ = [("signhide", C.c_int32), ("reserved", C.c_int32 * 3)]
@@ -308,6 +313,8 @@ SIGNATURES = {
     "kvz_hip_intra_recon_frames": (_I, [C.POINTER(ChainPicture), _I, _P]),
     "kvz_hip_inter_residual_frames_ts": (_I, [C.POINTER(ChainPictureTs), _I, _P]),
     "kvz_hip_intra_recon_frames_ts": (_I, [C.POINTER(ChainPictureTs), _I, _P]),
+    "kvz_hip_inter_residual_frames_rdoq": (_I, [C.POINTER(ChainPictureRdoq), _I, _P]),
+    "kvz_hip_intra_recon_frames_rdoq": (_I, [C.POINTER(ChainPictureRdoq), _I, _P]),
     "kvz_hip_cu_qp_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_deblock_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),
     "kvz_hip_sao_stats_frames": (_I, [C.POINTER(FilterPicture), _I, _P]),

@@ -1123,6 +1123,64 @@ def _chain_frames_ts(intra, pictures):
     return [st.result() for st in staged]
 
 
+# ---- several independent pictures with RDOQ ----
+def inter_residual_frames_rdoq(pictures):
+    """kvz_hip_inter_residual_frames_rdoq.  pictures: as for inter_residual_frames, each dict with the optional keys tables=(quant,
+    dequant), the packed arrays of scaling_tables_pack, and rdoq=dict(sets=..., states=..., tables=(quant, err_scale), lcu_ctx=...,
+    skip=0 | 1) as inter_residual_frame takes it.  Either every picture carries tables or none does, and the same for rdoq; skip and
+    the RDOQ tables are the call's: tables with the same values are uploaded once and shared, as the entry requires.  grid is accepted
+    and ignored: the stage does not depend on tiles.  Returns inter_residual_frames' list of dicts."""
+    return _chain_frames_rdoq(False, pictures)
+
+
+def intra_recon_frames_rdoq(pictures):
+    """kvz_hip_intra_recon_frames_rdoq.  pictures: as for intra_recon_frames, each dict with the optional keys grid=(col_bd, row_bd),
+    the tile boundaries in LCUs as tile_grid takes them, and tables / rdoq as for inter_residual_frames_rdoq.  Tiled pictures may stand
+    beside untiled ones; every picture has its own context sets, states and lcu_ctx."""
+    return _chain_frames_rdoq(True, pictures)
+
+
+class _ChainPictureRdoq(_ChainPictureTs):
+    """_ChainPictureTs without transform skip, with the kvz_hip_rdoq_source of one picture, and the 192-byte record.  shared: the RDOQ
+    tables already on the device for this call, [(quant, err_scale, device quant, device err_scale)]"""
+
+    def __init__(self, intra, shared, rdoq=None, **plain):
+        super().__init__(intra, **plain)
+        assert self.dts is None, "rdoq together with trskip: the _rdoq entries take no kvz_hip_trskip"
+        height, width = plain["src"][0].shape
+        rec = _lib.ChainPictureRdoq()
+        rec.pic, rec.grid, rec.tables = self.record_ts.pic, self.record_ts.grid, self.record_ts.tables
+        if rdoq is not None:
+            sets = np.ascontiguousarray(rdoq["sets"], dtype=COEFF_CTX).ravel()
+            states = np.ascontiguousarray(rdoq["states"], dtype=RDOQ_STATE).ravel()
+            assert len(sets) == len(states)
+            rq_q = np.ascontiguousarray(rdoq["tables"][0], dtype=np.int32).reshape(SL_TABLE_LEN)
+            rq_e = np.ascontiguousarray(rdoq["tables"][1], dtype=np.float64).reshape(SL_TABLE_LEN)
+            same = [t for t in shared if np.array_equal(t[0], rq_q) and np.array_equal(t[1], rq_e)]
+            if not same:
+                shared.append((rq_q, rq_e, DeviceBuffer.from_numpy(rq_q), DeviceBuffer.from_numpy(rq_e)))
+                same = shared[-1:]
+            self.d_rq = [DeviceBuffer.from_numpy(sets), DeviceBuffer.from_numpy(states), same[0][2], same[0][3]]
+            self.d_lc = None
+            if rdoq.get("lcu_ctx") is not None:
+                self.d_lc = DeviceBuffer.from_numpy(np.ascontiguousarray(rdoq["lcu_ctx"], dtype=np.uint16).reshape(lcu_count(width, height)))
+            # the staged kvz_hip_rdoq_source stays alive with the picture, over the call
+            self.rq = _lib.RdoqSource(self.d_rq[0].ptr, self.d_rq[1].ptr, self.d_lc.ptr if self.d_lc is not None else None,
+                                      _lib.RdoqTables(self.d_rq[2].ptr, self.d_rq[3].ptr), len(sets), int(rdoq.get("skip", 0)))
+            rec.rdoq = C.pointer(self.rq)
+        self.record_rdoq = rec
+
+
+def _chain_frames_rdoq(intra, pictures):
+    L = _lib.init()
+    shared = []
+    staged = [_ChainPictureRdoq(intra, shared, **p) for p in pictures]
+    records = (_lib.ChainPictureRdoq * max(len(staged), 1))(*[st.record_rdoq for st in staged])
+    entry = L.kvz_hip_intra_recon_frames_rdoq if intra else L.kvz_hip_inter_residual_frames_rdoq
+    check(entry(records, len(staged), None), "intra_recon frames_rdoq" if intra else "inter_residual frames_rdoq")
+    return [st.result() for st in staged]
+
+
 # ---- lossless coding: the two residual stages of a picture coded with --lossless ----
 def inter_residual_frame_lossless(src, pred, cus, chroma=1, implicit_rdpcm=0, coeff=None, cbf_out=None, costs=None):
     """kvz_hip_inter_residual_frame_lossless.  Arguments and the returned dict as inter_residual_frame, without a QP: coeff = source -

@@ -223,6 +223,36 @@ inline const char *chain_record_ts_shared(const kvz_hip_chain_picture_ts *pictur
   return nullptr;
 }
 
+// kvz_hip_inter_residual_frames_rdoq / kvz_hip_intra_recon_frames_rdoq; lists: record 0 carries tables, skip: record 0's rdoq_skip (not
+// read where record 0 carries no rdoq).  Homogeneity comes first, as in chain_record_ts_why, so the kernel that would run is known
+// before a record is looked into: the presence of tables and of rdoq, then the three values that the records of a call share.  Then
+// the record's own checks -- tables, the picture, chain_rdoq_why, the QP; then (chain_record_rdoq_shared) the earlier records: the
+// intra entry checks the record's tile grid between the two
+static_assert(sizeof(kvz_hip_chain_picture_rdoq) == 192 && sizeof(kvz_hip_rdoq_source) == 48, "layout documented in kvz_hip.h");
+inline const char *chain_record_rdoq_why(const kvz_hip_chain_picture_rdoq *pictures, int i, bool intra, bool lists, bool skip)
+{
+  const kvz_hip_chain_picture_rdoq &r = pictures[i];
+  const kvz_hip_rdoq_source *first = pictures[0].rdoq;
+  const bool has_lists = r.tables.quant || r.tables.dequant;
+  if (has_lists != lists || (r.rdoq != nullptr) != (first != nullptr))
+    return "a call is homogeneous: every record carries tables or none does, every record carries rdoq or none does";
+  if (r.rdoq && ((r.rdoq->rdoq_skip != 0) != skip || r.rdoq->tables.quant != first->tables.quant || r.rdoq->tables.err_scale != first->tables.err_scale))
+    return "a call is homogeneous: rdoq_skip, rdoq->tables.quant and rdoq->tables.err_scale are those of record 0";
+  if (has_lists && !chain_tables_ok(r.tables)) return "a table is null or not 16-byte aligned";
+  if (!chain_picture_args_ok(r.pic, intra, has_lists))
+    return "null or misaligned buffer, size or parameter out of range, or scaling_list does not say whether tables are given";
+  if (r.rdoq)
+    if (const char *why = chain_rdoq_why(r.rdoq)) return why;
+  if (!chain_one_qp_ok(r.pic)) return "a negative qp without lcu_qp";
+  return nullptr;
+}
+inline const char *chain_record_rdoq_shared(const kvz_hip_chain_picture_rdoq *pictures, int i)
+{
+  for (int j = 0; j < i; ++j)
+    if (chain_output_shared(pictures[i].pic, pictures[j].pic)) return "an output shared with another picture";
+  return nullptr;
+}
+
 // ---- the hash stage: kvz_hip_picture_hash_frame(s) and kvz_hip_array_checksum_batch ----
 static_assert(sizeof(kvz_hip_lcu_hash) == 24 && sizeof(kvz_hip_picture_hash) == 40 && sizeof(kvz_hip_hash_picture) == 104 &&
               sizeof(kvz_hip_hash_plane) == 24, "layout documented in kvz_hip.h");

@@ -1,7 +1,7 @@
 // intra_recon_core.h -- the kernels and the host side of the whole-picture intra entries (intra_recon.hip: one QP per call,
 // intra_recon_qp.hip: a QP per LCU, intra_recon_tiles.hip: a tiled picture, intra_recon_sl.hip: scaling lists, intra_recon_ts.hip:
 // transform skip, intra_recon_multi.hip: several pictures in one call, intra_recon_multi_ts.hip: several pictures with tiles, scaling
-// lists and transform skip).  Everything here has
+// lists and transform skip, intra_recon_rdoq.hip: RDOQ, intra_recon_multi_rdoq.hip: several pictures with RDOQ).  Everything here has
 // internal linkage: each of the translation units gets its own copy and instantiates exactly one of the kernels.  The algorithm is
 // described in intra_recon.hip.
 #pragma once
@@ -96,9 +96,35 @@ static_assert(sizeof(intra_pic_ts) == 200 && sizeof(intra_batch_ts_data) == 3200
               "the records and the pool travel in the kernel arguments: 4 KB with the wave index");
 template <bool SL, bool TS> struct picture_type<intra_batch_ts<SL, TS>> { using type = intra_pic_ts; };
 // what the type of the kernel's first argument says about the instantiation
-template <typename ARGS> struct batch_of { static constexpr bool multi = false, tiles = false, sl = false, ts = false; };
-template <> struct batch_of<intra_batch> { static constexpr bool multi = true, tiles = false, sl = false, ts = false; };
-template <bool SL, bool TS> struct batch_of<intra_batch_ts<SL, TS>> { static constexpr bool multi = true, tiles = true, sl = SL, ts = TS; };
+template <typename ARGS> struct batch_of { static constexpr bool multi = false, tiles = false, sl = false, ts = false, rdoq = false; };
+template <> struct batch_of<intra_batch> { static constexpr bool multi = true, tiles = false, sl = false, ts = false, rdoq = false; };
+template <bool SL, bool TS> struct batch_of<intra_batch_ts<SL, TS>> { static constexpr bool multi = true, tiles = true, sl = SL, ts = TS, rdoq = false; };
+
+// One picture of kvz_hip_intra_recon_frames_rdoq: intra_pic, the picture's scaling tables, its own context sets, states and set index
+// per LCU, and its tile grid in the pool as in intra_pic_ts.  208 bytes.  The RDOQ tables and rdoq_skip are the call's, once beside
+// the records: a pair of pointers per record more would pass the 4 KB of the kernel arguments.
+struct intra_pic_rdoq : intra_pic {
+  const int32_t *quant, *dequant;          // SL: the packed tables
+  const kvz_hip_coeff_ctx *sets;
+  const kvz_hip_rdoq_state *states;
+  const uint16_t *lcu_ctx;                 // or nullptr: set 0 in every LCU
+  u32 n_sets;
+  uint16_t col_at, row_at;                 // where col_bd[0] and row_bd[0] stand in the pool
+  u8 cols, rows, pad2[6];
+};
+struct intra_batch_rdoq_data {
+  intra_pic_rdoq p[KVZ_HIP_MAX_CHAIN_PICTURES];
+  u32 bd[KVZ_HIP_CHAIN_TILE_BOUNDS / 2];
+  const int32_t *quant;                    // kvz_hip_rdoq_tables of the call
+  const double *err_scale;
+  int skip, pad;
+  __device__ __forceinline__ int bound(int i) const { return (int)((bd[i >> 1] >> (16 * (i & 1))) & 0xffffu); }
+};
+template <bool SL> struct intra_batch_rdoq : intra_batch_rdoq_data {};
+static_assert(sizeof(intra_pic_rdoq) == 208 && sizeof(intra_batch_rdoq_data) == 3328 + 2 * KVZ_HIP_CHAIN_TILE_BOUNDS + 24 &&
+              sizeof(intra_batch_rdoq<true>) + 8 <= 4096, "the records, the pool and the shared tables travel in the kernel arguments: 4 KB with the wave index");
+template <bool SL> struct picture_type<intra_batch_rdoq<SL>> { using type = intra_pic_rdoq; };
+template <bool SL> struct batch_of<intra_batch_rdoq<SL>> { static constexpr bool multi = true, tiles = true, sl = SL, ts = false, rdoq = true; };
 
 // The LCU's tile in LDS: pixel (x, y) of the plane relative to the LCU's top-left, x = -1 .. T + T/2 - 1, y = -1 .. T - 1
 // (T = 64 luma, 32 chroma).  Column 0 stands at a dword boundary.
@@ -530,7 +556,9 @@ __device__ __forceinline__ int compact4(int i) { i &= 0x55; i = (i | (i >> 1)) &
 // tile column, LCU (x0 + t - 2 (ly - y0), ly) of the tile that begins at LCU (x0, y0): the waves of all tiles share the launches, and the
 // rectangle that stands for the picture in everything about neighbours is the tile.  Several pictures (ARGS = intra_batch,
 // kvz_hip_intra_recon_frames): grid (max lcus_y, planes, pictures); the workgroup takes its picture's record at blockIdx.z, leaves at
-// once where that picture has no such plane, row or wave, and derives its constants as the per-LCU kernel does.  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
+// once where that picture has no such plane, row or wave, and derives its constants as the per-LCU kernel does.  With RDOQ
+// (ARGS = intra_batch_rdoq<SL>, kvz_hip_intra_recon_frames_rdoq) it also makes its rdoq_source of its picture's record and the call's
+// tables.  WG = 64 is part of the algorithm, not a tuning value: intra_tu lets
 // the lanes beyond a TU's N rows repeat row lane % N, which is the same value to the same LDS address only while all of them are
 // one wave in lockstep; with a second wave the read-modify-write of ta / tq would race.
 constexpr int WG = 64;
@@ -540,8 +568,8 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
 {
   constexpr bool MULTI = batch_of<ARGS>::multi, LCU_QP = MULTI || sizeof...(PER_LCU) != 0, TILES = sizeof...(PER_LCU) >= 2 || batch_of<ARGS>::tiles,
                  SL = pack_has<sl_source, PER_LCU...> || batch_of<ARGS>::sl, TS = pack_has<ts_source, PER_LCU...> || batch_of<ARGS>::ts,
-                 CABAC = pack_has<cabac_source, PER_LCU...>, RDOQ = pack_has<rdoq_source, PER_LCU...>;
-  static_assert(!RDOQ || (LCU_QP && !MULTI && !TS), "RDOQ: the single-picture entries without transform skip");
+                 CABAC = pack_has<cabac_source, PER_LCU...>, RDOQ = pack_has<rdoq_source, PER_LCU...> || batch_of<ARGS>::rdoq;
+  static_assert(!RDOQ || (LCU_QP && !TS), "RDOQ: not together with transform skip");
   __shared__ __attribute__((aligned(16))) u8 tile[TILE_BYTES];
   __shared__ __attribute__((aligned(16))) u8 s_ref[4][RS];
   __shared__ __attribute__((aligned(16))) u8 s_ext[3 * 32 + 4];
@@ -651,6 +679,15 @@ __global__ __launch_bounds__(WG) void intra_recon_wave_kernel(ARGS args, int t, 
     if constexpr (TS) {
       const int v = (int)__builtin_amdgcn_readfirstlane((u32)(a.lcu_bit_cost ? a.lcu_bit_cost[(size_t)lcu_y * a.lcus_x + lcu_x] : a.bit_cost));
       skip = { qp, (u32)max(v, 0), a.tr_skip_out };
+    }
+    if constexpr (RDOQ) {
+      // the wave's source from its picture's record and the call's tables (scalar loads from the kernel arguments), then as below
+      __shared__ typename rdoq_lcu<RDOQ>::lds s_rdoq;
+      rq.m = &s_rdoq;
+      rq.r = { a.sets, a.states, a.lcu_ctx, args.quant, args.err_scale, a.n_sets, args.skip };
+      rq.qp = qp;
+      rq.signhide = a.signhide != 0;
+      rq.stage((size_t)lcu_y * a.lcus_x + lcu_x, lane);
     }
   } else if constexpr (LCU_QP) {
     const lcu_qp_source &q = source_of<lcu_qp_source>(per_lcu...);

@@ -263,6 +263,8 @@ def main():
         rdoq_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
     if not args.only or any(o in "inter_residual_rdoq_1080p intra_recon_rdoq_1080p_mixed intra_recon_rdoq_1080p_all" for o in args.only.split(",")):
         rdoq_chain_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
+    if not args.only or any(o in "inter_residual_frames_rdoq_1080p_x4 intra_recon_frames_rdoq_1080p_all_x4" for o in args.only.split(",")):
+        rdoq_chain_multi_rows(L, st, dev, max(args.rounds, 5), args.only.split(",") if args.only else [""])
 
 
 RDOQ_QP = 27
@@ -395,6 +397,98 @@ def rdoq_chain_rows(L, st, dev, rounds, only, iters=3):
         for what, _ in variants:
             ms = float(np.median(t[what]))
             print("%-34s %12s %9d %10.4f %18s %10d %10.1f" % (name, what, launches, ms, "%.4f..%.4f" % (min(t[what]), max(t[what])), n_tus, ms * 1e6 / n_tus))
+
+
+def rdoq_chain_multi_rows(L, st, dev, rounds, only, iters=3, n_pic=4):
+    """RDOQ in the multi-picture entries: four 1080p P pictures through kvz_hip_inter_residual_frames_rdoq and four all-intra 1080p pictures
+    through kvz_hip_intra_recon_frames_rdoq (the pictures, QP, sets and sign hiding of rdoq_chain_rows, rdoq_skip 0, every picture with
+    outputs of its own), against four calls of the single-picture _rdoq entry on the same records; the two interleaved round by round in
+    one process.  Device time by events, ms for the four pictures: median and min..max over the rounds."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import inter_residual_cases as RC
+    import intra_recon_cases as XC
+    import rdoq_cases as K
+    W, H = 1920, 1080
+    lx, ly = (W + 63) // 64, (H + 63) // 64
+    z = np.load(os.path.join(ROOT, "tests", "golden", "rdoq.npz"))
+    dumps = z["dumps"][np.random.default_rng(61).integers(0, len(z["dumps"]), ly)]
+    sets = np.array([api.coeff_ctx_from_dump(d, 256) for d in dumps], dtype=api.COEFF_CTX)
+    states = np.array([api.rdoq_state_from_dump(d, K.lambda_of(RDOQ_QP), RDOQ_QP) for d in dumps], dtype=api.RDOQ_STATE)
+    lcu_ctx = np.repeat(np.arange(ly, dtype=np.uint16), lx)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+    up2 = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).copy()).to(dev)
+    d_s, d_t, d_l, d_q, d_e = (up(a) for a in (sets, states, lcu_ctx, z["quant"][0], z["err_scale"][0]))
+    rq = _lib.RdoqSource(d_s.data_ptr(), d_t.data_ptr(), d_l.data_ptr(), _lib.RdoqTables(d_q.data_ptr(), d_e.data_ptr()), len(sets), 0)
+    print("%-34s %16s %9s %10s %18s" % ("kernel", "variant", "launches", "ms", "min..max ms"))
+    for name, intra in (("inter_residual_frames_rdoq_1080p_x4", False), ("intra_recon_frames_rdoq_1080p_all_x4", True)):
+        if not any(o in name for o in only):
+            continue
+        if not intra:
+            cus, _ = RC.make_map(W, H, 41, intra_share=0.0, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+            pred = RC.smooth_planes(W, H, 42)
+            src, modes, signhide, launches = RC.make_source(pred, cus, 43), None, 0, 5
+        else:
+            cus, _, modes = XC.make_map(W, H, 51, intra_share=1.0, blank_share=0.0, bad_share=0.0, far=0.0, edge_cu=False)
+            (src, pred), signhide, launches = XC.make_planes(cus, 52), 1, 1 + lx + 2 * (ly - 1)
+        src_d, master = [up2(p) for p in src], [up2(p) for p in pred]
+        modes_d = up2(modes) if modes is not None else None
+        table = api.ref_picture_table([(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2)], W, H)
+        prm = api.inter_residual_params(RDOQ_QP, 0, signhide, 1)
+        shapes = api.coeff_shapes(W, H)
+        # per picture: a map, coefficients, flags and costs of its own, and a prediction per call of a round (the stages work in place)
+        pics = []
+        for _ in range(n_pic):
+            pics.append(dict(cus=up2(cus), co=[torch.empty(shapes[1 if k else 0], dtype=torch.int16, device=dev) for k in range(3)],
+                             cbf=torch.empty(cus.shape, dtype=torch.uint8, device=dev), cost=torch.empty(cus.shape + (6,), dtype=torch.int32, device=dev),
+                             recs=[[torch.empty_like(m) for m in master] for _ in range(iters + 1)]))
+        turn = [0]
+
+        def records():
+            recs = (_lib.ChainPictureRdoq * n_pic)()
+            for r, p in zip(recs, pics):
+                rec = p["recs"][turn[0] % (iters + 1)]
+                r.pic.src = _lib.RefPicture(src_d[0].data_ptr(), src_d[1].data_ptr(), src_d[2].data_ptr(), W, W // 2, W, H)
+                r.pic.rec_y, r.pic.rec_u, r.pic.rec_v, r.pic.stride_y, r.pic.stride_c = rec[0].data_ptr(), rec[1].data_ptr(), rec[2].data_ptr(), W, W // 2
+                r.pic.cus, r.pic.intra_modes = p["cus"].data_ptr(), modes_d.data_ptr() if intra else None
+                r.pic.coeff_y, r.pic.coeff_u, r.pic.coeff_v = (c.data_ptr() for c in p["co"])
+                r.pic.cbf_out, r.pic.costs = p["cbf"].data_ptr(), p["cost"].data_ptr()
+                r.pic.params = _lib.InterResidualParams(RDOQ_QP, 0, signhide, 0, 1, 0)
+                r.rdoq = C.pointer(rq)
+            turn[0] += 1
+            return recs
+
+        def one_call():
+            entry = L.kvz_hip_intra_recon_frames_rdoq if intra else L.kvz_hip_inter_residual_frames_rdoq
+            _lib.check(entry(records(), n_pic, st), name)
+
+        def four_calls():
+            for r in records():
+                p = r.pic
+                head = (table.ctypes.data, p.rec_y, W, p.rec_u, p.rec_v, W // 2, p.cus)
+                outs = (p.coeff_y, p.coeff_u, p.coeff_v, p.cbf_out, p.costs)
+                if intra:
+                    _lib.check(L.kvz_hip_intra_recon_frame_rdoq(*head, p.intra_modes, *outs, None, None, None, C.byref(rq), prm.ctypes.data, st), name)
+                else:
+                    _lib.check(L.kvz_hip_inter_residual_frame_rdoq(*head, *outs, None, None, C.byref(rq), prm.ctypes.data, st), name)
+
+        def refresh():
+            for p in pics:
+                for r in p["recs"]:
+                    for d, m in zip(r, master):
+                        d.copy_(m)
+            torch.cuda.synchronize()
+            turn[0] = 0
+        variants = (("four calls", four_calls, n_pic * launches), ("one call", one_call, launches))
+        t = {v[0]: [] for v in variants}
+        for _ in range(rounds):                          # interleaved round by round
+            for what, fn, _n in variants:
+                refresh()
+                t[what].append(timed(L, st, fn, iters=iters - 1, warm=1))
+        for what, _fn, n in variants:
+            ms = float(np.median(t[what]))
+            print("%-34s %16s %9d %10.4f %18s" % (name, what, n, ms, "%.4f..%.4f" % (min(t[what]), max(t[what]))))
+        print("%-34s %16s %9s %10.2f" % (name, "four / one", "", float(np.median(t["four calls"])) / float(np.median(t["one call"]))))
 
 
 def rdoq_cpu_rows(limit=4000):
