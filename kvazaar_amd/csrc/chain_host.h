@@ -3,7 +3,8 @@
 // kvz_hip_sao_*), motion compensation (kvz_hip_inter_recon_*) and the hash stage (kvz_hip_picture_hash_frame(s),
 // kvz_hip_array_checksum_batch): the refusal that names a record, the prologue on the record count, the size and plane rules, the tile
 // grid on the host with the pool of boundaries of a call, and per stage the rules of one picture as predicates on the stage's record,
-// the pack of a single-picture entry's arguments into that record, and why a record of a call is refused.  Each rule is written once.
+// the pack of a single-picture entry's arguments into that record, why a record of a call is refused, and the walk over the records
+// of a call (chain_records_why with the launch plan, filter_records_why, recon_records_why).  Each rule is written once.
 //
 // Host only: pointer and integer arithmetic on the structs of kvz_hip.h, which compare pointers and never follow them (a
 // kvz_hip_tile_grid, a kvz_hip_trskip and the pool of reference pictures are host memory and are read).  No device code and no HIP call,
@@ -174,6 +175,14 @@ inline const char *chain_rdoq_why(const kvz_hip_rdoq_source *r)
   if ((uintptr_t)r->tables.quant & 15) return "quant not 16-byte aligned";
   return nullptr;
 }
+// the text under which a single-picture entry refuses for that reason: refuse_entry(__func__, invalid_because(why).text)
+struct refusal_text { char text[200]; };
+inline refusal_text invalid_because(const char *why)
+{
+  refusal_text t;
+  snprintf(t.text, sizeof t.text, "invalid argument (%s)", why);
+  return t;
+}
 // one QP for the picture (no lcu_qp): what the one-QP entry refuses.  That entry asks make_consts (quant_core.h) for the constants of
 // the 4x4 luma and chroma TUs, which fails where scaled_qp is negative: for luma that is the QP itself, for chroma it is clamped into
 // 0..57 (tests/test_chain_host_checks.py holds this rule against what make_consts decided for every QP)
@@ -250,6 +259,66 @@ inline const char *chain_record_rdoq_shared(const kvz_hip_chain_picture_rdoq *pi
 {
   for (int j = 0; j < i; ++j)
     if (chain_output_shared(pictures[i].pic, pictures[j].pic)) return "an output shared with another picture";
+  return nullptr;
+}
+
+// ---- the records of a call of either residual stage, all checked before anything is launched ----
+// The three record types differ in how the picture and the grid are reached, and in which checks are theirs (chain_own_why takes
+// lists and skip from record 0).  kvz_hip_chain_picture has one reason for everything, the earlier records included, and never a grid.
+inline const kvz_hip_chain_picture &chain_pic(const kvz_hip_chain_picture &r) { return r; }
+inline const kvz_hip_chain_picture &chain_pic(const kvz_hip_chain_picture_ts &r) { return r.pic; }
+inline const kvz_hip_chain_picture &chain_pic(const kvz_hip_chain_picture_rdoq &r) { return r.pic; }
+inline const kvz_hip_tile_grid *chain_grid(const kvz_hip_chain_picture &) { return nullptr; }
+inline const kvz_hip_tile_grid *chain_grid(const kvz_hip_chain_picture_ts &r) { return r.grid; }
+inline const kvz_hip_tile_grid *chain_grid(const kvz_hip_chain_picture_rdoq &r) { return r.grid; }
+inline const char *chain_own_why(const kvz_hip_chain_picture *pictures, int i, bool intra) { return chain_record_why(pictures, i, intra); }
+inline const char *chain_own_why(const kvz_hip_chain_picture_ts *pictures, int i, bool intra)
+{
+  return chain_record_ts_why(pictures, i, intra, pictures[0].tables.quant || pictures[0].tables.dequant, pictures[0].ts != nullptr);
+}
+inline const char *chain_own_why(const kvz_hip_chain_picture_rdoq *pictures, int i, bool intra)
+{
+  const kvz_hip_rdoq_source *first = pictures[0].rdoq;
+  return chain_record_rdoq_why(pictures, i, intra, pictures[0].tables.quant || pictures[0].tables.dequant, first && first->rdoq_skip != 0);
+}
+inline const char *chain_shared_why(const kvz_hip_chain_picture *, int) { return nullptr; }
+inline const char *chain_shared_why(const kvz_hip_chain_picture_ts *pictures, int i) { return chain_record_ts_shared(pictures, i); }
+inline const char *chain_shared_why(const kvz_hip_chain_picture_rdoq *pictures, int i) { return chain_record_rdoq_shared(pictures, i); }
+
+// the grids of an intra call: the pool of boundaries as tile_pool_pack takes it, and every picture's place in it
+struct chain_tiles { uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS]; int used; pic_tiles pic[KVZ_HIP_MAX_CHAIN_PICTURES]; };
+// What the records ask of the launches.  init_scus: the SCUs of the largest picture that has cbf_out or costs, 0 where none has: the
+// init launch.  The intra stage: the largest tile's wavefront count, a workgroup per LCU row and tile column of the picture with the
+// most, and three planes where a picture has chroma.  The inter stage sizes its launches of the kernel's records (launch_pictures).
+struct chain_plan { int init_scus, waves, groups, planes; };
+
+// Per record: its own checks, homogeneity first; for the intra stage its grid, and the grid's place in the pool (tiles); then its
+// outputs against those of the earlier records.  The inter stage does not depend on tiles: it never looks at a grid, and tiles is
+// not read.  The order is part of the interface (tests/test_chain_host_checks.py and test_chain_multi_rdoq_host_checks.py run this
+// function).  -> the reason, with *at the record that is refused, or nullptr
+template <typename RECORD>
+inline const char *chain_records_why(const RECORD *pictures, int n, bool intra, chain_tiles *tiles, chain_plan *plan, int *at)
+{
+  *plan = { 0, 0, 0, 1 };
+  if (intra) tiles->used = 0;
+  for (int &i = *at = 0; i < n; ++i) {
+    const kvz_hip_chain_picture &p = chain_pic(pictures[i]);
+    if (const char *w = chain_own_why(pictures, i, intra)) return w;
+    if (intra) {
+      // a record without a grid is one tile of lcus_x x lcus_y LCUs: lcus_x + 2 (lcus_y - 1) waves, lcus_y workgroups
+      const kvz_hip_tile_grid *grid = chain_grid(pictures[i]);
+      kvz_hip_tile_grid g;
+      if (!tile_grid_make(grid, p.src.width, p.src.height, &g)) return "invalid tile grid";
+      if (!tile_pool_add(grid, g, tiles->bounds, tiles->used, &tiles->pic[i])) return "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record";
+      const int waves = tile_grid_waves(g), groups = (int)tiles->pic[i].lcus_y * g.cols;
+      if (waves > plan->waves) plan->waves = waves;
+      if (groups > plan->groups) plan->groups = groups;
+      if (p.params.chroma) plan->planes = 3;
+    }
+    if (const char *w = chain_shared_why(pictures, i)) return w;
+    const int scus = (p.src.width >> 2) * (p.src.height >> 2);
+    if ((p.cbf_out || p.costs) && scus > plan->init_scus) plan->init_scus = scus;
+  }
   return nullptr;
 }
 

@@ -3,10 +3,15 @@
 // stage's own tile_source / sl_source / ts_source (they differ between the stages and live in the cores), then cabac_source; or,
 // behind sl_source and without transform skip, rdoq_source.  The
 // pack's type selects the instantiation; inside the kernel a source is found by its type (source_of), whatever else the pack holds.
-// Also here: the body of the stages' init kernels.  Everything has internal linkage, as in the cores.
+// Also here: the body of the stages' init kernels with the init kernel of the multi-picture entries and its launch.
+// Not device code only: the header holds the host code that both stages' record types share and that neither core could hold for the
+// other -- rdoq_source_of, the launch of the init kernel, and the fills of the options of a kernel's per-picture record (fill_lists,
+// fill_trskip, fill_rdoq, fill_tiles), which is why it includes chain_host.h.  The fill of the picture itself differs between the
+// stages and stays beside each core's record.  Everything has internal linkage, as in the cores.
 #pragma once
 
 #include "kvz_hip_internal.h"
+#include "chain_host.h"
 
 using namespace kvzhip;
 
@@ -52,7 +57,31 @@ struct rdoq_source {
   u32 n_sets;
   int skip;
 };
+inline rdoq_source rdoq_source_of(const kvz_hip_rdoq_source &r)
+{
+  return { r.ctx_sets, r.states, r.lcu_ctx, r.tables.quant, r.tables.err_scale, r.n_sets, r.rdoq_skip != 0 };
+}
 template <bool ON> struct rdoq_lcu { static constexpr bool on = false; };
+
+// The options of a checked record of a multi-picture call into the kernel's per-picture record, which starts as zeros: resid_pic_* and
+// intra_pic_* use the same member names on purpose.  The scaling tables (both NULL in a call without them);
+template <typename PIC> void fill_lists(PIC &a, const kvz_hip_scaling_tables &t) { a.quant = t.quant; a.dequant = t.dequant; }
+// transform skip;
+template <typename PIC> void fill_trskip(PIC &a, const kvz_hip_trskip *ts, uint8_t *tr_skip_out)
+{
+  if (ts) { a.lcu_bit_cost = ts->lcu_bit_cost; a.tr_skip_out = tr_skip_out; a.bit_cost = ts->bit_cost; }
+}
+// the picture's own part of RDOQ, which every record of a checked call with RDOQ carries;
+template <typename PIC> void fill_rdoq(PIC &a, const kvz_hip_rdoq_source &r)
+{
+  a.sets = r.ctx_sets; a.states = r.states; a.lcu_ctx = r.lcu_ctx; a.n_sets = r.n_sets;
+}
+// the grid's place in the pool.  The kernel reads cols == 0 as "no grid": a picture without one keeps the zeros, where pic_tiles says
+// one tile
+template <typename PIC> void fill_tiles(PIC &a, const kvz_hip_tile_grid *grid, const pic_tiles &t)
+{
+  if (grid) { a.cols = t.cols; a.rows = t.rows; a.col_at = t.col_at; a.row_at = t.row_at; }
+}
 
 // The body of the init kernels: outputs that the TUs of several planes accumulate into start from zero inside the stage's CUs, and
 // keep their contents elsewhere.  a: the picture's record (cus, cus_stride, cbf_out, cost), i: an SCU of it in raster order, cu_at:
@@ -68,6 +97,27 @@ __device__ __forceinline__ void zero_cu_outputs(const PIC &a, int i, CU_RULE cu_
 #pragma unroll
     for (int j = 0; j < 6; ++j) a.cost[(size_t)i * 6 + j] = 0u;
   }
+}
+
+// The init kernel of the multi-picture entries, for every picture that has cbf_out or costs: grid (blocks of the largest such picture,
+// pictures).  BATCH: the table of per-picture records, CU_RULE: the stage's
+template <typename BATCH, typename CU_RULE>
+__global__ __launch_bounds__(256) void init_pictures_kernel(BATCH b)
+{
+  const auto &a = b.p[blockIdx.y];
+  if (!a.cbf_out && !a.cost) return;
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.cus_stride * (a.height >> 2)) return;
+  zero_cu_outputs(a, i, CU_RULE());
+}
+// init_scus: chain_plan's, 0 where no picture has such an output and nothing is launched
+template <typename CU_RULE, typename BATCH>
+int init_pictures(const BATCH &b, int init_scus, int n_pictures, hipStream_t st)
+{
+  if (!init_scus) return KVZ_HIP_OK;
+  hipLaunchKernelGGL((init_pictures_kernel<BATCH, CU_RULE>), dim3((unsigned)((init_scus + 255) / 256), (unsigned)n_pictures), dim3(256), 0, st, b);
+  KVZ_CHECK_LAUNCH("init_pictures_kernel");
+  return KVZ_HIP_OK;
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // inter_residual_core.h -- the kernels and the host side of the whole-picture inter residual entries (inter_residual.hip: one QP per
 // call and a QP per LCU; inter_residual_sl.hip: scaling lists; inter_residual_ts.hip: transform skip; inter_residual_multi.hip: several pictures in one call;
-// inter_residual_multi_ts.hip: several pictures with scaling lists and transform skip).  Everything here has internal linkage: each translation unit gets
-// its own copy and instantiates its own kernels.  The algorithm is described in inter_residual.hip.
+// inter_residual_multi_ts.hip: several pictures with scaling lists and transform skip; through inter_residual_rdoq_core.h the two RDOQ
+// units, which take the fill of resid_args, the init launch and the 4x4 launch of rdoq_skip from here).  Everything here has internal
+// linkage: each translation unit gets its own copy and instantiates its own kernels.  The algorithm is described in inter_residual.hip.
 #pragma once
 
 #include "kvz_hip_internal.h"
@@ -30,6 +31,18 @@ struct resid_args {
   int cus_stride, lcus_x;
   int width, height;
 };
+// a checked record into the arguments of the single-picture kernels
+inline void fill(resid_args &a, const kvz_hip_chain_picture &p)
+{
+  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+  a.src_y = p.src.y; a.src_u = chroma ? p.src.u : nullptr; a.src_v = chroma ? p.src.v : nullptr;
+  a.rec_y = p.rec_y; a.rec_u = chroma ? p.rec_u : nullptr; a.rec_v = chroma ? p.rec_v : nullptr;
+  a.src_stride_y = p.src.stride_y; a.src_stride_c = p.src.stride_c; a.rec_stride_y = p.stride_y; a.rec_stride_c = p.stride_c;
+  a.coeff_y = p.coeff_y; a.coeff_u = chroma ? p.coeff_u : nullptr; a.coeff_v = chroma ? p.coeff_v : nullptr;
+  a.cus = (u32 *)p.cus; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs;
+  a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
+  a.width = width; a.height = height;
+}
 
 // One picture of a multi-picture call (kvz_hip_inter_residual_frames): resid_args under the same member names, and what a TU derives
 // its constants from (flat_consts with lcu_qp[] or qp, as the per-LCU kernel).  136 bytes; sixteen of them are the kernel's argument,
@@ -115,6 +128,15 @@ __global__ __launch_bounds__(256) void inter_residual_init_kernel(resid_args a, 
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n_scu) return;
   zero_cu_outputs(a, i, inter_cu_rule());
+}
+// launched where the picture has one of the two outputs
+inline int residual_init(const resid_args &a, hipStream_t st)
+{
+  if (!a.cbf_out && !a.cost) return KVZ_HIP_OK;
+  const int n_scu = (a.width >> 2) * (a.height >> 2);
+  hipLaunchKernelGGL(inter_residual_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
+  KVZ_CHECK_LAUNCH("inter_residual_init_kernel");
+  return KVZ_HIP_OK;
 }
 
 // The trailing sources of the kernel below (frame_sources.h), in their order.  The instantiations that an option adds have a
@@ -538,21 +560,11 @@ int residual_frame(const char *entry, const kvz_hip_chain_picture &p, const kvz_
                    const ts_source *skip = nullptr, const cabac_source *price = nullptr)
 {
   if (!chain_picture_args_ok(p, false, SL) || (SL && (!tables || !chain_tables_ok(*tables))) || !chain_one_qp_ok(p)) return kvzhip::invalid_arg(entry);
-  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+  const int chroma = p.params.chroma ? 1 : 0;
   resid_args a;
-  a.src_y = p.src.y; a.src_u = chroma ? p.src.u : nullptr; a.src_v = chroma ? p.src.v : nullptr;
-  a.rec_y = p.rec_y; a.rec_u = chroma ? p.rec_u : nullptr; a.rec_v = chroma ? p.rec_v : nullptr;
-  a.src_stride_y = p.src.stride_y; a.src_stride_c = p.src.stride_c; a.rec_stride_y = p.stride_y; a.rec_stride_c = p.stride_c;
-  a.coeff_y = p.coeff_y; a.coeff_u = chroma ? p.coeff_u : nullptr; a.coeff_v = chroma ? p.coeff_v : nullptr;
-  a.cus = (u32 *)p.cus; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs;
-  a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
-  a.width = width; a.height = height;
+  fill(a, p);
   hipStream_t st = ctx_stream(s);
-  if (p.cbf_out || p.costs) {
-    const int n_scu = (width >> 2) * (height >> 2);
-    hipLaunchKernelGGL(inter_residual_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
-    KVZ_CHECK_LAUNCH("inter_residual_init_kernel");
-  }
+  if (int e = residual_init(a, st)) return e;
   const kvz_hip_quant_params qp = { p.params.qp, p.params.slice_is_intra, p.params.signhide, 0, nullptr, nullptr };
   const lcu_qp_source per_lcu = qp_source_of(p);
   quant_consts ky = {}, kc = {};                                              // read by the kernel without a trailing source only

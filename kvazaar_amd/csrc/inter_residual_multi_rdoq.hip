@@ -3,27 +3,19 @@
 // launch where a picture has cbf_out or costs -- each covering all pictures, the picture being the grid's second dimension.
 //
 // The kernel is inter_residual_rdoq_kernel (inter_residual_rdoq_core.h) with the table of per-picture records as its argument
-// (resid_batch_rdoq): a wave per TU, the slot at blockIdx.x and the picture at blockIdx.y.  The wave reads its picture's record from
-// the kernel arguments with scalar loads, counts that picture's slots itself (a slot beyond them leaves at once) and builds the
-// sources of the single-picture kernel from the record -- every picture has its own context sets, states and set index per LCU; the
-// RDOQ tables and rdoq_skip are the call's.  From there on it is the single-picture kernel's code, hence the same bytes.  With
-// rdoq_skip every 4x4 TU keeps the plain quantiser: that launch is the 4x4 launch of kvz_hip_inter_residual_frames_ts on the same
-// records.  This translation unit is compiled with -ffp-contract=off (Makefile), as rdoq.hip is.
+// (resid_batch_rdoq), behind init_pictures_kernel (frame_sources.h) on the same table: a wave per TU, the slot at blockIdx.x and the
+// picture at blockIdx.y.  The wave reads its picture's record from the kernel arguments with scalar loads, counts that picture's
+// slots itself (a slot beyond them leaves at once) and builds the sources of the single-picture kernel from the record -- every
+// picture has its own context sets, states and set index per LCU; the RDOQ tables and rdoq_skip are the call's.  From there on it is
+// the single-picture kernel's code, hence the same bytes.  With rdoq_skip every 4x4 TU keeps the plain quantiser: that launch is the
+// 4x4 launch of kvz_hip_inter_residual_frames_ts on the same records.  The records are checked by the walk that the six
+// multi-picture entries of the residual stages share (chain_records_why, chain_host.h).  This translation unit is compiled with
+// -ffp-contract=off (Makefile), as rdoq.hip is.
 #include "inter_residual_rdoq_core.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-// inter_residual_init_kernel for every picture that has cbf_out or costs: grid (blocks of the largest such picture, pictures)
-__global__ __launch_bounds__(256) void inter_residual_init_multi_rdoq_kernel(resid_batch_rdoq b)
-{
-  const resid_pic_rdoq &a = b.p[blockIdx.y];
-  if (!a.cbf_out && !a.cost) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.cus_stride * (a.height >> 2)) return;
-  zero_cu_outputs(a, i, inter_cu_rule());
-}
 
 template <int N, bool SL>
 void launch_rdoq_pictures(const resid_batch_rdoq &b, int n_pictures, hipStream_t st)
@@ -78,37 +70,28 @@ int kvz_hip_inter_residual_frames_rdoq(const kvz_hip_chain_picture_rdoq *picture
     for (int i = 0; i < n_pictures; ++i) plain[i] = { pictures[i].pic, nullptr, pictures[i].tables, nullptr, nullptr };
     return kvz_hip_inter_residual_frames_ts(plain, n_pictures, s);
   }
-  const kvz_hip_rdoq_source *first = pictures[0].rdoq;
-  const bool lists = pictures[0].tables.quant || pictures[0].tables.dequant, skip = first && first->rdoq_skip != 0;
+  chain_plan plan;
+  int at;
+  // every record is checked before anything is launched: a refused call writes nothing
+  if (const char *why = chain_records_why(pictures, n_pictures, false, nullptr, &plan, &at)) return refuse_picture(__func__, at, why);
+  const kvz_hip_rdoq_source *first = pictures[0].rdoq;                          // not NULL: some record carries one and the call is homogeneous
+  const bool lists = pictures[0].tables.quant || pictures[0].tables.dequant;
   resid_batch_rdoq b;
   resid_batch_ts_data plain;
   __builtin_memset(&b, 0, sizeof b);
   __builtin_memset(&plain, 0, sizeof plain);
-  int init_scus = 0;
-  // every record is checked before anything is launched: a refused call writes nothing
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_chain_picture_rdoq &r = pictures[i];
-    const kvz_hip_chain_picture &p = r.pic;
-    const char *why = chain_record_rdoq_why(pictures, i, false, lists, skip);
-    if (!why) why = chain_record_rdoq_shared(pictures, i);
-    if (why) return refuse_picture(__func__, i, why);
-    resid_pic_rdoq &a = b.p[i];
-    fill(a, p, p.params.qp);                                                    // the slot clamps it with tables only, as the single entry
-    if (lists) { a.quant = r.tables.quant; a.dequant = r.tables.dequant; }
-    // (record 0 without rdoq passes its own checks; the call is then refused at the first record that carries one)
-    if (r.rdoq) { a.sets = r.rdoq->ctx_sets; a.states = r.rdoq->states; a.lcu_ctx = r.rdoq->lcu_ctx; a.n_sets = r.rdoq->n_sets; }
-    resid_pic_ts &o = plain.p[i];
-    fill(o, p, lists ? clip_lcu_qp(p.params.qp) : p.params.qp);                 // as kvz_hip_inter_residual_frames_ts fills it
-    if (lists) { o.quant = r.tables.quant; o.dequant = r.tables.dequant; }
-    if (p.cbf_out || p.costs) init_scus = max(init_scus, (p.src.width >> 2) * (p.src.height >> 2));
+    fill(b.p[i], r.pic, r.pic.params.qp);                                       // the slot clamps it with tables only, as the single entry
+    fill_lists(b.p[i], r.tables);
+    fill_rdoq(b.p[i], *r.rdoq);
+    fill(plain.p[i], r.pic, lists ? clip_lcu_qp(r.pic.params.qp) : r.pic.params.qp);   // as kvz_hip_inter_residual_frames_ts fills it
+    fill_lists(plain.p[i], r.tables);
   }
-  b.quant = first->tables.quant; b.err_scale = first->tables.err_scale; b.skip = skip;
+  b.quant = first->tables.quant; b.err_scale = first->tables.err_scale; b.skip = first->rdoq_skip != 0;
   hipStream_t st = ctx_stream(s);
   // the launch sequence depends on the sizes, the chroma flags, rdoq_skip and the presence of cbf_out / costs alone
-  if (init_scus) {
-    hipLaunchKernelGGL(inter_residual_init_multi_rdoq_kernel, dim3((unsigned)((init_scus + 255) / 256), (unsigned)n_pictures), dim3(256), 0, st, b);
-    KVZ_CHECK_LAUNCH("inter_residual_init_multi_rdoq_kernel");
-  }
+  if (int e = init_pictures<inter_cu_rule>(b, plan.init_scus, n_pictures, st)) return e;
   return lists ? launch_all<true>(b, plain, n_pictures, st) : launch_all<false>(b, plain, n_pictures, st);
 }
 

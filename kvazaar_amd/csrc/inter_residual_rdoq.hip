@@ -27,7 +27,7 @@ template <bool SL>
 int residual_rdoq_frame(const char *entry, const kvz_hip_chain_picture &p, const kvz_hip_scaling_tables *tables, const rdoq_source &r, kvz_hip_stream s)
 {
   if (!chain_picture_args_ok(p, false, SL) || (SL && !chain_tables_ok(*tables)) || !chain_one_qp_ok(p)) return kvzhip::invalid_arg(entry);
-  const int width = p.src.width, height = p.src.height, chroma = p.params.chroma ? 1 : 0;
+  const int chroma = p.params.chroma ? 1 : 0;
   const kvz_hip_quant_params qp = { p.params.qp, p.params.slice_is_intra, p.params.signhide, 0, nullptr, nullptr };
   quant_consts ky = {}, kc = {};                                              // read by the 4x4 kernel without a trailing source only
   if (!SL && !p.lcu_qp) {
@@ -36,19 +36,9 @@ int residual_rdoq_frame(const char *entry, const kvz_hip_chain_picture &p, const
       if (!make_consts(&qp, n, 0, 0, &ky) || !make_consts(&qp, n, 2, 2, &kc)) return kvzhip::invalid_arg(entry);
   }
   resid_args a;
-  a.src_y = p.src.y; a.src_u = chroma ? p.src.u : nullptr; a.src_v = chroma ? p.src.v : nullptr;
-  a.rec_y = p.rec_y; a.rec_u = chroma ? p.rec_u : nullptr; a.rec_v = chroma ? p.rec_v : nullptr;
-  a.src_stride_y = p.src.stride_y; a.src_stride_c = p.src.stride_c; a.rec_stride_y = p.stride_y; a.rec_stride_c = p.stride_c;
-  a.coeff_y = p.coeff_y; a.coeff_u = chroma ? p.coeff_u : nullptr; a.coeff_v = chroma ? p.coeff_v : nullptr;
-  a.cus = (u32 *)p.cus; a.cbf_out = p.cbf_out; a.cost = (u32 *)p.costs;
-  a.cus_stride = width >> 2; a.lcus_x = (width + 63) >> 6;
-  a.width = width; a.height = height;
+  fill(a, p);
   hipStream_t st = ctx_stream(s);
-  if (p.cbf_out || p.costs) {
-    const int n_scu = (width >> 2) * (height >> 2);
-    hipLaunchKernelGGL(inter_residual_init_kernel, dim3((unsigned)((n_scu + 255) / 256)), dim3(256), 0, st, a, n_scu);
-    KVZ_CHECK_LAUNCH("inter_residual_init_kernel");
-  }
+  if (int e = residual_init(a, st)) return e;
   const lcu_qp_source per_lcu = qp_source_of(p);
   const sl_source lists = { SL ? tables->quant : nullptr, SL ? tables->dequant : nullptr, p.params.qp };
   launch_rdoq_size<32, SL>(a, chroma, st, per_lcu, lists, r);
@@ -86,19 +76,14 @@ int kvz_hip_inter_residual_frame_rdoq(const kvz_hip_ref_picture *src, kvz_hip_pi
     return kvz_hip_inter_residual_frame_sl(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp, tables,
                                            params, s);
   }
-  if (const char *why = chain_rdoq_why(rdoq)) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "invalid argument (%s)", why);
-    return refuse_entry(__func__, msg);
-  }
+  if (const char *why = chain_rdoq_why(rdoq)) return refuse_entry(__func__, invalid_because(why).text);
   kvz_hip_chain_picture p;
   const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, nullptr, coeff_y, coeff_u, coeff_v, cbf_out, costs,
                                          lcu_qp, params);
   if (!packed) return kvzhip::invalid_arg(__func__);
-  const rdoq_source rq = { rdoq->ctx_sets, rdoq->states, rdoq->lcu_ctx, rdoq->tables.quant, rdoq->tables.err_scale, rdoq->n_sets, rdoq->rdoq_skip != 0 };
   // without tables, what the _sl entry refuses without them is refused: scaling_list says whether tables are given
-  if (tables) return residual_rdoq_frame<true>(__func__, p, tables, rq, s);
-  return residual_rdoq_frame<false>(__func__, p, nullptr, rq, s);
+  if (tables) return residual_rdoq_frame<true>(__func__, p, tables, rdoq_source_of(*rdoq), s);
+  return residual_rdoq_frame<false>(__func__, p, nullptr, rdoq_source_of(*rdoq), s);
 }
 
 }  // extern "C"

@@ -5,27 +5,19 @@
 // as many dependent launches as the largest tile of any picture alone.
 //
 // The kernels are the two instantiations of intra_recon_core.h whose argument is the table of per-picture records with the pool of
-// tile boundaries and the call's RDOQ tables (intra_batch_rdoq<SL>): flat lists or tables.  A wave builds its rdoq_source from its
-// picture's record -- every picture has its own context sets, states and set index per LCU -- and stages that picture's set of its LCU
-// (rdoq_lcu<true>::stage); from there on it is the single-picture kernel, hence the same bytes.  The kernels have this translation
-// unit to themselves, so that the other kernels are compiled as they always were, and it is compiled with -ffp-contract=off
-// (Makefile) as rdoq.hip is.
+// tile boundaries and the call's RDOQ tables (intra_batch_rdoq<SL>): flat lists or tables; behind them init_pictures_kernel
+// (frame_sources.h) on the same table.  A wave builds its rdoq_source from its picture's record -- every picture has its own context
+// sets, states and set index per LCU -- and stages that picture's set of its LCU (rdoq_lcu<true>::stage); from there on it is the
+// single-picture kernel, hence the same bytes.  The kernels have this translation unit to themselves, so that the other kernels are
+// compiled as they always were, and it is compiled with -ffp-contract=off (Makefile) as rdoq.hip is.  The records are checked, the
+// pool filled and the launches sized by the walk that the six multi-picture entries of the residual stages share (chain_records_why,
+// chain_host.h).
 #include "rdoq_stage.h"
 #include "intra_recon_core.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-// intra_recon_init_kernel for every picture that has cbf_out or costs: grid (blocks of the largest such picture, pictures)
-__global__ __launch_bounds__(256) void intra_recon_init_multi_rdoq_kernel(intra_batch_rdoq_data b)
-{
-  const intra_pic_rdoq &a = b.p[blockIdx.y];
-  if (!a.cbf_out && !a.cost) return;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.cus_stride * (a.height >> 2)) return;
-  zero_cu_outputs(a, i, intra_cu_rule());
-}
 
 template <bool SL>
 int launch_waves(const intra_batch_rdoq_data &d, int waves, dim3 grid, hipStream_t st)
@@ -54,47 +46,29 @@ int kvz_hip_intra_recon_frames_rdoq(const kvz_hip_chain_picture_rdoq *pictures, 
     for (int i = 0; i < n_pictures; ++i) plain[i] = { pictures[i].pic, pictures[i].grid, pictures[i].tables, nullptr, nullptr };
     return kvz_hip_intra_recon_frames_ts(plain, n_pictures, s);
   }
-  const kvz_hip_rdoq_source *first = pictures[0].rdoq;
-  const bool lists = pictures[0].tables.quant || pictures[0].tables.dequant, skip = first && first->rdoq_skip != 0;
+  chain_tiles tiles;
+  chain_plan plan;
+  int at;
+  // every record is checked before anything is launched: a refused call writes nothing
+  if (const char *why = chain_records_why(pictures, n_pictures, true, &tiles, &plan, &at)) return refuse_picture(__func__, at, why);
+  const kvz_hip_rdoq_source *first = pictures[0].rdoq;                          // not NULL: some record carries one and the call is homogeneous
+  const bool lists = pictures[0].tables.quant || pictures[0].tables.dequant;
   intra_batch_rdoq_data b;
   __builtin_memset(&b, 0, sizeof b);
-  uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
-  int waves = 0, groups = 0, planes = 1, init_scus = 0, used = 0;
-  // every record is checked before anything is launched: a refused call writes nothing
   for (int i = 0; i < n_pictures; ++i) {
     const kvz_hip_chain_picture_rdoq &r = pictures[i];
-    const kvz_hip_chain_picture &p = r.pic;
-    // homogeneity and the record's own checks, its grid and the grid's place in the pool, then the outputs of the earlier records: the
-    // order decides which reason a record with two defects reports
-    const char *why = chain_record_rdoq_why(pictures, i, true, lists, skip);
-    kvz_hip_tile_grid g;
-    pic_tiles t;
-    if (!why && !tile_grid_make(r.grid, p.src.width, p.src.height, &g)) why = "invalid tile grid";
-    if (!why && !tile_pool_add(r.grid, g, bounds, used, &t)) why = "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record";
-    if (!why) why = chain_record_rdoq_shared(pictures, i);
-    if (why) return refuse_picture(__func__, i, why);
-    intra_pic_rdoq &a = b.p[i];
-    fill(a, p, clip_lcu_qp(p.params.qp));                                     // the single-picture entry clamps the picture's QP too
-    if (lists) { a.quant = r.tables.quant; a.dequant = r.tables.dequant; }
-    // (record 0 without rdoq passes its own checks; the call is then refused at the first record that carries one)
-    if (r.rdoq) { a.sets = r.rdoq->ctx_sets; a.states = r.rdoq->states; a.lcu_ctx = r.rdoq->lcu_ctx; a.n_sets = r.rdoq->n_sets; }
-    // the kernel reads cols == 0 as "no grid": a picture without one keeps the zeros, where pic_tiles says one tile
-    if (r.grid) { a.cols = t.cols; a.rows = t.rows; a.col_at = t.col_at; a.row_at = t.row_at; }
-    waves = max(waves, tile_grid_waves(g));
-    groups = max(groups, (int)t.lcus_y * g.cols);
-    if (a.chroma) planes = 3;
-    if (p.cbf_out || p.costs) init_scus = max(init_scus, (a.width >> 2) * (a.height >> 2));
+    fill(b.p[i], r.pic, clip_lcu_qp(r.pic.params.qp));                          // the single-picture entry clamps the picture's QP too
+    fill_lists(b.p[i], r.tables);
+    fill_rdoq(b.p[i], *r.rdoq);
+    fill_tiles(b.p[i], r.grid, tiles.pic[i]);
   }
-  tile_pool_pack(bounds, used, b.bd);
-  b.quant = first->tables.quant; b.err_scale = first->tables.err_scale; b.skip = skip;
+  tile_pool_pack(tiles.bounds, tiles.used, b.bd);
+  b.quant = first->tables.quant; b.err_scale = first->tables.err_scale; b.skip = first->rdoq_skip != 0;
   hipStream_t st = ctx_stream(s);
   // the launch sequence depends on the sizes, the chroma flags, the grids and the presence of cbf_out / costs alone
-  if (init_scus) {
-    hipLaunchKernelGGL(intra_recon_init_multi_rdoq_kernel, dim3((unsigned)((init_scus + 255) / 256), (unsigned)n_pictures), dim3(256), 0, st, b);
-    KVZ_CHECK_LAUNCH("intra_recon_init_multi_rdoq_kernel");
-  }
-  const dim3 grid((unsigned)groups, (unsigned)planes, (unsigned)n_pictures);
-  return lists ? launch_waves<true>(b, waves, grid, st) : launch_waves<false>(b, waves, grid, st);
+  if (int e = init_pictures<intra_cu_rule>(b, plan.init_scus, n_pictures, st)) return e;
+  const dim3 grid((unsigned)plan.groups, (unsigned)plan.planes, (unsigned)n_pictures);
+  return lists ? launch_waves<true>(b, plan.waves, grid, st) : launch_waves<false>(b, plan.waves, grid, st);
 }
 
 }  // extern "C"

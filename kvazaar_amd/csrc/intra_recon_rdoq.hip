@@ -26,11 +26,7 @@ int kvz_hip_intra_recon_frame_rdoq(const kvz_hip_ref_picture *src, kvz_hip_pixel
     return kvz_hip_intra_recon_frame_sl(src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs, lcu_qp,
                                         grid, tables, params, s);
   }
-  if (const char *why = chain_rdoq_why(rdoq)) {
-    char msg[200];
-    snprintf(msg, sizeof msg, "invalid argument (%s)", why);
-    return refuse_entry(__func__, msg);
-  }
+  if (const char *why = chain_rdoq_why(rdoq)) return refuse_entry(__func__, invalid_because(why).text);
   // what the _sl entry refuses: a picture that needs tables without them, and tables for a picture that says it has none
   if (!tables && params && params->scaling_list != 0) return kvzhip::invalid_arg(__func__);
   kvz_hip_chain_picture p;
@@ -38,7 +34,7 @@ int kvz_hip_intra_recon_frame_rdoq(const kvz_hip_ref_picture *src, kvz_hip_pixel
   const bool packed = chain_picture_pack(&p, src, rec_y, stride_y, rec_u, rec_v, stride_c, cus, intra_modes, coeff_y, coeff_u, coeff_v, cbf_out, costs,
                                          lcu_qp, params);
   if (!packed || (tables && !chain_tables_ok(*tables)) || !tile_source_make(p, grid, &tiles)) return kvzhip::invalid_arg(__func__);
-  const rdoq_source rq = { rdoq->ctx_sets, rdoq->states, rdoq->lcu_ctx, rdoq->tables.quant, rdoq->tables.err_scale, rdoq->n_sets, rdoq->rdoq_skip != 0 };
+  const rdoq_source rq = rdoq_source_of(*rdoq);
   if (tables) {
     const sl_source lists = { tables->quant, tables->dequant };
     return intra_frame(__func__, p, s, qp_source_of(p), tiles, lists, rq);

@@ -78,19 +78,25 @@ static kvz_hip_chain_picture_ts clean_ts(int i, bool lists, bool skip)
   return r;
 }
 
-static void report(const char *name, const char *stage, int n, const std::function<const char *(int)> &why)
+// n records as a call of the inter and of the intra entry of their type: the walk that the entries make (chain_records_why), which
+// alone decides the order of the checks.  The intra entry alone reads the grid
+template <typename RECORD>
+static void report(const char *name, int n, const RECORD *r)
 {
-  for (int i = 0; i < n; ++i)
-    if (const char *w = why(i)) {
-      // through refuse_picture, as the entries do: the message names the record
-      refuse_picture("entry", i, w);
-      char head[64];
-      snprintf(head, sizeof head, "entry: invalid argument in picture %d (", i);
-      if (last_message != std::string(head) + w + ")") { printf("%s/%s: MESSAGE %s\n", name, stage, last_message.c_str()); return; }
-      printf("%s/%s: %d %s\n", name, stage, i, w);
-      return;
-    }
-  printf("%s/%s: ok\n", name, stage);
+  for (int intra = 0; intra < 2; ++intra) {
+    const char *stage = intra ? "intra" : "inter";
+    chain_tiles tiles;
+    chain_plan plan;
+    int at = -1;
+    const char *w = chain_records_why(r, n, intra != 0, intra ? &tiles : nullptr, &plan, &at);
+    if (!w) { printf("%s/%s: ok\n", name, stage); continue; }
+    // through refuse_picture, as the entries do: the message names the record
+    refuse_picture("entry", at, w);
+    char head[64];
+    snprintf(head, sizeof head, "entry: invalid argument in picture %d (", at);
+    if (last_message != std::string(head) + w + ")") printf("%s/%s: MESSAGE %s\n", name, stage, last_message.c_str());
+    else printf("%s/%s: %d %s\n", name, stage, at, w);
+  }
 }
 
 // kvz_hip_inter_residual_frames / kvz_hip_intra_recon_frames on n records that `plant` changed
@@ -99,36 +105,16 @@ static void plain_case(const char *name, int n, const std::function<void(kvz_hip
   kvz_hip_chain_picture p[MAX];
   for (int i = 0; i < n; ++i) p[i] = clean(i);
   plant(p);
-  for (int intra = 0; intra < 2; ++intra) report(name, intra ? "intra" : "inter", n, [&](int i) { return chain_record_why(p, i, intra != 0); });
+  report(name, n, p);
 }
 
-// kvz_hip_inter_residual_frames_ts / kvz_hip_intra_recon_frames_ts: the entries' sequence of checks.  The intra entry alone reads the
-// grid, between the record's own checks and the outputs of the earlier records
-static void ts_records(const char *name, int n, const kvz_hip_chain_picture_ts *r)
-{
-  const bool lists = r[0].tables.quant || r[0].tables.dequant, skip = r[0].ts != nullptr;
-  for (int intra = 0; intra < 2; ++intra) {
-    uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
-    int used = 0;
-    report(name, intra ? "intra" : "inter", n, [&](int i) {
-      const char *why = chain_record_ts_why(r, i, intra != 0, lists, skip);
-      if (intra) {
-        kvz_hip_tile_grid g;
-        pic_tiles t;
-        if (!why && !tile_grid_make(r[i].grid, r[i].pic.src.width, r[i].pic.src.height, &g)) why = "invalid tile grid";
-        if (!why && !tile_pool_add(r[i].grid, g, bounds, used, &t)) why = "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record";
-      }
-      if (!why) why = chain_record_ts_shared(r, i);
-      return why;
-    });
-  }
-}
+// kvz_hip_inter_residual_frames_ts / kvz_hip_intra_recon_frames_ts
 static void ts_case(const char *name, int n, bool lists, bool skip, const std::function<void(kvz_hip_chain_picture_ts *)> &plant)
 {
   kvz_hip_chain_picture_ts r[MAX];
   for (int i = 0; i < n; ++i) r[i] = clean_ts(i, lists, skip);
   plant(r);
-  ts_records(name, n, r);
+  report(name, n, r);
 }
 
 // ---- the named checks of the options, and the record of a single-picture entry ----
@@ -215,7 +201,7 @@ static void pool_case(const char *name, int n_grids, int last_cols, int last_row
     r[i].grid = i < n_grids ? &full : i == n_grids ? &last : (i == n_grids + 1 && tail_grid) ? &one : nullptr;
   }
   r[n - 1].pic.coeff_y = nullptr;
-  ts_records(name, n, r);
+  report(name, n, r);
 }
 
 int main()

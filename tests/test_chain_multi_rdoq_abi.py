@@ -146,4 +146,6 @@ def test_the_new_kernels_doubles_stay_unfused_and_the_record_fits_the_arguments(
     assert "sizeof(intra_pic_rdoq) == 208" in core and "sizeof(intra_batch_rdoq<true>) + 8 <= 4096" in core
     for unit in ("inter_residual_multi_rdoq.hip", "intra_recon_multi_rdoq.hip"):
         text = open(os.path.join(csrc, unit)).read()
-        assert "chain_record_rdoq_why(pictures, i" in text and "chain_record_rdoq_shared(pictures, i)" in text and "refuse_picture(__func__, i, why)" in text, unit
+        # the checks are the walk's, which tests/test_chain_multi_rdoq_host_checks.py runs: the unit calls it and spells none itself
+        assert "chain_records_why(pictures, n_pictures, " in text and "return refuse_picture(__func__, at, why);" in text, unit
+        assert "chain_record_rdoq_why(" not in text and "chain_record_rdoq_shared(" not in text and "tile_pool_add(" not in text, unit

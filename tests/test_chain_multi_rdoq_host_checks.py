@@ -1,10 +1,17 @@
 """CPU: the record checks of kvz_hip_inter_residual_frames_rdoq and kvz_hip_intra_recon_frames_rdoq (chain_record_rdoq_why and
 chain_record_rdoq_shared, kvazaar_amd/csrc/chain_host.h) as a host program: the header takes a plain C++17 compiler with kvz_hip.h
-alone.  The program walks the records as the intra entry does -- homogeneity and the record's own checks, the grid and its place in the
-pool, the outputs of the earlier records -- and prints the first record that is refused with its reason.  The order of the checks is
-part of the interface: it decides which reason a record with two defects reports."""
+alone.  The program calls the walk that the entries call (chain_records_why) -- homogeneity and the record's own checks, for the intra
+entry the grid and its place in the pool, the outputs of the earlier records -- and prints the first record that is refused with its
+reason.  The order of the checks is part of the interface: it decides which reason a record with two defects reports.
+
+The walk also returns what the records ask of the launches (chain_plan): the program prints it for the smallest calls at which each
+term can be wrong, for the three record types.  The expected figures follow from the rules, not from the code: a tile of w x h LCUs
+takes w + 2 (h - 1) dependent launches, a picture a workgroup per LCU row and tile column, the init launch the SCUs of the largest
+picture that has cbf_out or costs."""
 import os
 import subprocess
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -67,23 +74,62 @@ static void grid(call &c, int i, int cols, int rows, int lx, int ly)
   c.rec[i].grid = &g;
 }
 
-// the checks of a call in the order of the intra entry (intra_recon_multi_rdoq.hip); the inter entry leaves the grid out
+// record i becomes a picture of another size
+static void size(call &c, int i, int width, int height)
+{
+  kvz_hip_chain_picture &p = c.rec[i].pic;
+  p.src.width = width; p.src.height = height;
+  p.src.stride_y = p.stride_y = (uint32_t)width; p.src.stride_c = p.stride_c = (uint32_t)width / 2;
+}
+
+// the call through the walk that the entries make (chain_records_why, chain_host.h), which alone decides the order of the checks; the
+// inter entry never looks at a grid
 static void report(const char *name, const call &c, bool intra)
 {
-  const kvz_hip_rdoq_source *first = c.rec[0].rdoq;
-  const bool lists = c.rec[0].tables.quant || c.rec[0].tables.dequant, skip = first && first->rdoq_skip != 0;
-  uint16_t bounds[KVZ_HIP_CHAIN_TILE_BOUNDS];
-  int used = 0;
-  for (int i = 0; i < c.n; ++i) {
-    const char *why = chain_record_rdoq_why(c.rec, i, intra, lists, skip);
-    kvz_hip_tile_grid g;
-    pic_tiles t;
-    if (intra && !why && !tile_grid_make(c.rec[i].grid, c.rec[i].pic.src.width, c.rec[i].pic.src.height, &g)) why = "invalid tile grid";
-    if (intra && !why && !tile_pool_add(c.rec[i].grid, g, bounds, used, &t)) why = "the tile grids of the call exceed KVZ_HIP_CHAIN_TILE_BOUNDS boundaries at this record";
-    if (!why) why = chain_record_rdoq_shared(c.rec, i);
-    if (why) { printf("%s: picture %d: %s\n", name, i, why); return; }
-  }
-  printf("%s: ok\n", name);
+  chain_tiles tiles;
+  chain_plan plan;
+  int at = -1;
+  const char *why = chain_records_why(c.rec, c.n, intra, intra ? &tiles : nullptr, &plan, &at);
+  if (why) printf("%s: picture %d: %s\n", name, at, why);
+  else printf("%s: ok\n", name);
+}
+
+// what the walk says the records ask of the launches; the call is accepted
+template <typename RECORD>
+static void plan_of(const char *name, const RECORD *rec, int n, bool intra)
+{
+  chain_tiles tiles;
+  chain_plan plan;
+  int at = -1;
+  const char *why = chain_records_why(rec, n, intra, intra ? &tiles : nullptr, &plan, &at);
+  if (why) printf("plan %s: picture %d: %s\n", name, at, why);
+  else printf("plan %s: waves %d groups %d planes %d init_scus %d\n", name, plan.waves, plan.groups, plan.planes, plan.init_scus);
+}
+
+static void plans()
+{
+  static call c;
+  good(c, 4); plan_of("four untiled 128x64", c.rec, c.n, true);
+  good(c, 4); grid(c, 1, 2, 1, 2, 1); plan_of("2x1 tiles in record 1", c.rec, c.n, true);
+  good(c, 2); size(c, 0, 1024, 512); grid(c, 0, 16, 8, 16, 8); plan_of("16x8 tiles of one LCU beside untiled 128x64", c.rec, c.n, true);
+  good(c, 1, 1024, 512); plan_of("untiled 1024x512", c.rec, c.n, true);
+  good(c, 3); for (int i = 0; i < 3; ++i) c.rec[i].pic.params.chroma = 0;
+  plan_of("4:0:0 only", c.rec, c.n, true);
+  good(c, 3); c.rec[0].pic.params.chroma = 0; c.rec[2].pic.params.chroma = 0; plan_of("4:2:0 among 4:0:0", c.rec, c.n, true);
+  good(c, 3); size(c, 0, 1024, 512); size(c, 2, 1920, 1080); c.rec[1].pic.costs = (kvz_hip_inter_residual_cost *)0x3000;
+  plan_of("costs on the 128x64 record alone", c.rec, c.n, true);
+  plan_of("costs on the 128x64 record alone, inter", c.rec, c.n, false);
+  good(c, 3); size(c, 0, 1024, 512); c.rec[0].pic.cbf_out = (uint8_t *)0x3000; c.rec[1].pic.costs = (kvz_hip_inter_residual_cost *)0x4000;
+  plan_of("cbf_out on 1024x512 beside costs on 128x64", c.rec, c.n, true);
+  // kvz_hip_intra_recon_frames and kvz_hip_intra_recon_frames_ts go through the same code: the embedded pictures as records that have
+  // no grid (one tile each), and as records that carry the grids
+  good(c, 2); size(c, 0, 1024, 512); grid(c, 0, 16, 8, 16, 8);
+  kvz_hip_chain_picture plain[2] = { c.rec[0].pic, c.rec[1].pic };
+  kvz_hip_chain_picture_ts ts[2];
+  static kvz_hip_trskip skip = { 5, 0, nullptr };
+  for (int i = 0; i < 2; ++i) ts[i] = { c.rec[i].pic, c.rec[i].grid, c.rec[i].tables, &skip, (uint8_t *)(uintptr_t)(0x5000 + 0x1000 * i) };
+  plan_of("plain records, 1024x512 and 128x64", plain, 2, true);
+  plan_of("ts records, 1024x512 in 16x8 tiles and 128x64", ts, 2, true);
 }
 
 int main()
@@ -162,6 +208,7 @@ int main()
   grid(c, 9, 9, 8, 16, 8); grid(c, 11, 1, 1, 16, 8); report("no pool in the inter entry", c, false);
   good(c, 12, 1024, 512); for (int i = 0; i < 10; ++i) grid(c, i, 16, 8, 16, 8);
   c.rec[9].pic.rec_y = c.rec[0].pic.rec_y; report("pool before shared outputs", c, true);
+  plans();
   return 0;
 }
 """
@@ -192,8 +239,28 @@ EXPECTED = {
 }
 
 
-def test_record_checks_as_a_host_program(tmp_path):
-    src, exe = tmp_path / "multi_rdoq_checks.cpp", tmp_path / "multi_rdoq_checks"
+# what the records ask of the launches: "waves groups planes init_scus".  128 x 64 is 2 x 1 LCUs (2 waves, 1 workgroup), 1024 x 512 is
+# 16 x 8 (16 + 2 * 7 = 30 waves, 8 workgroups), 1920 x 1080 is 30 x 17 (30 + 2 * 16 = 62, 17)
+EXPECTED_PLAN = {
+    "four untiled 128x64": (2, 1, 3, 0),
+    "2x1 tiles in record 1": (2, 2, 3, 0),                              # its tiles are one LCU, one wave: the untiled records' 2 stand
+    "16x8 tiles of one LCU beside untiled 128x64": (2, 8 * 16, 3, 0),
+    "untiled 1024x512": (30, 8, 3, 0),
+    "4:0:0 only": (2, 1, 1, 0),
+    "4:2:0 among 4:0:0": (2, 1, 3, 0),
+    "costs on the 128x64 record alone": (62, 17, 3, 32 * 16),
+    "costs on the 128x64 record alone, inter": (0, 0, 1, 32 * 16),      # the inter stage sizes its launches of the kernel's records
+    "cbf_out on 1024x512 beside costs on 128x64": (30, 8, 3, 256 * 128),
+    "plain records, 1024x512 and 128x64": (30, 8, 3, 0),
+    "ts records, 1024x512 in 16x8 tiles and 128x64": (2, 8 * 16, 3, 0),
+}
+
+
+@pytest.fixture(scope="module")
+def program_output(tmp_path_factory):
+    """the program's lines, compiled and run once for the module: ({case: verdict}, {case: plan})"""
+    tmp = tmp_path_factory.mktemp("multi_rdoq_checks")
+    src, exe = tmp / "multi_rdoq_checks.cpp", tmp / "multi_rdoq_checks"
     src.write_text(PROGRAM)
     cmd = ["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unused-function", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "kvazaar_amd", "csrc"),
            str(src), "-o", str(exe)]
@@ -202,18 +269,37 @@ def test_record_checks_as_a_host_program(tmp_path):
     r = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert r.returncode == 0, r.stdout
     got = dict(line.split(": ", 1) for line in r.stdout.splitlines())
+    plans = {name[len("plan "):]: got.pop(name) for name in list(got) if name.startswith("plan ")}
+    return got, plans
+
+
+def test_record_checks_as_a_host_program(program_output):
+    got, _ = program_output
     assert got == EXPECTED
 
 
-def test_both_entries_walk_the_records_in_that_order():
+def test_the_walk_returns_the_launch_plan(program_output):
+    _, plans = program_output
+    assert plans == {name: "waves %d groups %d planes %d init_scus %d" % plan for name, plan in EXPECTED_PLAN.items()}
+
+
+UNITS = ("inter_residual_multi.hip", "inter_residual_multi_ts.hip", "inter_residual_multi_rdoq.hip",
+         "intra_recon_multi.hip", "intra_recon_multi_ts.hip", "intra_recon_multi_rdoq.hip")
+
+
+def test_the_six_entries_call_the_walk_and_spell_no_check_themselves():
+    """the order of the checks is executed above; what is left to pin in text is that the entries call what was executed, refuse with
+    what it returned before they launch anything, and check nothing beside it"""
+    import re
     csrc = os.path.join(ROOT, "kvazaar_amd", "csrc")
-    intra = open(os.path.join(csrc, "intra_recon_multi_rdoq.hip")).read()
-    intra = intra[intra.index("int kvz_hip_intra_recon_frames_rdoq("):]
-    at = [intra.index(s) for s in ("chain_record_rdoq_why(pictures, i, true, lists, skip)", "tile_grid_make(r.grid", "tile_pool_add(r.grid",
-                                   "chain_record_rdoq_shared(pictures, i)", "refuse_picture(__func__, i, why)", "hipLaunchKernelGGL(")]
-    assert at == sorted(at)
-    inter = open(os.path.join(csrc, "inter_residual_multi_rdoq.hip")).read()
-    body = inter[inter.index("int kvz_hip_inter_residual_frames_rdoq("):]
-    at = [body.index(s) for s in ("chain_record_rdoq_why(pictures, i, false, lists, skip)", "chain_record_rdoq_shared(pictures, i)",
-                                  "refuse_picture(__func__, i, why)", "hipLaunchKernelGGL(")]
-    assert at == sorted(at) and "tile_grid_make" not in inter
+    for unit in UNITS:
+        text = open(os.path.join(csrc, unit)).read()
+        intra = "true, &tiles" if unit.startswith("intra") else "false, nullptr"
+        call = "if (const char *why = chain_records_why(pictures, n_pictures, %s, &plan, &at)) return refuse_picture(__func__, at, why);" % intra
+        assert text.count("chain_records_why(") == 1 and text.count(call) == 1, unit
+        # the entry launches nothing before the walk: neither itself nor through a helper of its unit
+        entry = text[text.index('extern "C" {'):]
+        before = entry[:entry.index(call)]
+        assert "hipLaunchKernelGGL(" not in before and "launch_" not in before and "init_pictures" not in before and "ctx_stream(" not in before, unit
+        for gone in (r"tile_pool_add\(", r"tile_grid_make\(", r"chain_record_\w*why\(", r"chain_record_\w*shared\(", r"chain_picture_args_ok\("):
+            assert not re.search(gone, text), (unit, gone)
